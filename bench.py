@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): KKT solves/sec + A*D*A' SpMV HBM GB/s on the 1M-row
 synthetic LP, 1/2/4/8 GPUs.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one KKTSolver::Solve (reference src/kkt_solver_diag.cc:82-118: right-hand-side
@@ -59,7 +59,36 @@ def parse():
     ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2 and 5 (config.other_configs)")
     ap.add_argument("--no-direct-exchange", action="store_true",
                     help="N > 1: skip the extra measurement over the direct (hipIpc) exchange (config.direct_exchange)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (x, y of the KKT solve) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, rank, world, x, y, it, errflag):
+    """The arrays a caller of the timed path receives from its last step, as float64 .npy files: the solution x
+    (n + m) and y (m) of KKTSolver::Solve, and [CR iterations, errflag].  Inputs are seeded, so two builds run with
+    the same arguments can be compared file for file (N > 1: each rank writes its own slab, suffix _rank<r>).
+    Beyond 64 MB in all, x and y are cut to a fixed seeded sample of their entries, whose positions are written
+    next to them as <name>_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    out = {"x": x, "y": y}
+    budget = (DUMP_BYTES // world - 4096) // 8           # float64 entries this rank may write, headers aside
+    if x.size + y.size > budget:
+        keep = budget // 2 // 2                          # each of x, y: its sample and the sample's positions
+        rng = np.random.default_rng(12345)
+        for name, v in (("x", x), ("y", y)):
+            idx = np.sort(rng.choice(v.size, min(keep, v.size), replace=False))
+            out[name], out[name + "_index"] = v[idx], idx
+    out["iterations_errflag"] = np.array([it, errflag])
+    for name, v in out.items():
+        np.save(os.path.join(d, name + sfx + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def cpu_baseline(A, st, tol, maxiter):
@@ -260,6 +289,8 @@ def main():
         cr_time += tm.cr
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, x.download(), y.download(), it, errflag)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=tdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
