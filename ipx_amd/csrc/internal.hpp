@@ -274,6 +274,10 @@ constexpr int kAccThreads = 512;
 constexpr int kAccPerThread = 4;
 constexpr int kAccBatch = kAccThreads * kAccPerThread;     // 2048 entries between two barriers
 constexpr int kAccMaxRows = 16384;                         // 128 KB of row sums; 14 bits of row in the entry word
+// workgroups of the persistent tile kernel on the current device: its CU count rounded down to a multiple of 8 (XCDs) and of
+// ns, so that a workgroup's tiles are all of one slice and stay on one XCD; 0 with IPXK_ACC_PERSIST=0 (one workgroup per tile);
+// IPXK_ACC_PERSIST=<g> caps it at g
+int acc_persist_grid(int ns);
 //   * FUSED form (one slice = all of x, for matrices whose gathers have locality; round 4): a tile is a row block of RB rows
 //     (as many as give every CU two tiles), the gathered index is stored relative to the tile's smallest one (`xmin`; the
 //     tile's window of x must span less than 2^18 entries), the row sums start from the epilogue's initial value and the

@@ -13,6 +13,7 @@
 // Every array equals the host builder's bit for bit (tests/test_gpu_layout.py compares them all); the host builder
 // (spmv.hip) stays as that test's reference and as the path of matrices the device path does not cover
 // (long rows, gathered vectors that fit an XCD's L2, gathers with locality: phased / fused / sorted-fused layouts).
+#include <numeric>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -719,8 +720,36 @@ bool device_build_sorted(LayoutScratch& S, SortedMatrix& out, const SlicedMatrix
 // ---------------------------------------------------------------------------
 // accumulated tiles (the arrays of GatherMatrix::build_acc, bit for bit); needs the sliced layout's slices
 // ---------------------------------------------------------------------------
+int acc_persist_grid(int ns) {
+    // IPXK_ACC_PERSIST: unset or 1 = on; 0 = one workgroup per tile; a larger number caps the grid (tests: many tiles per
+    // workgroup on small matrices), still rounded down to a multiple of 8 and of ns
+    static const int setting = [] { const char* e = getenv("IPXK_ACC_PERSIST"); return e ? std::max(0, atoi(e)) : 1; }();
+    if (setting == 0 || ns < 1) return 0;
+    static int cus[64] = {};
+    int dev = 0;
+    IPXK_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) dev = 0;
+    if (cus[dev] == 0) IPXK_HIP(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
+    const int L = std::lcm(8, ns);
+    const int n = setting > 1 ? std::min(setting, cus[dev]) : cus[dev];
+    return std::max(L, n / L * L);
+}
+
 int acc_rows_per_block(int nrows, int ns) {
-    static const int cap = [] { const char* e = getenv("IPXK_ACC_ROWS"); return e && atoi(e) >= 1024 ? std::min(atoi(e), kAccMaxRows) : kAccMaxRows; }();
+    static const int cap = [] { const char* e = getenv("IPXK_ACC_ROWS"); return e && atoi(e) >= 1024 ? std::min(atoi(e), kAccMaxRows) & ~1 : kAccMaxRows; }();
+    static const bool balance = !(getenv("IPXK_ACC_BALANCE") && getenv("IPXK_ACC_BALANCE")[0] == '0');   // (0: measuring aid)
+    // persistent kernel: as many row blocks as fill every workgroup of the grid equally (a multiple of G / ns), each of
+    // ceil(nrows / nrb) rows rounded up to an even number (16-byte partial stores); 1M rows, 8 slices, 256 CUs: 64 blocks of
+    // 15626 rows instead of 62 of 16384 (the last one 576 rows) on the second round of 256 workgroups.  Only while that
+    // shrinks the row block by at most 1/8 (smaller blocks hold fewer entries per line of a slice: 8192 rows cost 14 % per
+    // pass at C3, below); otherwise the rule below
+    if (const int G = balance ? acc_persist_grid(ns) : 0) {
+        const int64_t per = G / ns;
+        const int64_t nrb = (((int64_t)nrows + cap - 1) / cap + per - 1) / per * per;
+        int rb = (int)(((int64_t)nrows + nrb - 1) / nrb);
+        rb += rb & 1;
+        if (rb >= 1024 && 8 * (int64_t)rb >= 7 * (int64_t)cap) return rb;
+    }
     int RB = cap;
     // (at least one tile per CU; halving the row block halves the entries per line of the slice and doubles the waiting entries:
     // 1M x 2M with 8192 rows: 107 us per pass, with 16384: 94)

@@ -367,13 +367,7 @@ static void launch_acc(const AccMatrix& A, const SlicedMatrix& P, int nrows, con
     AccView W;
     W.nrows = nrows; W.nrows_pad = A.nrows_pad; W.nslices = A.nslices; W.nrb = A.nrb; W.RB = A.RB; W.slice_elems = A.slice_elems;
     W.tile_batch = A.tile_batch.get(); W.bptr = A.bptr.get(); W.pack = A.pack.get(); W.val = A.val.get(); W.partial = A.partial.get();
-    static bool lds_attr_set = false;
-    if (!lds_attr_set) {
-        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_tile_kernel<Epi>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(kAccMaxRows * sizeof(double))));
-        lds_attr_set = true;
-    }
-    hipLaunchKernelGGL((spmv_acc_tile_kernel<Epi>), dim3(W.nrb * W.nslices), dim3(kAccThreads), (size_t)W.RB * sizeof(double), s, W, x, done);
+    launch_acc_tiles<Epi>(W, x, done, s);
     SlicedView V = view_of(P, nrows);
     V.nrows_pad = A.nrows_pad; V.partial = A.partial.get();
     const int cg = (int)std::min<int64_t>(1024, std::max<int64_t>(1, ((int64_t)nrows + kBlock - 1) / kBlock));

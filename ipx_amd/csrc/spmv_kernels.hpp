@@ -738,6 +738,144 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, c
     for (int r = 2 * tid; r < M.RB; r += 2 * T) reinterpret_cast<double2*>(dst + r)[0] = make_double2(ac_sum[r], ac_sum[r + 1]);
 }
 
+// The PERSISTENT form of the tile kernel (launch_acc_tiles; IPXK_ACC_PERSIST=0 selects the kernel above).  The grid is a
+// multiple of nslices (acc_persist_grid); workgroup w takes tiles w, w + G, w + 2G, ..., all of slice w % nslices, and runs
+// the pipeline above over the concatenation of their batches, so the first stream loads and batch pointers of the next tile
+// are in flight while the current one finishes.  At a tile boundary each thread moves its row pairs (2 tid + 2 T j) from LDS
+// into registers and zeroes them in place between two barriers; the parked sums leave as 16-byte stores, kAccParkPerBatch
+// pairs after each of the next tile's batches (after that batch's stream loads, so that no s_waitcnt of the pipeline waits
+// for them).  The last tile's sums leave from LDS at the end.  Workgroups never wait for each other; each row sum is the
+// same sequence of ds_add_f64 as in the one-tile kernel, so the partials are equal bit for bit.
+constexpr int kAccParkPairs = kAccMaxRows / (2 * kAccThreads);       // 16 row pairs (64 VGPRs) per thread
+constexpr int kAccParkPerBatch = 2;
+template <class Prod>
+// (the batch tables come as __restrict__ arguments: the partial stores of the loop would otherwise keep the compiler from
+// reading them with scalar loads, and a vector load of a batch pointer waits vmcnt(0) -- for the whole pipeline)
+__global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M, const unsigned* __restrict__ tile_batch,
+                                                                       const unsigned* __restrict__ bptr, const double* __restrict__ x,
+                                                                       const int* done) {
+    if (done && *done) return;
+    extern __shared__ double ac_sum[];
+    constexpr int U = kAccPerThread, T = kAccThreads, NP = kAccParkPairs, PB = kAccParkPerBatch;
+    static_assert(NP % PB == 0, "parked pairs per batch");
+    const int tid = threadIdx.x;
+    const int ntiles = M.nrb * M.nslices, G = gridDim.x;
+    const int s = blockIdx.x % M.nslices;                       // the same for every tile of the workgroup (G % nslices == 0)
+    const double* __restrict__ xs = x + (size_t)s * M.slice_elems;
+    double* const part = M.partial + (size_t)s * M.nrows_pad;
+    // walker over the workgroup's batches (wave-uniform: scalar loads); an empty tile yields one empty batch, so that its
+    // partial is written (zeros) like any other
+    struct Batch { unsigned e0, e1; int tile; };                // tile -1: past the workgroup's last tile
+    int wt = blockIdx.x, wq = 0, wnb = 0;
+    unsigned wb0 = 0;
+    if (wt < ntiles) { wb0 = tile_batch[wt]; wnb = (int)(tile_batch[wt + 1] - wb0); }
+    auto next = [&]() -> Batch {
+        Batch b{0u, 0u, -1};
+        if (wt >= ntiles) return b;
+        b.tile = wt;
+        if (wnb > 0) { b.e0 = bptr[wb0 + wq]; b.e1 = bptr[wb0 + wq + 1]; }
+        if (++wq >= max(wnb, 1)) {
+            wt += G; wq = 0;
+            if (wt < ntiles) { wb0 = tile_batch[wt]; wnb = (int)(tile_batch[wt + 1] - wb0); }
+        }
+        return b;
+    };
+    constexpr int NE = 6;
+    Batch q[NE];                          // q[i] = batch k + i for the current batch k
+#pragma unroll
+    for (int i = 0; i < NE; i++) q[i] = next();
+    unsigned pk[3][U];
+    double v[3][U], xg[2][U];
+    // The loads of an empty batch are issued too, from entry 0 and x[0] (the product has at least one entry and one column):
+    // a load issued on one path only makes the compiler's s_waitcnt after the join count the other path's loads, and an
+    // empty batch k + 1 then turned the adds of batch k into a wait for everything in flight (vmcnt(0)) in every batch.
+    auto stream = [&](unsigned (&pkb)[U], double (&vb)[U], unsigned e0, unsigned e1) {     // entries [e0, e1) of a batch
+        const int ne = (int)(e1 - e0);
+        const unsigned base = ne > 0 ? e0 : 0u;
+        const int last = max(ne - 1, 0);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int i = min(u * T + tid, last);
+            pkb[u] = __builtin_nontemporal_load(M.pack + base + i);
+            vb[u] = __builtin_nontemporal_load(M.val + base + i);
+        }
+    };
+    auto gather = [&](double (&xgb)[U], const unsigned (&pkb)[U], const Batch& b) {
+        const bool live = b.e1 > b.e0;
+        const double* __restrict__ xb = live ? xs : x;
+        const unsigned mask = live ? (1u << kSortedOffBits) - 1u : 0u;
+#pragma unroll
+        for (int u = 0; u < U; u++) xgb[u] = xb[pkb[u] & mask];
+    };
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+#pragma unroll
+        for (int u = 0; u < U; u++) { pk[d][u] = 0u; v[d][u] = 0.0; }
+        stream(pk[d], v[d], q[d].e0, q[d].e1);
+    }
+    for (int r = tid; r < M.RB; r += T) ac_sum[r] = 0.0;
+    gather(xg[0], pk[0], q[0]);
+    int cur = q[0].tile;                  // the tile whose row sums are in LDS
+    // parked row sums of the previous tile: park[0] is row pair prow of pdst, the next PB * pleft pairs follow 2 T rows apart
+    double2 park[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) park[j] = make_double2(0.0, 0.0);
+    int pleft = 0, prow = 0;
+    double* pdst = part;
+    auto store_parked = [&]() {           // PB pairs, then the rest moves down (static register indices)
+#pragma unroll
+        for (int j = 0; j < PB; j++)
+            if (prow + 2 * T * j < M.RB) reinterpret_cast<double2*>(pdst + prow + 2 * T * j)[0] = park[j];
+#pragma unroll
+        for (int j = 0; j + PB < NP; j++) park[j] = park[j + PB];
+        prow += 2 * T * PB;
+        pleft--;
+    };
+    while (q[0].tile >= 0) {
+#pragma unroll
+        for (int d = 0; d < 6; d++) {
+            if (q[0].tile >= 0) {
+                const int ne = (int)(q[0].e1 - q[0].e0);
+                gather(xg[(d + 1) & 1], pk[(d + 1) % 3], q[1]);          // batch k + 1
+                __syncthreads();                  // the adds of the previous batch (first batch: the zeroing) are done
+                if (q[0].tile != cur) {           // first batch of the next tile: park the finished row sums, zero them
+                    while (pleft > 0) store_parked();          // (the tile before had fewer batches than NP / PB)
+#pragma unroll
+                    for (int j = 0; j < NP; j++) {
+                        const int r = 2 * tid + 2 * T * j;
+                        if (r < M.RB) {
+                            park[j] = make_double2(ac_sum[r], ac_sum[r + 1]);
+                            ac_sum[r] = 0.0;
+                            ac_sum[r + 1] = 0.0;
+                        }
+                    }
+                    pdst = part + (size_t)(cur / M.nslices) * M.RB;
+                    prow = 2 * tid;
+                    pleft = NP / PB;
+                    cur = q[0].tile;
+                    __syncthreads();
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++)
+                    if (u * T + tid < ne)
+                        __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), Prod::prod(xg[d & 1][u], v[d % 3][u]), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                stream(pk[d % 3], v[d % 3], q[3].e0, q[3].e1);               // batch k + 3 into the buffer just emptied
+                if (pleft > 0) store_parked();
+#pragma unroll
+                for (int i = 0; i + 1 < NE; i++) q[i] = q[i + 1];
+                q[NE - 1] = next();
+            }
+        }
+    }
+    __syncthreads();
+    while (pleft > 0) store_parked();
+    if (cur >= 0) {
+        double* dst = part + (size_t)(cur / M.nslices) * M.RB;
+        for (int r = 2 * tid; r < M.RB; r += 2 * T) reinterpret_cast<double2*>(dst + r)[0] = make_double2(ac_sum[r], ac_sum[r + 1]);
+    }
+}
+
 // ---- plain rows (small matrices) --------------------------------------------------------------
 // The matrix as it is (the device's plain copy, layout_device.hip): 8 lanes per row, lane k takes entries k, k + 8, ...
 // (coalesced: a wavefront reads 64 consecutive entries), the first lane of the group adds the products in storage
@@ -881,6 +1019,25 @@ __global__ __launch_bounds__(kBlock) void spmv_sliced_combine_kernel(SlicedView 
     }
 }
 
+// The tile kernel of the accumulated tiles (every unmasked product, nmatrix.hip's N N' passes too): the persistent kernel on
+// acc_persist_grid workgroups (at most one per tile), or one workgroup per tile when IPXK_ACC_PERSIST=0.
+template <class Prod>
+inline void launch_acc_tiles(const AccView& W, const double* x, const int* done, hipStream_t s) {
+    static bool lds_attr_set = false;       // per instantiation: dynamic LDS beyond 64 KB has to be allowed once
+    if (!lds_attr_set) {
+        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_tile_kernel<Prod>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(kAccMaxRows * sizeof(double))));
+        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(kAccMaxRows * sizeof(double))));
+        lds_attr_set = true;
+    }
+    const size_t lds = (size_t)W.RB * sizeof(double);
+    const int ntiles = W.nrb * W.nslices, G = acc_persist_grid(W.nslices);
+    if (G > 0) hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod>), dim3(std::min(G, ntiles)), dim3(kAccThreads), lds, s, W, W.tile_batch, W.bptr,
+                                  x, done);
+    else hipLaunchKernelGGL((spmv_acc_tile_kernel<Prod>), dim3(ntiles), dim3(kAccThreads), lds, s, W, x, done);
+}
+
 // COMPACT: use the compacted copy of the tiles (GatherMatrix::compact_tiles) -- the plain kernels on fewer entries
 template <class Epi, bool MASKED = false, bool COMPACT = false>
 inline void launch_spmv_sliced(const GatherMatrix& M, const double* x, const Epi& epi, double* dot_partials,
@@ -889,14 +1046,7 @@ inline void launch_spmv_sliced(const GatherMatrix& M, const double* x, const Epi
     if (M.use_acc && !MASKED && !COMPACT) {
         // accumulated tiles + the sliced layout's combine on their partial vectors
         const AccView W = M.acc_view();
-        const size_t lds = (size_t)W.RB * sizeof(double);
-        static bool lds_attr_set = false;       // per instantiation: dynamic LDS beyond 64 KB has to be allowed once
-        if (!lds_attr_set) {
-            IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_tile_kernel<Epi>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(kAccMaxRows * sizeof(double))));
-            lds_attr_set = true;
-        }
-        hipLaunchKernelGGL((spmv_acc_tile_kernel<Epi>), dim3(W.nrb * W.nslices), dim3(kAccThreads), lds, s, W, x, done);
+        launch_acc_tiles<Epi>(W, x, done, s);
         SlicedView C = M.sliced_view(0);
         C.nrows_pad = W.nrows_pad; C.partial = W.partial;
         hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(M.combine_grid()), dim3(kBlock), 0, s, C, epi, dot_partials, done);
