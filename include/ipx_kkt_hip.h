@@ -578,11 +578,12 @@ ipxint ipxk_normal_apply_bytes(const ipxk_context* ctx);
  * with one slice and the epilogue in the tile kernel, for matrices whose gathers have
  * locality and whose rows are stored sorted: bit-identical to 0, 2, 4, 6).  The sliced layouts are
  * chosen by a property of the matrix (x larger than an XCD's L2 and gathers that
- * spread over the slices), between 1 and 3 the faster at ipxk_create; otherwise a
- * timing picks the fastest of phased, fused and sorted fused, which are
- * bit-identical (IPXK_SPMV_LAYOUT=phased|sliced|fused|sorted|sortedfused overrides);
- * us[6] receives the measured microseconds {pass1 phased, sliced (or sorted, if
- * that was kept), fused (or sorted fused), pass2 likewise} (0 = not timed). */
+ * spread over the slices): 5 when it can be built, else the faster of 1 and 3;
+ * otherwise a timing at ipxk_create picks among the bit-identical 0, 2, 4, 6 and 7
+ * (IPXK_SPMV_LAYOUT=phased|sliced|fused|sorted|sortedfused|acc|plain|accfused
+ * overrides).  us[6] receives the measured microseconds {pass 1: phased, the layout
+ * in use if it is 1, 3 or 5 (else sliced), the layout in use if it is 2, 4, 6 or 7
+ * (else fused); pass 2 likewise} (0 = not timed). */
 int ipxk_spmv_layout(const ipxk_context* ctx, int layout[2], double us[6]);
 /* The guard of the explicit inverses of SplittedNormalMatrix::Prepare's device
  * form (ipxk_split_prepare*): narrow first / last levels of a sweep and large
@@ -617,7 +618,10 @@ ipxint ipxk_split_inverse_refined(const ipxk_context* ctx);
  * sorted.built, nslices, nsub, nrb, RB, nrows_pad, max_sub, slice_elems, fused,
  * nnz, P, G, RT*1e6 + Q*1e3, use_acc, acc.built, nslices, nrb, RB, nrows_pad,
  * slice_elems, # batches, # entries that waited for a later batch, use_acc_fused,
- * accf.built, nrb, RB, # batches, use_plain}. */
+ * accf.built, nrb, RB, # batches, use_plain}.  use_sorted, use_sorted_fused, use_acc,
+ * use_acc_fused and use_plain say whether that is the layout of ipxk_spmv_layout (at
+ * most one of them is 1); use_sliced whether the sliced or fused tiles are built, which
+ * masked products (the basis path) use whatever the layout. */
 int ipxk_layout_info(const ipxk_context* ctx, int which, ipxint info[40],
                      double create_ms[4]);
 /* array: 0 sliced tile_ptr (u32), 1 sliced cnt (u8), 2 sliced idx (i32), 3

@@ -1011,7 +1011,8 @@ int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[40], double c
         IPXK_REQUIRE(c && info && (which == 0 || which == 1), "bad argument");
         const GatherMatrix& M = which == 0 ? c->Acols : c->Arows;
         for (int i = 0; i < 40; i++) info[i] = 0;
-        info[0] = M.use_sliced; info[1] = M.use_sorted; info[2] = M.use_sorted_fused; info[3] = M.nlong;
+        const SpmvLayout L = M.layout;
+        info[0] = M.tile_base() != SpmvLayout::phased; info[1] = L == SpmvLayout::sorted; info[2] = L == SpmvLayout::sortedfused; info[3] = M.nlong;
         info[4] = M.sliced.built; info[5] = M.sliced.R; info[6] = M.sliced.nslices; info[7] = M.sliced.nrb;
         info[8] = M.sliced.nrows_pad; info[9] = M.sliced.max_tile;
         { double d = M.sliced.dominant_fraction; memcpy(&info[10], &d, sizeof d); }
@@ -1019,10 +1020,10 @@ int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[40], double c
         info[15] = M.sorted.RB; info[16] = M.sorted.nrows_pad; info[17] = M.sorted.max_sub; info[18] = M.sorted.slice_elems;
         info[19] = M.sorted.fused; info[20] = M.nnz;
         info[21] = M.P; info[22] = M.G; info[23] = (ipxint)M.RT * 1000000 + (ipxint)M.Q * 1000 + 0;
-        info[24] = M.use_acc; info[25] = M.acc.built; info[26] = M.acc.nslices; info[27] = M.acc.nrb; info[28] = M.acc.RB;
+        info[24] = L == SpmvLayout::acc; info[25] = M.acc.built; info[26] = M.acc.nslices; info[27] = M.acc.nrb; info[28] = M.acc.RB;
         info[29] = M.acc.nrows_pad; info[30] = M.acc.slice_elems; info[31] = M.acc.nbatches; info[32] = M.acc.deferred;
-        info[33] = M.use_acc_fused; info[34] = M.accf.built; info[35] = M.accf.nrb; info[36] = M.accf.RB; info[37] = M.accf.nbatches;
-        info[38] = M.use_plain;
+        info[33] = L == SpmvLayout::accfused; info[34] = M.accf.built; info[35] = M.accf.nrb; info[36] = M.accf.RB; info[37] = M.accf.nbatches;
+        info[38] = L == SpmvLayout::plain;
         if (create_ms) for (int i = 0; i < 4; i++) create_ms[i] = c->create_ms[i];
     });
 }
@@ -1078,14 +1079,16 @@ ipxint ipxk_normal_apply_bytes(const ipxk_context* c) {
 int ipxk_spmv_layout(const ipxk_context* c, int layout[2], double us[6]) {
     return guarded([&] {
         IPXK_REQUIRE(c && layout, "bad argument");
-        auto code = [](const GatherMatrix& M) { return M.use_acc_fused ? 7 : M.use_plain ? 6 : M.use_acc ? 5 : M.use_sorted_fused ? 4 : !M.use_sliced ? 0 : M.sliced.nslices == 1 ? 2 : M.use_sorted ? 3 : 1; };
-        layout[0] = code(c->Acols);
-        layout[1] = code(c->Arows);
-        if (us) {
-            us[0] = c->Acols.tuned_us_phased; us[1] = c->Acols.use_acc ? c->Acols.tuned_us_acc : c->Acols.use_sorted ? c->Acols.tuned_us_sorted : c->Acols.tuned_us_sliced;
-            us[2] = c->Acols.use_acc_fused ? c->Acols.tuned_us_acc_fused : c->Acols.use_plain ? c->Acols.tuned_us_plain : c->Acols.use_sorted_fused ? c->Acols.tuned_us_sorted_fused : c->Acols.tuned_us_fused;
-            us[3] = c->Arows.tuned_us_phased; us[4] = c->Arows.use_acc ? c->Arows.tuned_us_acc : c->Arows.use_sorted ? c->Arows.tuned_us_sorted : c->Arows.tuned_us_sliced;
-            us[5] = c->Arows.use_acc_fused ? c->Arows.tuned_us_acc_fused : c->Arows.use_plain ? c->Arows.tuned_us_plain : c->Arows.use_sorted_fused ? c->Arows.tuned_us_sorted_fused : c->Arows.tuned_us_fused;
+        const GatherMatrix* M[2] = {&c->Acols, &c->Arows};
+        for (int k = 0; k < 2; k++) {
+            const SpmvLayout L = M[k]->layout;
+            layout[k] = (int)L;
+            if (!us) continue;
+            const bool tiles = L == SpmvLayout::sliced || L == SpmvLayout::sorted || L == SpmvLayout::acc;
+            const bool fused = L == SpmvLayout::fused || L == SpmvLayout::sortedfused || L == SpmvLayout::plain || L == SpmvLayout::accfused;
+            us[3 * k] = M[k]->tuned_us[(int)SpmvLayout::phased];
+            us[3 * k + 1] = M[k]->tuned_us[(int)(tiles ? L : SpmvLayout::sliced)];
+            us[3 * k + 2] = M[k]->tuned_us[(int)(fused ? L : SpmvLayout::fused)];
         }
     });
 }

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -305,6 +306,13 @@ struct AccMatrix {
 
 struct LayoutScratch;                 // layout_device.hip
 
+// The layout of a gather matrix's unmasked products; the values are the codes ipxk_spmv_layout reports.
+enum class SpmvLayout { phased, sliced, fused, sorted, sortedfused, acc, plain, accfused };
+constexpr int kNumSpmvLayouts = 8;
+// their names (IPXK_SPMV_LAYOUT, verbose lines; ipx_amd/kkt.py uses the same)
+inline constexpr const char* kSpmvLayoutNames[kNumSpmvLayouts] = {"phased", "sliced", "fused", "sorted", "sortedfused", "acc", "plain",
+                                                                  "accfused"};
+
 struct GatherMatrix {
     int nrows = 0, ncols = 0;
     int64_t nnz = 0;
@@ -338,43 +346,40 @@ struct GatherMatrix {
     bool build_device_local(LayoutScratch& S, int64_t nrows_, int64_t ncols_, int64_t nnz_, const int* dptr, const int* didx,
                             const double* dval, double share, hipStream_t s);
     void set_geometry(int64_t nrows_, int64_t ncols_);      // P, G, RT, Q, RWrows of the phased layout
-    // optional second layout and the choice between the two (IPXK_SPMV_LAYOUT=phased|sliced|auto;
-    // auto times both once at build time on this matrix and keeps the faster one)
+    // The layout of the unmasked launches, chosen by select_layout.  Masked and compacted launches run on the tile base.
+    SpmvLayout layout = SpmvLayout::phased;
+    // the tile base: the sliced or fused tiles when they are built, the phased layout otherwise
+    SpmvLayout tile_base() const { return !sliced.built ? SpmvLayout::phased : sliced.nslices == 1 ? SpmvLayout::fused : SpmvLayout::sliced; }
+    float tuned_us[kNumSpmvLayouts] = {};       // microseconds per product measured by time_layout (0: not timed)
+    float time_layout(SpmvLayout L, hipStream_t s);
+    // The choice of `layout` (spmv.hip has the rules), shared by the host and the device builders: make(L) builds the arrays of
+    // candidate L in place and returns whether it could; the routine times the candidates, keeps the winner and releases the
+    // arrays of the losers.
+    void select_layout(const std::function<bool(SpmvLayout)>& make, hipStream_t s);
+    // XCD-sliced tiles (several slices) or fused tiles (one slice)
     SlicedMatrix sliced;
-    bool use_sliced = false;
-    // the sliced layout's tiles with sorted gathers (bit-identical results: a timing may choose between the two)
+    // the sliced layout's tiles with sorted gathers, or their FUSED form (independent of the sliced layout)
     SortedMatrix sorted;
-    bool use_sorted = false;           // only with use_sliced and sliced.nslices > 1
     void build_sorted(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
-    // accumulated tiles (the sliced layout's slices, row sums in LDS); use_acc: the layout in use for unmasked products
+    void build_sorted_fused(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
+    // accumulated tiles (the sliced layout's slices, row sums in LDS), and their FUSED form
     AccMatrix acc;
-    bool use_acc = false;
-    float tuned_us_acc = 0.f;
     void build_acc(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);     // host builder (test reference)
     void build_acc_fused(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
-    AccMatrix accf;                    // the FUSED form (an overlay for the unmasked launches, like the sorted fused tiles)
-    bool use_acc_fused = false;
-    float tuned_us_acc_fused = 0.f;
+    AccMatrix accf;
     AccView acc_fused_view() const;
     AccView acc_view() const;
-    // plain rows (small matrices): the device's plain copy of the matrix itself, 8 lanes per row (spmv_rowgroup_kernel); an
-    // overlay for the unmasked launches like the sorted fused tiles; set by the caller of build() (the model matrices)
+    // plain rows (small matrices): the device's plain copy of the matrix itself, 8 lanes per row (spmv_rowgroup_kernel); set by
+    // the caller of build() (the model matrices)
     const int* csr_ptr = nullptr;
     const int* csr_idx = nullptr;
     const double* csr_val = nullptr;
-    bool use_plain = false;
-    float tuned_us_plain = 0.f;
     int plain_grid() const { return (int)std::min<int64_t>(kMaxPartials, std::max<int64_t>(1, ((int64_t)nrows * 8 + kBlock - 1) / kBlock)); }
-    // the FUSED form (independent of the sliced layout); use_sorted_fused: it is the layout in use
-    void build_sorted_fused(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
-    bool use_sorted_fused = false;
-    float tuned_us_sorted_fused = 0.f;
     int sorted_fused_grid() const {
         static const int cap = [] { const char* e = getenv("IPXK_SF_GRID"); return e && atoi(e) > 0 ? std::min(atoi(e), kMaxPartials) : kMaxPartials; }();
         return std::min(sorted.nrb, cap);
     }
     SortedView sorted_view() const;
-    float tuned_us_phased = 0.f, tuned_us_sliced = 0.f, tuned_us_fused = 0.f, tuned_us_sorted = 0.f;
     // ns_request: 0 = as many slices as x needs (>= 2), 1 = the fused single-slice variant
     void build_sliced(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s, int ns_request);
     // which: 0 = the matrix, 1 = the masked value array (mask_values), 2 = the compacted copy (compact_tiles)
@@ -385,7 +390,7 @@ struct GatherMatrix {
     GatherView view(bool masked = false) const;
     int grid() const { return G; }
     // Masked products (the basis path's N N' on the model matrix: entries of BASIC / fixed columns count for
-    // nothing): a second value array of the layout in use in which those entries are zero -- the kernels issue no
+    // nothing): a second value array of the tile base in which those entries are zero -- the kernels issue no
     // gather for an entry whose value is zero.  mask_values() fills it from a weight per ROW of the gather matrix
     // (by_row) or per GATHERED index; view(true) / sliced_view(true) show it (launch_spmv<Epi, true>).
     DevBuf<double> valM, lvalM;
@@ -404,11 +409,19 @@ struct GatherMatrix {
     void compact_tiles(const double* weight, bool by_row, hipStream_t s);
     DevBuf<int> rowof;                  // row of every stored short entry (built on first use by mask_values(by_row))
     void mask_values(const double* weight, bool by_row, hipStream_t s);
-    // # dot partials a launch of the phased / sliced / fused layouts produces (the sorted-fused overlay: launch_spmv)
-    int num_partials() const {
-        const int extra = nlong > 0 ? 1 : 0;      // the long-row fix-up kernel adds one
-        if (!use_sliced) return G + extra;
-        return (sliced.nslices == 1 ? fused_grid() : combine_grid()) + extra;   // fused: one dot partial per workgroup
+    // # dot partials a launch writes (launch_spmv returns it; masked launches run on the tile base): one per workgroup of the
+    // kernel that applies the epilogue, then the long-row fix-up's
+    int num_partials(bool masked = false) const {
+        int n;
+        switch (masked ? tile_base() : layout) {
+            case SpmvLayout::phased: n = G; break;
+            case SpmvLayout::fused: n = fused_grid(); break;
+            case SpmvLayout::sortedfused: n = sorted_fused_grid(); break;
+            case SpmvLayout::plain: n = plain_grid(); break;
+            case SpmvLayout::accfused: n = accf.nrb; break;
+            default: n = combine_grid(); break;         // sliced, sorted, acc: the combine kernel
+        }
+        return n + (nlong > 0 ? 1 : 0);
     }
     std::vector<unsigned char> h_row_long;   // host copy of row_long (empty: no long rows)
 };

@@ -245,7 +245,8 @@ bool nmatrix_prepare(Context* c, const double* W) {
     if (getenv("IPXK_REAL_N") && getenv("IPXK_REAL_N")[0] == '0') return false;
     const int m = (int)c->m, n = (int)c->n;
     // only where the gathered vectors need slicing, and no long rows
-    if (!(c->Arows.use_sliced && c->Arows.sliced.nslices > 1 && c->Acols.use_sliced && c->Acols.nlong == 0 && c->Arows.nlong == 0)) return false;
+    if (!(c->Arows.tile_base() == SpmvLayout::sliced && c->Acols.tile_base() != SpmvLayout::phased && c->Acols.nlong == 0 && c->Arows.nlong == 0))
+        return false;
     if (c->nnz >= (int64_t(1) << 31) || n < 1 || m < 1) return false;
     hipStream_t s = c->stream;
     if (!c->nmat) c->nmat = new NMatrix;

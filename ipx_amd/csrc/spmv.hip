@@ -8,6 +8,7 @@
 
 #include <cstdio>
 #include <string>
+#include <utility>
 
 #include "context.hpp"
 #include "spmv_kernels.hpp"
@@ -177,145 +178,136 @@ void GatherMatrix::build(int64_t nrows_, int64_t ncols_, const ipxint* hptr, con
     }
     IPXK_HIP(hipStreamSynchronize(s));  // host vectors go out of scope
 
-    // alternative layouts + choice
-    use_sliced = false;
-    sliced = SlicedMatrix();
-    std::string layout = "auto";
-    if (const char* e = getenv("IPXK_SPMV_LAYOUT")) layout = e;
-    if (layout == "phased") return;
-    use_sorted = false;
-    use_sorted_fused = false;
-    sorted = SortedMatrix();
-    use_acc = false;
-    acc = AccMatrix();
-    use_plain = false;
-    use_acc_fused = false;
-    accf = AccMatrix();
-    if (layout == "plain") { use_plain = csr_ptr != nullptr; return; }
-    if (layout == "accfused") { build_acc_fused(hptr, hidx, hval, s); use_acc_fused = accf.built; return; }
-    if (layout == "acc") {
-        build_sliced(hptr, hidx, hval, s, 0);
-        use_sliced = sliced.built;
-        build_acc(hptr, hidx, hval, s);
-        use_acc = acc.built;
-        return;
-    }
-    if (layout == "sortedfused") {
-        build_sorted_fused(hptr, hidx, hval, s);
-        use_sorted_fused = sorted.built;
-        return;
-    }
-    if (layout == "sliced" || layout == "fused" || layout == "sorted") {
-        build_sliced(hptr, hidx, hval, s, layout == "fused" ? 1 : 0);
-        use_sliced = sliced.built;
-        if (layout == "sorted") { build_sorted(hptr, hidx, hval, s); use_sorted = sorted.built; }
-        return;
-    }
-    // auto.  The phased and the fused layout add a row's products in the same (the reference's) order and give
-    // bit-identical results, so a timing on the spot may choose between them (the phased layout wins ties,
-    // 5 % margin).  The sliced layout associates a row's sum per slice, hence whether it is used must not
-    // depend on a timing: it is chosen by a property of the matrix alone -- x does not fit an XCD's L2 and
-    // the gathers of a row block spread over the slices (share of its fullest slice <= 1.5 / #slices: that
-    // is where confining every XCD to one slice of x pays; measured, C3-sized: uniformly random indices 256
-    // against 300 us per apply, banded ones 240-400 against 190-220).  Timings of all three are recorded.
+    select_layout([&](SpmvLayout L) {
+        switch (L) {
+            case SpmvLayout::phased: return true;
+            case SpmvLayout::sliced:
+            case SpmvLayout::fused: build_sliced(hptr, hidx, hval, s, L == SpmvLayout::fused ? 1 : 0); return sliced.built;
+            case SpmvLayout::sorted: build_sorted(hptr, hidx, hval, s); return sorted.built;
+            case SpmvLayout::sortedfused: build_sorted_fused(hptr, hidx, hval, s); return sorted.built;
+            case SpmvLayout::acc: build_acc(hptr, hidx, hval, s); return acc.built;
+            case SpmvLayout::accfused: build_acc_fused(hptr, hidx, hval, s); return accf.built;
+            case SpmvLayout::plain: return csr_ptr != nullptr;
+        }
+        return false;
+    }, s);
+}
+
+// an IPXK_SPMV_* switch set to 0
+static bool env_off(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '0';
+}
+
+// Times the unmasked product on layout L, whose arrays must be in place: two warm-up launches, then five between events, x = 0.
+float GatherMatrix::time_layout(SpmvLayout L, hipStream_t s) {
+    const SpmvLayout in_use = layout;
+    layout = L;
     DevBuf<double> tx((size_t)std::max(ncols, 1)), tout((size_t)std::max(nrows, 1));
     IPXK_HIP(hipMemsetAsync(tx.get(), 0, tx.size() * sizeof(double), s));
     hipEvent_t e0, e1;
     IPXK_HIP(hipEventCreate(&e0));
     IPXK_HIP(hipEventCreate(&e1));
-    EpiScale epi{{}, nullptr, tout.get()};
-    auto time_current = [&]() {
-        const int reps = 5;
-        for (int w = 0; w < 2; w++) launch_spmv(*this, tx.get(), epi, nullptr, nullptr, s);
-        IPXK_HIP(hipEventRecord(e0, s));
-        for (int r = 0; r < reps; r++) launch_spmv(*this, tx.get(), epi, nullptr, nullptr, s);
-        IPXK_HIP(hipEventRecord(e1, s));
-        IPXK_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        IPXK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return ms * 1e3f / reps;
-    };
-    // small matrices: a few microseconds either way, not worth two more copies of the matrix
-    if (nnz >= (1 << 16) && tune_level > 0) {
-        tuned_us_phased = time_current();
-        SlicedMatrix fusedm, slicedm;
-        build_sliced(hptr, hidx, hval, s, 1);
-        if (sliced.built) { use_sliced = true; tuned_us_fused = time_current(); use_sliced = false; fusedm = std::move(sliced); }
-        sliced = SlicedMatrix();
-        if (tune_level > 1) build_sliced(hptr, hidx, hval, s, 0);
-        if (sliced.built) { use_sliced = true; tuned_us_sliced = time_current(); use_sliced = false; slicedm = std::move(sliced); }
-        sliced = SlicedMatrix();
-        const double share = slicedm.built ? slicedm.dominant_fraction : 1.0;
-        const bool spread = slicedm.built && share <= 1.5 / slicedm.nslices;
-        if (spread) sliced = std::move(slicedm);
-        else if (fusedm.built && tuned_us_fused < 0.95f * tuned_us_phased) sliced = std::move(fusedm);
-        use_sliced = sliced.built;
-        if (!spread && tune_level > 1 && !(getenv("IPXK_SPMV_SORTED") && getenv("IPXK_SPMV_SORTED")[0] == '0')) {
-            // gathers with locality: the fused tiles with the gathers in address order (bit-identical to the phased
-            // and fused layouts, so a timing may choose); kept if it beats what the timing chose so far
-            // (an overlay: masked products -- the basis path's N N' -- keep using the layout chosen above)
-            build_sorted_fused(hptr, hidx, hval, s);
-            if (sorted.built) {
-                use_sorted_fused = true;
-                tuned_us_sorted_fused = time_current();
-                const float best = use_sliced ? tuned_us_fused : tuned_us_phased;
-                if (!(tuned_us_sorted_fused < 0.95f * best)) { use_sorted_fused = false; sorted = SortedMatrix(); }
-            }
-        }
-        if (spread && !(getenv("IPXK_SPMV_SORTED") && getenv("IPXK_SPMV_SORTED")[0] == '0')) {
-            // the same slices with the gathers of a tile in address order: bit-identical partial sums, so the faster
-            // of the two is kept (the sliced arrays stay: the basis path compacts them)
-            build_sorted(hptr, hidx, hval, s);
-            if (sorted.built) {
-                use_sorted = true;
-                tuned_us_sorted = time_current();
-                use_sorted = tuned_us_sorted < tuned_us_sliced || (getenv("IPXK_SPMV_SORTED") && getenv("IPXK_SPMV_SORTED")[0] == '1');
-                if (!use_sorted && !getenv("IPXK_BUILD_ALL_LAYOUTS")) sorted = SortedMatrix();
-            }
-        }
-        if (!spread && tune_level > 1 && !(getenv("IPXK_SPMV_ACC") && getenv("IPXK_SPMV_ACC")[0] == '0')) {
-            // gathers with locality, second candidate: the fused accumulated tiles (bit-identical to the layouts timed above for
-            // rows stored with ascending indices -- build_acc_fused checks that); kept if it beats what was chosen so far
-            build_acc_fused(hptr, hidx, hval, s);
-            if (accf.built) {
-                use_acc_fused = true;
-                tuned_us_acc_fused = time_current();
-                const float best = use_sorted_fused ? tuned_us_sorted_fused : use_sliced ? tuned_us_fused : tuned_us_phased;
-                if (!(tuned_us_acc_fused < 0.95f * best)) { use_acc_fused = false; accf = AccMatrix(); }
-                else if (use_sorted_fused) { use_sorted_fused = false; sorted = SortedMatrix(); }
-            }
-        }
-        if (!spread && !use_acc_fused && csr_ptr && nnz <= (int64_t(4) << 20) && !(getenv("IPXK_SPMV_PLAIN") && getenv("IPXK_SPMV_PLAIN")[0] == '0')) {
-            // small matrices: the plain rows, 8 lanes each (bit-identical to the three layouts timed above); kept if it beats them
-            use_plain = true;
-            tuned_us_plain = time_current();
-            const float best = use_sorted_fused ? tuned_us_sorted_fused : use_sliced ? tuned_us_fused : tuned_us_phased;
-            if (!(tuned_us_plain < 0.95f * best)) use_plain = false;
-        }
-        if (spread && !(getenv("IPXK_SPMV_ACC") && getenv("IPXK_SPMV_ACC")[0] == '0')) {
-            // accumulated tiles: used whenever they can be built (never a timing decision: see build_device)
-            build_acc(hptr, hidx, hval, s);
-            if (acc.built) {
-                use_acc = true;
-                tuned_us_acc = time_current();
-                if (!getenv("IPXK_BUILD_ALL_LAYOUTS")) { use_sorted = false; sorted = SortedMatrix(); }
-            }
-        }
-        if (use_sliced) {        // the phased copy of the entries is not needed any more
-            idx.release(); val.release(); counts.release(); step_ptr.release();
-            wg_chunk_ptr.release(); chunk_start.release(); chunk_info.release(); chunk_step.release();
-        }
-        if (getenv("IPXK_VERBOSE"))
-            fprintf(stderr, "ipxk: gather matrix %d x %d nnz %lld: phased %.1f us, fused %.1f us, sliced %.1f us, sorted %.1f us, plain rows %.1f us (fullest-slice share %.2f) -> %s\n",
-                    nrows, ncols, (long long)nnz, tuned_us_phased, tuned_us_fused, tuned_us_sliced, tuned_us_sorted, tuned_us_plain, share,
-                    use_acc_fused ? "accumulated-fused" : use_plain ? "plain rows" : use_sorted_fused ? "sorted-fused" : !use_sliced ? "phased" : sliced.nslices == 1 ? "fused" : use_sorted ? "sorted" : "sliced");
-        if (getenv("IPXK_VERBOSE") && tuned_us_sorted_fused > 0.f) fprintf(stderr, "ipxk:   sorted-fused %.1f us\n", tuned_us_sorted_fused);
-        if (getenv("IPXK_VERBOSE") && tuned_us_acc_fused > 0.f)
-            fprintf(stderr, "ipxk:   accumulated-fused %.1f us (%d rows per tile, %lld batches, %.1f%% of the entries waited)\n", tuned_us_acc_fused, accf.RB,
-                    (long long)accf.nbatches, accf.built ? 100.0 * (double)accf.deferred / (double)nnz : 0.0);
+    const EpiScale epi{{}, nullptr, tout.get()};
+    const int reps = 5;
+    for (int r = 0; r < 2 + reps; r++) {
+        if (r == 2) IPXK_HIP(hipEventRecord(e0, s));
+        launch_spmv(*this, tx.get(), epi, nullptr, nullptr, s);
     }
+    IPXK_HIP(hipEventRecord(e1, s));
+    IPXK_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    IPXK_HIP(hipEventElapsedTime(&ms, e0, e1));
     IPXK_HIP(hipEventDestroy(e0));
     IPXK_HIP(hipEventDestroy(e1));
+    layout = in_use;
+    return tuned_us[(int)L] = ms * 1e3f / reps;
+}
+
+// The layout choice.  IPXK_SPMV_LAYOUT=<name> forces a layout where it can be built (else the tile base, else the phased layout);
+// unset or "auto":
+//   * the phased, fused, sorted fused, fused accumulated layouts and the plain rows add a row's products in the same (the
+//     reference's) order and give bit-identical results, so a timing on the spot may choose among them: a candidate is kept if
+//     it beats the layout in use by 5 %;
+//   * the sliced layout associates a row's sum per slice, hence whether it is used must not depend on a timing: it is chosen by a
+//     property of the matrix alone -- x does not fit an XCD's L2 and the gathers of a row block spread over the slices (share of
+//     its fullest slice <= 1.5 / #slices: that is where confining every XCD to one slice of x pays; measured, C3-sized: uniformly
+//     random indices 256 against 300 us per apply, banded ones 240-400 against 190-220).  Its sorted sub-tiles give bit-identical
+//     partial sums (the faster of the two is kept); the accumulated tiles give them for rows stored with ascending indices only,
+//     so they are used whenever they can be built, never by a timing.
+// Masked products (the basis path's N N') keep the tile base whatever the choice; the arrays of the candidates that lost are
+// released unless IPXK_BUILD_ALL_LAYOUTS is set (tests: the device builders against the host builders).
+void GatherMatrix::select_layout(const std::function<bool(SpmvLayout)>& make, hipStream_t s) {
+    using L = SpmvLayout;
+    layout = L::phased;
+    sliced = SlicedMatrix(); sorted = SortedMatrix(); acc = AccMatrix(); accf = AccMatrix();
+    if (const char* e = getenv("IPXK_SPMV_LAYOUT")) {
+        for (int f = 0; f < kNumSpmvLayouts; f++) {
+            if (strcmp(e, kSpmvLayoutNames[f]) != 0) continue;
+            if (L(f) == L::sorted || L(f) == L::acc) make(L::sliced);          // their slices
+            layout = make(L(f)) ? L(f) : tile_base();
+            return;
+        }
+    }
+    // small matrices (a few microseconds either way, not worth more copies of the matrix) and auxiliary ones: no timing
+    if (nnz < (1 << 16) || tune_level == 0) return;
+    const bool keep_all = getenv("IPXK_BUILD_ALL_LAYOUTS") != nullptr;
+    auto drop = [&](L l) {                       // (never the tile base: the masked products use it)
+        if (keep_all) return;
+        if (l == L::sorted || l == L::sortedfused) sorted = SortedMatrix();
+        else if (l == L::acc) acc = AccMatrix();
+        else if (l == L::accfused) accf = AccMatrix();
+    };
+    // the tile base (tune_level 1: phased against fused only)
+    const bool phased = make(L::phased);       // (not built by the device builders)
+    if (phased) time_layout(L::phased, s);
+    SlicedMatrix fusedm, slicedm;
+    if (make(L::fused)) { time_layout(L::fused, s); fusedm = std::exchange(sliced, SlicedMatrix()); }
+    if (tune_level > 1 && make(L::sliced)) { time_layout(L::sliced, s); slicedm = std::exchange(sliced, SlicedMatrix()); }
+    const double share = slicedm.built ? slicedm.dominant_fraction : fusedm.built ? fusedm.dominant_fraction : 1.0;
+    const bool spread = slicedm.built && share <= 1.5 / slicedm.nslices;
+    if (spread) {
+        sliced = std::move(slicedm);
+        layout = L::sliced;
+        const bool with_acc = !env_off("IPXK_SPMV_ACC") && make(L::acc);
+        // the sorted sub-tiles: the fall-back of the accumulated tiles
+        if (!env_off("IPXK_SPMV_SORTED") && (!with_acc || keep_all) && make(L::sorted)) {
+            const char* e = getenv("IPXK_SPMV_SORTED");
+            if (time_layout(L::sorted, s) < tuned_us[(int)L::sliced] || (e && e[0] == '1')) layout = L::sorted;
+            else drop(L::sorted);
+        }
+        if (with_acc) {
+            time_layout(L::acc, s);
+            layout = L::acc;
+        }
+    } else {
+        if (fusedm.built && (!phased || tuned_us[(int)L::fused] < 0.95f * tuned_us[(int)L::phased])) {
+            sliced = std::move(fusedm);
+            layout = L::fused;
+        }
+        auto consider = [&](L cand) {
+            if (!make(cand)) return;
+            if (time_layout(cand, s) < 0.95f * tuned_us[(int)layout]) { drop(layout); layout = cand; }
+            else drop(cand);
+        };
+        if (tune_level > 1 && !env_off("IPXK_SPMV_SORTED")) consider(L::sortedfused);
+        if (tune_level > 1 && !env_off("IPXK_SPMV_ACC")) consider(L::accfused);
+        if (layout != L::accfused && nnz <= (int64_t(4) << 20) && !env_off("IPXK_SPMV_PLAIN")) consider(L::plain);
+    }
+    if (sliced.built) {        // the phased copy of the entries is not needed
+        idx.release(); val.release(); counts.release(); step_ptr.release();
+        wg_chunk_ptr.release(); chunk_start.release(); chunk_info.release(); chunk_step.release();
+    }
+    if (getenv("IPXK_VERBOSE")) {
+        fprintf(stderr, "ipxk: gather matrix %d x %d nnz %lld:", nrows, ncols, (long long)nnz);
+        for (int l = 0; l < kNumSpmvLayouts; l++)
+            if (tuned_us[l] > 0.f) fprintf(stderr, " %s %.1f us,", kSpmvLayoutNames[l], tuned_us[l]);
+        fprintf(stderr, " fullest-slice share %.2f -> %s\n", share, kSpmvLayoutNames[(int)layout]);
+        const AccMatrix& a = layout == L::accfused ? accf : acc;
+        if (a.built)
+            fprintf(stderr, "ipxk:   %d rows per tile, %lld batches, %.1f%% of the entries waited\n", a.RB, (long long)a.nbatches,
+                    100.0 * (double)a.deferred / (double)nnz);
+    }
 }
 
 // The device path for matrices whose gathers have locality, or whose gathered vector fits an XCD's L2 (round 4): the fused tiles
@@ -328,63 +320,27 @@ bool GatherMatrix::build_device_local(LayoutScratch& S, int64_t nrows_, int64_t 
     SlicedMatrix fu;
     if (!device_build_sliced(S, fu, (int)nrows_, (int)ncols_, nnz_, dptr, didx, dval, s, 1)) return false;
     nrows = (int)nrows_; ncols = (int)ncols_; nnz = nnz_;
-    set_geometry(nrows_, ncols_);
-    sliced = std::move(fu);                       // (nlong, nseg, ... : set by build_device)
-    sliced.dominant_fraction = share;
-    use_sliced = true;
-    use_sorted = false; use_sorted_fused = false; use_acc = false; use_acc_fused = false; use_plain = false;
-    sorted = SortedMatrix(); acc = AccMatrix(); accf = AccMatrix();
-    DevBuf<double> tx((size_t)std::max(ncols, 1)), tout((size_t)std::max(nrows, 1));
-    IPXK_HIP(hipMemsetAsync(tx.get(), 0, tx.size() * sizeof(double), s));
-    hipEvent_t e0, e1;
-    IPXK_HIP(hipEventCreate(&e0));
-    IPXK_HIP(hipEventCreate(&e1));
-    EpiScale epi{{}, nullptr, tout.get()};
-    auto time_current = [&]() {
-        const int reps = 5;
-        for (int w = 0; w < 2; w++) launch_spmv(*this, tx.get(), epi, nullptr, nullptr, s);
-        IPXK_HIP(hipEventRecord(e0, s));
-        for (int r = 0; r < reps; r++) launch_spmv(*this, tx.get(), epi, nullptr, nullptr, s);
-        IPXK_HIP(hipEventRecord(e1, s));
-        IPXK_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        IPXK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return ms * 1e3f / reps;
-    };
-    const bool keep_all = getenv("IPXK_BUILD_ALL_LAYOUTS") != nullptr;          // (tests: the layouts the timing discards stay built)
-    tuned_us_fused = time_current();
-    float best = tuned_us_fused;
-    SortedMatrix so;
-    if (device_build_sorted_fused(S, so, nrows, ncols, nnz_, dptr, didx, dval, s)) {
-        sorted = std::move(so);
-        use_sorted_fused = true;
-        tuned_us_sorted_fused = time_current();
-        if (tuned_us_sorted_fused < 0.95f * best) best = tuned_us_sorted_fused;
-        else { use_sorted_fused = false; if (!keep_all) sorted = SortedMatrix(); }
-    }
-    AccMatrix af;
-    if (nlong == 0 && !(getenv("IPXK_SPMV_ACC") && getenv("IPXK_SPMV_ACC")[0] == '0') && device_build_acc_fused(S, af, nrows, ncols, nnz_, dptr, didx, dval, s)) {
-        accf = std::move(af);
-        use_acc_fused = true;
-        tuned_us_acc_fused = time_current();
-        if (tuned_us_acc_fused < 0.95f * best) { best = tuned_us_acc_fused; use_sorted_fused = false; if (!keep_all) sorted = SortedMatrix(); }
-        else { use_acc_fused = false; if (!keep_all) accf = AccMatrix(); }
-    }
-    if (!use_acc_fused && csr_ptr && nnz <= (int64_t(4) << 20) && !(getenv("IPXK_SPMV_PLAIN") && getenv("IPXK_SPMV_PLAIN")[0] == '0')) {
-        const bool sf = use_sorted_fused;
-        use_sorted_fused = false;
-        use_plain = true;
-        tuned_us_plain = time_current();
-        if (tuned_us_plain < 0.95f * best) { best = tuned_us_plain; if (!keep_all) sorted = SortedMatrix(); }
-        else { use_plain = false; use_sorted_fused = sf; }
-    }
-    IPXK_HIP(hipEventDestroy(e0));
-    IPXK_HIP(hipEventDestroy(e1));
-    if (getenv("IPXK_VERBOSE"))
-        fprintf(stderr, "ipxk: gather matrix %d x %d nnz %lld built on the device (gathers with locality): fused %.1f us, sorted-fused %.1f us, accumulated-fused %.1f us, "
-                        "plain rows %.1f us (fullest-slice share %.2f) -> %s\n", nrows, ncols, (long long)nnz, tuned_us_fused, tuned_us_sorted_fused,
-                tuned_us_acc_fused, tuned_us_plain, share,
-                use_acc_fused ? "accumulated-fused" : use_plain ? "plain rows" : use_sorted_fused ? "sorted-fused" : "fused");
+    set_geometry(nrows_, ncols_);                 // (nlong, nseg, ... : set by build_device)
+    fu.dominant_fraction = share;
+    select_layout([&](SpmvLayout L) {
+        switch (L) {
+            case SpmvLayout::fused: sliced = std::move(fu); return true;
+            case SpmvLayout::sortedfused: {
+                SortedMatrix so;
+                if (!device_build_sorted_fused(S, so, nrows, ncols, nnz_, dptr, didx, dval, s)) return false;
+                sorted = std::move(so);
+                return true;
+            }
+            case SpmvLayout::accfused: {
+                AccMatrix af;
+                if (nlong > 0 || !device_build_acc_fused(S, af, nrows, ncols, nnz_, dptr, didx, dval, s)) return false;
+                accf = std::move(af);
+                return true;
+            }
+            case SpmvLayout::plain: return csr_ptr != nullptr;
+            default: return false;
+        }
+    }, s);
     return true;
 }
 
@@ -395,7 +351,7 @@ bool GatherMatrix::build_device(LayoutScratch& S, int64_t nrows_, int64_t ncols_
                                 const double* dval, hipStream_t s) {
     if (const char* e = getenv("IPXK_LAYOUT_BUILD")) if (e[0] == 'h') return false;           // host: the test reference
     if (const char* e = getenv("IPXK_SPMV_LAYOUT")) if (std::string(e) != "auto") return false;
-    if (const char* e = getenv("IPXK_SPMV_SORTED")) if (e[0] == '0') return false;
+    if (env_off("IPXK_SPMV_SORTED")) return false;
     if (tune_level < 2 || keep_plain || nnz_ < (1 << 16) || getenv("IPXK_STAMPS")) return false;
     if (nrows_ >= (int64_t(1) << 31) - 1 || ncols_ >= (int64_t(1) << 31) - 1 || nnz_ >= (int64_t(1) << 31) - kLongSeg) return false;
     nlong = 0; nseg = 0;
@@ -420,55 +376,24 @@ bool GatherMatrix::build_device(LayoutScratch& S, int64_t nrows_, int64_t ncols_
     }
     nrows = (int)nrows_; ncols = (int)ncols_; nnz = nnz_;
     set_geometry(nrows_, ncols_);
-    sliced = std::move(sl);
-    use_sliced = true;
-    use_sorted = false; use_sorted_fused = false;
-    sorted = SortedMatrix();
-    acc = AccMatrix(); use_acc = false;
-    const bool want_acc = !(getenv("IPXK_SPMV_ACC") && getenv("IPXK_SPMV_ACC")[0] == '0');
-    AccMatrix ac;
-    if (want_acc && device_build_acc(S, ac, sliced, nrows, ncols, nnz_, dptr, didx, dval, s)) acc = std::move(ac);
-    SortedMatrix so;
-    // (the sorted sub-tiles are the fall-back of the accumulated tiles; both are built only when asked for)
-    if ((!acc.built || getenv("IPXK_BUILD_ALL_LAYOUTS")) && device_build_sorted(S, so, sliced, nrows, ncols, nnz_, dptr, didx, dval, s)) sorted = std::move(so);
-    // sliced against sorted: bit-identical partial sums, the faster one is kept (as in build())
-    DevBuf<double> tx((size_t)std::max(ncols, 1)), tout((size_t)std::max(nrows, 1));
-    IPXK_HIP(hipMemsetAsync(tx.get(), 0, tx.size() * sizeof(double), s));
-    hipEvent_t e0, e1;
-    IPXK_HIP(hipEventCreate(&e0));
-    IPXK_HIP(hipEventCreate(&e1));
-    EpiScale epi{{}, nullptr, tout.get()};
-    auto time_current = [&]() {
-        const int reps = 5;
-        for (int w = 0; w < 2; w++) launch_spmv(*this, tx.get(), epi, nullptr, nullptr, s);
-        IPXK_HIP(hipEventRecord(e0, s));
-        for (int r = 0; r < reps; r++) launch_spmv(*this, tx.get(), epi, nullptr, nullptr, s);
-        IPXK_HIP(hipEventRecord(e1, s));
-        IPXK_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        IPXK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return ms * 1e3f / reps;
-    };
-    tuned_us_sliced = time_current();
-    if (sorted.built) {
-        use_sorted = true;
-        tuned_us_sorted = time_current();
-        use_sorted = tuned_us_sorted < tuned_us_sliced || (getenv("IPXK_SPMV_SORTED") && getenv("IPXK_SPMV_SORTED")[0] == '1');
-        if (!use_sorted && !getenv("IPXK_BUILD_ALL_LAYOUTS")) sorted = SortedMatrix();
-    }
-    if (acc.built) {
-        // used whenever it was built: its row sums equal the sliced layout's bit for bit only for rows stored with
-        // ascending indices, so the choice is a property of the matrix and the environment, never of a timing
-        use_acc = true;
-        tuned_us_acc = time_current();
-    }
-    IPXK_HIP(hipEventDestroy(e0));
-    IPXK_HIP(hipEventDestroy(e1));
-    if (getenv("IPXK_VERBOSE"))
-        fprintf(stderr, "ipxk: gather matrix %d x %d nnz %lld built on the device: sliced %.1f us, sorted %.1f us, accumulated %.1f us (%lld batches, %.1f%% of the entries waited) (fullest-slice share %.2f) -> %s\n",
-                nrows, ncols, (long long)nnz, tuned_us_sliced, tuned_us_sorted, tuned_us_acc, (long long)acc.nbatches,
-                acc.built ? 100.0 * (double)acc.deferred / (double)nnz : 0.0, sliced.dominant_fraction,
-                use_acc ? "accumulated" : use_sorted ? "sorted" : "sliced");
+    select_layout([&](SpmvLayout L) {
+        switch (L) {
+            case SpmvLayout::sliced: sliced = std::move(sl); return true;
+            case SpmvLayout::acc: {
+                AccMatrix ac;
+                if (!device_build_acc(S, ac, sliced, nrows, ncols, nnz_, dptr, didx, dval, s)) return false;
+                acc = std::move(ac);
+                return true;
+            }
+            case SpmvLayout::sorted: {
+                SortedMatrix so;
+                if (!device_build_sorted(S, so, sliced, nrows, ncols, nnz_, dptr, didx, dval, s)) return false;
+                sorted = std::move(so);
+                return true;
+            }
+            default: return false;
+        }
+    }, s);
     nnz = nnz_all;
     return true;
 }
@@ -919,7 +844,7 @@ GatherView GatherMatrix::view(bool use_masked) const {
     V.step_ptr = step_ptr.get(); V.counts = counts.get();
     V.wg_chunk_ptr = wg_chunk_ptr.get(); V.chunk_start = chunk_start.get();
     V.chunk_info = chunk_info.get(); V.chunk_step = chunk_step.get();
-    V.idx = idx.get(); V.val = (use_masked && !use_sliced) ? valM.get() : val.get();
+    V.idx = idx.get(); V.val = (use_masked && tile_base() == SpmvLayout::phased) ? valM.get() : val.get();
     V.row_long = nlong > 0 ? row_long.get() : nullptr;
     V.nseg = nseg; V.seg_p0 = seg_p0.get(); V.seg_p1 = seg_p1.get();
     V.lidx = lidx.get(); V.lval = (use_masked && nlong > 0) ? lvalM.get() : lval.get();
@@ -994,13 +919,14 @@ __global__ void mask_long_rows_kernel(GatherView M, const double* __restrict__ w
 }
 
 void GatherMatrix::mask_values(const double* weight, bool by_row, hipStream_t s) {
-    const int64_t nz = use_sliced ? (int64_t)sliced.idx.size() : (int64_t)idx.size();
-    const int* gidx = use_sliced ? sliced.idx.get() : idx.get();
-    const double* gval = use_sliced ? sliced.val.get() : val.get();
+    const bool tiles = tile_base() != SpmvLayout::phased;
+    const int64_t nz = tiles ? (int64_t)sliced.idx.size() : (int64_t)idx.size();
+    const int* gidx = tiles ? sliced.idx.get() : idx.get();
+    const double* gval = tiles ? sliced.val.get() : val.get();
     if (by_row && rowof.size() == 0 && nz > 0) {
         rowof.resize((size_t)nz);
         IPXK_HIP(hipMemsetAsync(rowof.get(), 0, (size_t)nz * sizeof(int), s));
-        if (use_sliced) {
+        if (tiles) {
             const SlicedView V = sliced_view();
             hipLaunchKernelGGL(rowof_sliced_kernel, dim3(V.nrb * V.nslices), dim3(kBlock), 0, s, V, rowof.get());
         } else {
@@ -1098,7 +1024,7 @@ __global__ __launch_bounds__(kBlock) void compact_fill_kernel(SlicedView M, cons
 
 void GatherMatrix::compact_tiles(const double* weight, bool by_row, hipStream_t s) {
     compact.valid = false;
-    if (!use_sliced || !sliced.built) return;
+    if (tile_base() == SpmvLayout::phased) return;
     const int64_t nz = (int64_t)sliced.idx.size();
     const SlicedView V = sliced_view(0);
     const int ntiles = V.nrb * V.nslices;

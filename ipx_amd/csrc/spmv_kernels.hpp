@@ -1038,25 +1038,12 @@ inline void launch_acc_tiles(const AccView& W, const double* x, const int* done,
     else hipLaunchKernelGGL((spmv_acc_tile_kernel<Prod>), dim3(ntiles), dim3(kAccThreads), lds, s, W, x, done);
 }
 
-// COMPACT: use the compacted copy of the tiles (GatherMatrix::compact_tiles) -- the plain kernels on fewer entries
+// The tile kernel of the sliced / fused tiles and, with several slices, the combine.  COMPACT: the compacted copy of the tiles
+// (GatherMatrix::compact_tiles) -- the plain kernels on fewer entries
 template <class Epi, bool MASKED = false, bool COMPACT = false>
 inline void launch_spmv_sliced(const GatherMatrix& M, const double* x, const Epi& epi, double* dot_partials,
                                const int* done, hipStream_t s) {
     static_assert(!(MASKED && COMPACT), "the compacted copy needs no mask");
-    if (M.use_acc && !MASKED && !COMPACT) {
-        // accumulated tiles + the sliced layout's combine on their partial vectors
-        const AccView W = M.acc_view();
-        launch_acc_tiles<Epi>(W, x, done, s);
-        SlicedView C = M.sliced_view(0);
-        C.nrows_pad = W.nrows_pad; C.partial = W.partial;
-        hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(M.combine_grid()), dim3(kBlock), 0, s, C, epi, dot_partials, done);
-        if (M.nlong > 0) {
-            const GatherView G = M.view(false);
-            hipLaunchKernelGGL(spmv_long_kernel<Epi>, dim3(M.nseg), dim3(kBlock), 0, s, G, x, done);
-            hipLaunchKernelGGL(spmv_long_fixup_kernel<Epi>, dim3(1), dim3(kBlock), 0, s, G, epi, dot_partials, M.combine_grid(), done);
-        }
-        return;
-    }
     const SlicedView V = M.sliced_view(COMPACT ? 2 : MASKED ? 1 : 0);
     const size_t lds = (size_t)(M.sliced.max_tile + M.sliced.max_tile / 32 + 1) * sizeof(double);
     const dim3 grid(V.nrb * V.nslices), block(kBlock);
@@ -1072,78 +1059,76 @@ inline void launch_spmv_sliced(const GatherMatrix& M, const double* x, const Epi
         hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(M.combine_grid()), dim3(kBlock), 0, s, V, epi,
                            dot_partials, done);
     }
-    if (M.nlong > 0) {          // rows of more than kMaxRowLen entries: segment sums + ordered fix-up
-        const GatherView G = M.view(MASKED || COMPACT);
-        hipLaunchKernelGGL(spmv_long_kernel<Epi>, dim3(M.nseg), block, 0, s, G, x, done);
-        hipLaunchKernelGGL(spmv_long_fixup_kernel<Epi>, dim3(1), block, 0, s, G, epi, dot_partials,
-                           V.nslices == 1 ? M.fused_grid() : M.combine_grid(), done);
-    }
 }
 
-// Launches the SpMV (+ long-row kernels when the matrix has long rows).  Returns
-// the number of dot partials written (0 when dot_partials == nullptr).
+// Launches the SpMV on M.layout (masked products: on the tile base) + the long-row kernels when the matrix has long rows.
+// Returns the number of dot partials written (0 when dot_partials == nullptr).
 template <class Epi, bool MASKED = false>
 inline int launch_spmv(const GatherMatrix& M, const double* x, const Epi& epi, double* dot_partials,
                        const int* done, hipStream_t s) {
-    if (M.use_acc_fused && !MASKED) {
-        const AccView W = M.acc_fused_view();
-        static bool lds_attr_set = false;
-        if (!lds_attr_set) {
-            IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_fused_kernel<Epi>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(kAccMaxRows * sizeof(double))));
-            lds_attr_set = true;
+    switch (MASKED ? M.tile_base() : M.layout) {
+        case SpmvLayout::accfused: {
+            const AccView W = M.acc_fused_view();
+            static bool lds_attr_set = false;
+            if (!lds_attr_set) {
+                IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_fused_kernel<Epi>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(kAccMaxRows * sizeof(double))));
+                lds_attr_set = true;
+            }
+            hipLaunchKernelGGL((spmv_acc_fused_kernel<Epi>), dim3(W.nrb), dim3(kAccThreads), (size_t)W.RB * sizeof(double), s, W, x, epi, dot_partials, done);
+            break;
         }
-        hipLaunchKernelGGL((spmv_acc_fused_kernel<Epi>), dim3(W.nrb), dim3(kAccThreads), (size_t)W.RB * sizeof(double), s, W, x, epi, dot_partials, done);
-        return dot_partials ? W.nrb : 0;
-    }
-    if (M.use_plain && !MASKED) {
-        const int grid = M.plain_grid();
-        hipLaunchKernelGGL(spmv_rowgroup_kernel<Epi>, dim3(grid), dim3(kBlock), 0, s, M.nrows, M.csr_ptr, M.csr_idx, M.csr_val,
-                           M.nlong > 0 ? M.row_long.get() : nullptr, x, epi, dot_partials, done);
-        if (M.nlong > 0) {
-            const GatherView G = M.view(false);
-            hipLaunchKernelGGL(spmv_long_kernel<Epi>, dim3(M.nseg), dim3(kBlock), 0, s, G, x, done);
-            hipLaunchKernelGGL(spmv_long_fixup_kernel<Epi>, dim3(1), dim3(kBlock), 0, s, G, epi, dot_partials, grid, done);
+        case SpmvLayout::plain:
+            hipLaunchKernelGGL(spmv_rowgroup_kernel<Epi>, dim3(M.plain_grid()), dim3(kBlock), 0, s, M.nrows, M.csr_ptr, M.csr_idx, M.csr_val,
+                               M.nlong > 0 ? M.row_long.get() : nullptr, x, epi, dot_partials, done);
+            break;
+        case SpmvLayout::sortedfused: {
+            const SortedView W = M.sorted_view();
+            const size_t lds = (size_t)(M.sorted.max_sub + M.sorted.max_sub / 32 + 1) * sizeof(double);
+            const dim3 grid(M.sorted_fused_grid()), block(kSortedThreads);
+            switch (W.RB / kSortedThreads) {
+                case 32: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 32>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
+                case 16: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 16>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
+                case 8: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 8>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
+                case 4: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 4>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
+                case 2: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 2>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
+                default: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 1>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
+            }
+            break;
         }
-        return dot_partials ? grid + (M.nlong > 0 ? 1 : 0) : 0;
-    }
-    if (M.use_sorted_fused && !MASKED) {
-        const SortedView W = M.sorted_view();
-        const size_t lds = (size_t)(M.sorted.max_sub + M.sorted.max_sub / 32 + 1) * sizeof(double);
-        const dim3 grid(M.sorted_fused_grid()), block(kSortedThreads);
-        switch (W.RB / kSortedThreads) {
-            case 32: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 32>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
-            case 16: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 16>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
-            case 8: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 8>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
-            case 4: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 4>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
-            case 2: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 2>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
-            default: hipLaunchKernelGGL((spmv_sorted_fused_kernel<Epi, 1>), grid, block, lds, s, W, x, epi, dot_partials, done); break;
+        case SpmvLayout::acc: {         // accumulated tiles + the sliced layout's combine on their partial vectors
+            const AccView W = M.acc_view();
+            launch_acc_tiles<Epi>(W, x, done, s);
+            SlicedView C = M.sliced_view(0);
+            C.nrows_pad = W.nrows_pad; C.partial = W.partial;
+            hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(M.combine_grid()), dim3(kBlock), 0, s, C, epi, dot_partials, done);
+            break;
         }
-        if (M.nlong > 0) {
-            const GatherView G = M.view(false);
-            hipLaunchKernelGGL(spmv_long_kernel<Epi>, dim3(M.nseg), dim3(kBlock), 0, s, G, x, done);
-            hipLaunchKernelGGL(spmv_long_fixup_kernel<Epi>, dim3(1), dim3(kBlock), 0, s, G, epi, dot_partials, M.sorted_fused_grid(), done);
+        case SpmvLayout::sliced:
+        case SpmvLayout::fused:
+        case SpmvLayout::sorted:        // (runs the sliced layout's kernels)
+            if (MASKED && M.compact.valid) launch_spmv_sliced<Epi, false, true>(M, x, epi, dot_partials, done, s);
+            else launch_spmv_sliced<Epi, MASKED>(M, x, epi, dot_partials, done, s);
+            break;
+        case SpmvLayout::phased: {
+            const GatherView V = M.view(MASKED);
+            const dim3 grid(M.G), block(kBlock);
+            switch (M.RT) {
+                case 1: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 1, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
+                case 2: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 2, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
+                case 4: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 4, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
+                default: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 8, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
+            }
+            break;
         }
-        return dot_partials ? M.sorted_fused_grid() + (M.nlong > 0 ? 1 : 0) : 0;
     }
-    if (M.use_sliced) {
-        if (MASKED && M.compact.valid) launch_spmv_sliced<Epi, false, true>(M, x, epi, dot_partials, done, s);
-        else launch_spmv_sliced<Epi, MASKED>(M, x, epi, dot_partials, done, s);
-        return dot_partials ? M.num_partials() : 0;
+    const int np = M.num_partials(MASKED);
+    if (M.nlong > 0) {          // rows of more than kMaxRowLen entries: segment sums + ordered fix-up, whose dot partial comes last
+        const GatherView G = M.view(MASKED);
+        hipLaunchKernelGGL(spmv_long_kernel<Epi>, dim3(M.nseg), dim3(kBlock), 0, s, G, x, done);
+        hipLaunchKernelGGL(spmv_long_fixup_kernel<Epi>, dim3(1), dim3(kBlock), 0, s, G, epi, dot_partials, np - 1, done);
     }
-    const GatherView V = M.view(MASKED);
-    const dim3 grid(M.G), block(kBlock);
-    switch (M.RT) {
-        case 1: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 1, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
-        case 2: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 2, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
-        case 4: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 4, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
-        default: hipLaunchKernelGGL((spmv_phased_kernel<Epi, 8, MASKED>), grid, block, 0, s, V, x, epi, dot_partials, done); break;
-    }
-    if (M.nlong > 0) {
-        hipLaunchKernelGGL(spmv_long_kernel<Epi>, dim3(M.nseg), block, 0, s, V, x, done);
-        hipLaunchKernelGGL(spmv_long_fixup_kernel<Epi>, dim3(1), block, 0, s, V, epi, dot_partials, M.G, done);
-    }
-    return dot_partials ? M.num_partials() : 0;
+    return dot_partials ? np : 0;
 }
 
 }  // namespace ipxk
