@@ -133,6 +133,8 @@ int ipxk_set_interrupt(ipxk_context* ctx, ipxint (*interrupt)(void* user), void*
  * after an unstable exchange, like Basis::TightenLuPivotTol (src/basis.cc:490-503) -- is set to lu_pivottol
  * (Control::lu_pivottol(), src/basis.cc:30; <= 0: 0.1).  The model and its layouts stay; workspaces stay allocated. */
 int ipxk_reset_solver_state(ipxk_context* ctx, double lu_pivottol);
+/* # dense columns of Model::FindDenseColumns (src/model.cc:34-56).  After ipxk_comm_init / ipxk_comm_init_columns:
+ * of the WHOLE partitioned matrix, the same number on every rank (a rank of the column partition may own none). */
 ipxint ipxk_num_dense_cols(const ipxk_context* ctx);
 /* The locality-recovering renumbering of the model ("row/column reordering ... must stay a pure permutation").
  * ipxk_create looks for one -- breadth-first levels of the bipartite graph rows <-> columns from a pseudo-peripheral row, rows
@@ -167,7 +169,12 @@ int ipxk_normal_apply(ipxk_context* ctx, const double* rhs, double* lhs,
 
 /* ---- DiagonalPrecond (src/diagonal_precond.h:25-57) ---------------------- */
 /* Factorize (src/diagonal_precond.cc:17-111); *errflag = 0 or
- * IPX_ERROR_lapack_chol (401). */
+ * IPX_ERROR_lapack_chol (401).  On a partitioned system the dense-column (Sherman-Morrison-Woodbury) form
+ * factorizes the Schur complement of the whole matrix on every rank: all ranks hold the same k x k factor
+ * bit for bit and return the same errflag.  Row partition: one all-reduce of k^2 doubles here and one of k
+ * doubles per ipxk_diag_apply (lhs is this rank's slice; ipxk_diag_get returns the local diagonal and the
+ * global factor).  Column partition: the dense columns of all ranks are gathered once per communicator and
+ * the k dense weights per Factorize; Apply exchanges nothing (its vectors are replicated). */
 int ipxk_diag_factorize(ipxk_context* ctx, const double* W,
                         int precond_dense_cols, ipxint* errflag);
 /* _Apply (src/diagonal_precond.cc:121-159) */
@@ -538,14 +545,21 @@ int ipxk_ipm_driver_basis(ipxk_context* ctx, const double* b, const double* c,
 int ipxk_comm_unique_id(void* id128);
 /* The context must have been created from this rank's row slab (m = local
  * rows, all n columns, row indices local).  After this call dot products and
- * norms of the CR loop are global and ipxk_normal_apply all-reduces A_g' y_g. */
+ * norms of the CR loop are global and ipxk_normal_apply all-reduces A_g' y_g.
+ * Collective: the dense columns are classified once more from the column
+ * counts of the whole matrix (one all-reduce of n), so that every rank treats
+ * the same dense columns (ipxk_num_dense_cols, dense-column preconditioning). */
 int ipxk_comm_init(ipxk_context* ctx, const void* id128, int rank, int nranks);
 /* Alternative partition ("column partition"): the context
  * was created from this rank's slab of structural COLUMNS (all m rows, n =
  * local columns).  Vector arguments then are [local structural part; all m
  * slack entries] for (n+m)-vectors and full m-vectors; every m-vector and
  * every scalar of the CR loop is replicated, the one exchange step per
- * NormalMatrix::_Apply is the all-reduce of the m partial sums A_g t_g. */
+ * NormalMatrix::_Apply is the all-reduce of the m partial sums A_g t_g.
+ * Collective: the dense columns are classified from a histogram of the column
+ * counts of all ranks (an all-reduce of 1 and one of max count + 1 doubles);
+ * each rank keeps the dense columns it owns, and the first Factorize with
+ * dense-column preconditioning gathers those of every rank. */
 int ipxk_comm_init_columns(ipxk_context* ctx, const void* id128, int rank, int nranks);
 /* What the transport itself reports about the communicator of this context:
  * transport 0 = none, 1 = RCCL (nranks / rank from ncclCommCount /

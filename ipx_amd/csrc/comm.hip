@@ -349,21 +349,29 @@ bool comm_active(const Context* c) {
 bool comm_rows(const Context* c) { return comm_active(c) && !c->col_partition; }
 bool comm_cols(const Context* c) { return comm_active(c) && c->col_partition; }
 
+// The direct transport's exchange buffer holds max(n, m) local doubles (comm_init).  An operand larger than that (the
+// k x k Schur complement, the gathered dense columns) goes in consecutive chunks of at most that size; anything that
+// fits is one collective, as before.
+static void direct_allreduce(Context* c, double* buf, size_t count, int op) {
+    const size_t cap = c->direct->capacity;
+    for (size_t o = 0; o < count; o += cap) c->direct->allreduce(c, buf + o, std::min(cap, count - o), op);
+}
+
 void comm_allreduce_min(Context* c, double* buf, size_t count) {
     if (!comm_active(c) || count == 0) return;
-    if (c->direct) { c->direct->allreduce(c, buf, count, 2); return; }
+    if (c->direct) { direct_allreduce(c, buf, count, 2); return; }
     check(rccl().all_reduce(buf, buf, count, kNcclFloat64, kNcclMin, c->comm, c->stream), "ncclAllReduce");
 }
 
 void comm_allreduce_sum(Context* c, double* buf, size_t count) {
     if (!comm_active(c) || count == 0) return;
-    if (c->direct) { c->direct->allreduce(c, buf, count, 0); return; }
+    if (c->direct) { direct_allreduce(c, buf, count, 0); return; }
     check(rccl().all_reduce(buf, buf, count, kNcclFloat64, kNcclSum, c->comm, c->stream), "ncclAllReduce");
 }
 
 void comm_allreduce_max(Context* c, double* buf, size_t count) {
     if (!comm_active(c) || count == 0) return;
-    if (c->direct) { c->direct->allreduce(c, buf, count, 1); return; }
+    if (c->direct) { direct_allreduce(c, buf, count, 1); return; }
     check(rccl().all_reduce(buf, buf, count, kNcclFloat64, kNcclMax, c->comm, c->stream), "ncclAllReduce");
 }
 
@@ -374,7 +382,20 @@ void comm_allgather(Context* c, const double* send, double* recv, size_t count_p
                                     c->stream));
         return;
     }
-    if (c->direct) { c->direct->allgather(c, send, recv, count_per_rank); return; }
+    if (c->direct) {
+        const size_t cap = c->direct->capacity;
+        if (count_per_rank <= cap) { c->direct->allgather(c, send, recv, count_per_rank); return; }
+        // in chunks: chunk o of every rank lands in a scratch table, then at recv[p * count_per_rank + o ...]
+        DevBuf<double> tmp(cap * (size_t)c->nranks);
+        for (size_t o = 0; o < count_per_rank; o += cap) {
+            const size_t len = std::min(cap, count_per_rank - o);
+            c->direct->allgather(c, send + o, tmp.get(), len);
+            IPXK_HIP(hipMemcpy2DAsync(recv + o, count_per_rank * sizeof(double), tmp.get(), len * sizeof(double),
+                                      len * sizeof(double), (size_t)c->nranks, hipMemcpyDeviceToDevice, c->stream));
+        }
+        IPXK_HIP(hipStreamSynchronize(c->stream));     // before the scratch table goes
+        return;
+    }
     check(rccl().all_gather(send, recv, count_per_rank, kNcclFloat64, c->comm, c->stream), "ncclAllGather");
 }
 
@@ -447,18 +468,21 @@ static int comm_init_impl(ipxk_context* c, const void* id128, int rank, int nran
         c->col_partition = columns;
         if (columns) {          // every rank holds all m rows
             c->m_global = c->m;
-            return IPXK_OK;
+        } else {
+            // global row count (defines the default iteration cap m+100 identically on every rank)
+            DevBuf<double> cnt(1);
+            const double mine = (double)c->m;
+            IPXK_HIP(hipMemcpyAsync(cnt.get(), &mine, sizeof(double), hipMemcpyHostToDevice, c->stream));
+            if (c->direct) c->direct->allreduce(c, cnt.get(), 1, 0);
+            else check(rccl().all_reduce(cnt.get(), cnt.get(), 1, kNcclFloat64, kNcclSum, c->comm, c->stream), "ncclAllReduce");
+            double total = 0.0;
+            IPXK_HIP(hipMemcpyAsync(&total, cnt.get(), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            IPXK_HIP(hipStreamSynchronize(c->stream));
+            c->m_global = (int64_t)(total + 0.5);
         }
-        // global row count (defines the default iteration cap m+100 identically on every rank)
-        DevBuf<double> cnt(1);
-        const double mine = (double)c->m;
-        IPXK_HIP(hipMemcpyAsync(cnt.get(), &mine, sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (c->direct) c->direct->allreduce(c, cnt.get(), 1, 0);
-        else check(rccl().all_reduce(cnt.get(), cnt.get(), 1, kNcclFloat64, kNcclSum, c->comm, c->stream), "ncclAllReduce");
-        double total = 0.0;
-        IPXK_HIP(hipMemcpyAsync(&total, cnt.get(), sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        IPXK_HIP(hipStreamSynchronize(c->stream));
-        c->m_global = (int64_t)(total + 0.5);
+        // one dense-column classification for the whole matrix, the same on every rank; with partitioned columns the
+        // dense columns of the other ranks join this rank's at the next Factorize
+        if (comm_active(c) && (classify_dense_columns_global(c) || (columns && c->num_dense > 0))) reset_dense_columns(c);
         return IPXK_OK;
     } catch (const Error& e) {
         set_last_error(e.what());

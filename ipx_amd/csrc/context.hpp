@@ -97,6 +97,11 @@ struct Context {
     DevBuf<int> schur_colptr;
     DevBuf<int> chol_info;
     DevBuf<unsigned char> dense_mask;   // n, 1 for dense columns
+    // column partition: # dense columns of every rank (AdCols / AdRows then hold all of them, rank order, then local
+    // order) and the gathered dense weights
+    std::vector<int> dense_rank_k;
+    DevBuf<double> dense_W, dense_Wsend, dense_Wrecv;
+    DevBuf<int> dense_Widx;
 
     // ---- CR workspaces (m-vectors) ----
     DevBuf<double> v_rhs, v_lhs, v_residual, v_sresidual, v_step, v_Cstep, v_Cres, v_pCstep;
@@ -210,10 +215,13 @@ void finish_out(Context* c, double* user, const double* dev, size_t len);
 void normal_apply_dev(Context* c, const double* W, const double* rhs, double* lhs, int* ndot,
                       const int* done);
 void build_model(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax);
+// partitioned contexts: dense-column classification of the whole matrix (comm_init); true if it changed
+bool classify_dense_columns_global(Context* c);
 void debug_single_pass(Context* c, int which, const double* x, double* out);
 
 // ---- precond.hip ----
 void prepare_dense_columns(Context* c);   // model-dependent part of the dense-column preconditioner (precond.hip)
+void reset_dense_columns(Context* c);     // drops what was built from an earlier classification
 void diag_factorize_dev(Context* c, const double* W, bool precond_dense_cols, ipxint* errflag);
 // lhs = P rhs; partial dot rhs'lhs -> part(slot); returns # partials
 int diag_apply_dev(Context* c, const double* rhs, double* lhs, int slot, const int* done);

@@ -4,6 +4,9 @@
 //     S = inv(Wd) + Ad' inv(E) Ad is assembled column by column with the same SpMV
 //     kernel and factorized by an in-library dense Cholesky (the GPU box has no LAPACK).
 //   _Apply (:121-159): lhs = rhs ./ diagonal, or the Sherman-Morrison-Woodbury form.
+//   Partitioned: with rows partitioned S is a sum over the ranks of their rows' terms (one
+//   all-reduce of k^2 per Factorize, one of k per Apply); with columns partitioned every rank gathers all dense
+//   columns once and then runs the unpartitioned code on replicated vectors (one all-gather of k per Factorize).
 #include "context.hpp"
 #include "spmv_kernels.hpp"
 
@@ -42,6 +45,12 @@ __global__ void copy_mask_kernel(int n, const double* __restrict__ W,
                                  const unsigned char* __restrict__ is_dense, double* __restrict__ out) {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
         out[j] = is_dense[j] ? 0.0 : W[j];
+}
+
+// out[i] = W[idx[i]]
+__global__ void gather_weights_kernel(int len, const int* __restrict__ idx, const double* __restrict__ W,
+                                      double* __restrict__ out) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x) out[i] = W[idx[i]];
 }
 
 // u[Ai[p]] = set ? Ax[p]/diag[Ai[p]] : 0 over one column         (:76-78)
@@ -345,14 +354,71 @@ static int vec_grid(int64_t len) {
 // ---------------------------------------------------------------------------
 // Factorize
 // ---------------------------------------------------------------------------
+// Column partition: the dense columns of every rank, in rank order and then in local order (= ascending global column
+// order, the slabs being contiguous).  One all-gather of the sizes, one of [column counts; row indices; values] padded
+// to the largest rank's share; a rank without dense columns takes part all the same.
+static void gather_dense_columns(Context* c, std::vector<ipxint>& Cp, std::vector<ipxint>& Ci, std::vector<double>& Cx) {
+    hipStream_t s = c->stream;
+    const int R = c->nranks;
+    std::vector<ipxint> lp, li;
+    std::vector<double> lx;
+    fetch_columns(c, c->dense_cols, lp, li, lx);
+    const int64_t kl = (int64_t)c->dense_cols.size(), nzl = lp[(size_t)kl];
+    DevBuf<double> dsz(2), dszall((size_t)2 * R);
+    const double sz[2] = {(double)kl, (double)nzl};
+    dsz.upload(sz, 2, s);
+    comm_allgather(c, dsz.get(), dszall.get(), 2);
+    std::vector<double> szall((size_t)2 * R);
+    dszall.download(szall.data(), szall.size(), s);
+    IPXK_HIP(hipStreamSynchronize(s));
+    comm_check(c);
+    int64_t kmax = 0, nzmax = 0;
+    for (int p = 0; p < R; p++) { kmax = std::max(kmax, (int64_t)szall[2 * p]); nzmax = std::max(nzmax, (int64_t)szall[2 * p + 1]); }
+    const size_t per = (size_t)(kmax + 2 * nzmax);          // doubles hold counts and row indices exactly
+    std::vector<double> send(std::max<size_t>(per, 1), 0.0), recv(std::max<size_t>(per, 1) * R);
+    for (int64_t kk = 0; kk < kl; kk++) send[(size_t)kk] = (double)(lp[(size_t)kk + 1] - lp[(size_t)kk]);
+    for (int64_t p = 0; p < nzl; p++) {
+        send[(size_t)(kmax + p)] = (double)li[(size_t)p];
+        send[(size_t)(kmax + nzmax + p)] = lx[(size_t)p];
+    }
+    DevBuf<double> dsend, drecv(recv.size());
+    dsend.upload(send, s);
+    comm_allgather(c, dsend.get(), drecv.get(), std::max<size_t>(per, 1));
+    drecv.download(recv.data(), recv.size(), s);
+    IPXK_HIP(hipStreamSynchronize(s));
+    comm_check(c);
+    c->dense_rank_k.assign((size_t)R, 0);
+    Cp.assign(1, 0);
+    Ci.clear();
+    Cx.clear();
+    for (int p = 0; p < R; p++) {
+        const double* q = recv.data() + (size_t)p * std::max<size_t>(per, 1);
+        const int64_t kp = (int64_t)szall[2 * p];
+        c->dense_rank_k[(size_t)p] = (int)kp;
+        int64_t off = 0;
+        for (int64_t kk = 0; kk < kp; kk++) {
+            const int64_t len = (int64_t)q[kk];
+            for (int64_t e = off; e < off + len; e++) {
+                Ci.push_back((ipxint)q[kmax + e]);
+                Cx.push_back(q[kmax + nzmax + e]);
+            }
+            off += len;
+            Cp.push_back(Cp.back() + len);
+        }
+    }
+}
+
 static void build_dense_structures(Context* c) {
     // Ad as "rows = dense columns" (CopyColumns) and its transpose Atdense
     // (src/diagonal_precond.cc:59-65), both host-built once per model.
-    const int64_t k = (int64_t)c->dense_cols.size(), m = c->m;
-    if (c->AdCols.nrows == k && c->AdRows.nrows == m && k > 0) return;
+    const int64_t k = comm_cols(c) ? c->num_dense : (int64_t)c->dense_cols.size(), m = c->m;
+    if (c->AdCols.nrows == k && c->AdRows.nrows == m && k > 0 && (!comm_cols(c) || c->dense_rank_k.size() == (size_t)c->nranks))
+        return;
     std::vector<ipxint> Cp, Ci;
     std::vector<double> Cx;
-    fetch_columns(c, c->dense_cols, Cp, Ci, Cx);     // from the device's plain copy of the model
+    if (comm_cols(c)) gather_dense_columns(c, Cp, Ci, Cx);
+    else fetch_columns(c, c->dense_cols, Cp, Ci, Cx);     // from the device's plain copy of the model
+    IPXK_REQUIRE((int64_t)Cp.size() == k + 1, "dense columns: the ranks disagree on their number");
     // transpose (counting sort, ascending dense-column position within a row)
     std::vector<ipxint> Tp(m + 1, 0), Ti(Ci.size());
     std::vector<double> Tx(Ci.size());
@@ -367,7 +433,10 @@ static void build_dense_structures(Context* c) {
         }
     c->AdCols.keep_plain = true;
     c->AdCols.tune_level = 0;           // k long rows: the long-row kernels do all the work in any layout
-    c->AdRows.tune_level = 1;           // m short rows gathering from k numbers: phased against fused
+    // m short rows gathering from k numbers: phased against fused.  Not with partitioned columns: there every rank
+    // computes the same replicated product, and a choice by timing could differ between ranks (another layout,
+    // other dot partials, other bits) -- the phased layout on every rank.
+    c->AdRows.tune_level = comm_cols(c) ? 0 : 1;
     c->AdCols.build(k, m, Cp.data(), Ci.data(), Cx.data(), c->stream);
     c->AdRows.build(m, k, Tp.data(), Ti.data(), Tx.data(), c->stream);
     c->chol.resize((size_t)k * k);
@@ -399,6 +468,20 @@ void prepare_dense_columns(Context* c) {
     IPXK_HIP(hipStreamSynchronize(s));
 }
 
+// After comm_init changed the classification: everything built from the earlier one goes and is built again at the next
+// Factorize (the gather matrices of the dense columns, the mask, the Schur structures, the factor).
+void reset_dense_columns(Context* c) {
+    c->AdCols = GatherMatrix();
+    c->AdRows = GatherMatrix();
+    c->dense_mask.release();
+    c->schur_colptr.release();
+    c->schur_panel.release();
+    c->dense_rank_k.clear();
+    c->kdense = 0;
+    c->diag_factorized = false;
+    c->kkt_diag_factorized = false;
+}
+
 void diag_factorize_dev(Context* c, const double* W, bool precond_dense_cols, ipxint* errflag) {
     const int64_t m = c->m, n = c->n;
     hipStream_t s = c->stream;
@@ -406,9 +489,6 @@ void diag_factorize_dev(Context* c, const double* W, bool precond_dense_cols, ip
     c->diag_factorized = false;
     c->diagonal.resize(m);
     const bool smw = precond_dense_cols && c->num_dense > 0;
-    if (smw && comm_active(c))
-        throw Error(IPXK_E_UNSUPPORTED, "dense-column (SMW) preconditioning is not available on a partitioned "
-                                        "system: pass precond_dense_cols = 0");
     const double* Wcols = W;
     if (smw) {
         c->Wnodense.resize(n);
@@ -437,11 +517,36 @@ void diag_factorize_dev(Context* c, const double* W, bool precond_dense_cols, ip
     c->kdense = 0;
     if (smw) {
         build_dense_structures(c);
-        const int k = (int)c->dense_cols.size();
+        const int k = (int)c->AdCols.nrows;
         // :68-85 Schur complement, one column per dense column
         IPXK_HIP(hipMemsetAsync(c->smw_u.get(), 0, sizeof(double) * m, s));
         std::vector<int> dc(k);
-        for (int kk = 0; kk < k; kk++) dc[kk] = (int)c->dense_cols[kk];
+        const double* Wd = W;                 // W of dense column c at Wd[dc[c]]
+        if (comm_cols(c)) {
+            // the weights of all k dense columns, gathered in the order of AdCols
+            const int R = c->nranks, kl = (int)c->dense_cols.size();
+            const int kmax = std::max(1, *std::max_element(c->dense_rank_k.begin(), c->dense_rank_k.end()));
+            std::vector<int> li(kl);
+            for (int kk = 0; kk < kl; kk++) li[kk] = (int)c->dense_cols[kk];
+            c->dense_Wsend.resize(kmax);
+            c->dense_Wrecv.resize((size_t)kmax * R);
+            c->dense_W.resize(k);
+            IPXK_HIP(hipMemsetAsync(c->dense_Wsend.get(), 0, sizeof(double) * kmax, s));
+            if (kl > 0) {
+                c->dense_Widx.upload(li, s);
+                hipLaunchKernelGGL(gather_weights_kernel, dim3(1), dim3(kBlock), 0, s, kl, c->dense_Widx.get(), W,
+                                   c->dense_Wsend.get());
+            }
+            comm_allgather(c, c->dense_Wsend.get(), c->dense_Wrecv.get(), (size_t)kmax);
+            for (int p = 0, at = 0; p < R; at += c->dense_rank_k[p], p++)
+                if (c->dense_rank_k[p] > 0)
+                    IPXK_HIP(hipMemcpyAsync(c->dense_W.get() + at, c->dense_Wrecv.get() + (size_t)p * kmax,
+                                            sizeof(double) * c->dense_rank_k[p], hipMemcpyDeviceToDevice, s));
+            for (int kk = 0; kk < k; kk++) dc[kk] = kk;
+            Wd = c->dense_W.get();
+        } else {
+            for (int kk = 0; kk < k; kk++) dc[kk] = (int)c->dense_cols[kk];
+        }
         DevBuf<int> dcols;
         dcols.upload(dc, s);
         const bool blocked = (int64_t)m * k * 8 <= (int64_t(8) << 30) && !(getenv("IPXK_SCHUR_BLOCKED") && getenv("IPXK_SCHUR_BLOCKED")[0] == '0');
@@ -480,8 +585,10 @@ void diag_factorize_dev(Context* c, const double* W, bool precond_dense_cols, ip
                                c->AdCols.plain_idx.get(), c->AdCols.plain_val.get(), c->diagonal.get(),
                                c->smw_u.get(), 0);
         }
+        // rows partitioned: every rank formed its rows' share Ad_g' inv(E_g) Ad_g; all ranks factorize the same sum
+        if (comm_rows(c)) comm_allreduce_sum(c, c->chol.get(), (size_t)k * k);
         hipLaunchKernelGGL(schur_add_diag_kernel, dim3((k + 63) / 64), dim3(64), 0, s, k, dcols.get(),
-                           W, c->chol.get());
+                           Wd, c->chol.get());
         // :88-92
         if (k <= 64) {
             hipLaunchKernelGGL(cholesky_lower_kernel, dim3(1), dim3(64), 0, s, k, c->chol.get(), c->chol_info.get());
@@ -502,6 +609,7 @@ void diag_factorize_dev(Context* c, const double* W, bool precond_dense_cols, ip
         int info = 0;
         c->chol_info.download(&info, 1, s);
         IPXK_HIP(hipStreamSynchronize(s));
+        comm_check(c);
         if (info != 0) {
             *errflag = 401;  // IPX_ERROR_lapack_chol
             return;
@@ -530,8 +638,13 @@ int diag_apply_dev(Context* c, const double* rhs, double* lhs, int slot, const i
     // :135-137 work = Ad' * (rhs ./ diagonal)
     hipLaunchKernelGGL(divide_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, rhs,
                        c->diagonal.get(), c->smw_u.get(), done);
-    EpiScale es{{}, nullptr, c->smw_work.get()};
+    // rows partitioned: a partial of this rank's rows, summed over the ranks (written into the exchange buffer directly
+    // where the transport has one); columns partitioned: the vectors are replicated, nothing to exchange
+    double* stage = comm_rows(c) ? comm_stage(c, (size_t)k) : nullptr;
+    EpiScale es{{}, nullptr, stage ? stage : c->smw_work.get()};
     launch_spmv(c->AdCols, c->smw_u.get(), es, nullptr, done, s);
+    if (stage) comm_allreduce_sum_staged(c, c->smw_work.get(), (size_t)k);
+    else if (comm_rows(c)) comm_allreduce_sum(c, c->smw_work.get(), (size_t)k);
     // :140-141
     if (k <= 64)
         hipLaunchKernelGGL(potrs_wave_kernel, dim3(1), dim3(64), 0, s, k, c->chol.get(),

@@ -1060,34 +1060,96 @@ void GatherMatrix::compact_tiles(const double* weight, bool by_row, hipStream_t 
 // Dense-column classification of Model::FindDenseColumns (src/model.cc:34-56): with the column counts in ascending
 // order, the first count that exceeds max(40, 10 * its predecessor) is the threshold.  Equal neighbours never
 // satisfy that, so it is enough to walk the DISTINCT counts in ascending order (a histogram instead of a sort).
-static void find_dense_columns(Context* c) {
-    const int64_t n = c->n, m = c->m;
-    c->num_dense = 0;
-    c->nz_dense = m + 1;
-    c->dense_cols.clear();
-    if (n < 2) return;
-    ipxint maxcnt = 0;
-    for (int64_t j = 0; j < n; j++) maxcnt = std::max(maxcnt, c->h_Ap[j + 1] - c->h_Ap[j]);
-    std::vector<int64_t> hist((size_t)maxcnt + 1, 0);
-    for (int64_t j = 0; j < n; j++) hist[(size_t)(c->h_Ap[j + 1] - c->h_Ap[j])]++;
-    ipxint prev = -1;
-    int64_t below = 0;                  // # columns with a smaller count
-    for (ipxint v = 0; v <= maxcnt; v++) {
+// hist[v] = # columns with v entries, ncols their sum; sets num_dense and nz_dense (m + 1: no dense column).
+static void dense_threshold(const std::vector<int64_t>& hist, int64_t ncols, int64_t m, int64_t* num_dense, int64_t* nz_dense) {
+    *num_dense = 0;
+    *nz_dense = m + 1;
+    if (ncols < 2) return;
+    int64_t prev = -1, below = 0;       // below: # columns with a smaller count
+    for (int64_t v = 0; v < (int64_t)hist.size(); v++) {
         if (hist[(size_t)v] == 0) continue;
-        if (prev >= 0 && v > std::max<ipxint>(40, 10 * prev)) {
-            c->num_dense = n - below;
-            c->nz_dense = v;
+        if (prev >= 0 && v > std::max<int64_t>(40, 10 * prev)) {
+            *num_dense = ncols - below;
+            *nz_dense = v;
             break;
         }
         prev = v;
         below += hist[(size_t)v];
     }
-    if (c->num_dense > 1000) {
-        c->num_dense = 0;
-        c->nz_dense = m + 1;
+    if (*num_dense > 1000) {
+        *num_dense = 0;
+        *nz_dense = m + 1;
     }
+}
+
+static void find_dense_columns(Context* c) {
+    const int64_t n = c->n, m = c->m;
+    c->dense_cols.clear();
+    ipxint maxcnt = 0;
+    for (int64_t j = 0; j < n; j++) maxcnt = std::max(maxcnt, c->h_Ap[j + 1] - c->h_Ap[j]);
+    std::vector<int64_t> hist((size_t)maxcnt + 1, 0);
+    for (int64_t j = 0; j < n; j++) hist[(size_t)(c->h_Ap[j + 1] - c->h_Ap[j])]++;
+    dense_threshold(hist, n, m, &c->num_dense, &c->nz_dense);
     for (int64_t j = 0; j < n; j++)
         if (c->h_Ap[j + 1] - c->h_Ap[j] >= c->nz_dense) c->dense_cols.push_back(j);
+}
+
+// The same classification for the whole partitioned matrix, identical on every rank (comm_init).  Row partition: the
+// counts of the n columns are summed over the ranks (one all-reduce of n).  Column partition: the counts are global
+// already, but the rule looks at the counts of ALL columns -- the largest count (all-reduce max), then a histogram of
+// the counts (all-reduce sum of maxcnt + 1 bins).  m is the global row count.  dense_cols keeps local column
+// indices: under the column partition only the dense columns this rank owns.  Returns whether the classification
+// differs from the one the context had (built from its own slab alone).
+bool classify_dense_columns_global(Context* c) {
+    const int64_t n = c->n;
+    hipStream_t s = c->stream;
+    std::vector<int64_t> cnt((size_t)n), hist;
+    for (int64_t j = 0; j < n; j++) cnt[(size_t)j] = c->h_Ap[j + 1] - c->h_Ap[j];
+    int64_t ncols = n;
+    if (comm_rows(c)) {
+        std::vector<double> h(cnt.begin(), cnt.end());
+        DevBuf<double> d;
+        d.upload(h, s);
+        comm_allreduce_sum(c, d.get(), (size_t)n);
+        d.download(h.data(), (size_t)n, s);
+        IPXK_HIP(hipStreamSynchronize(s));
+        comm_check(c);
+        int64_t maxcnt = 0;
+        for (int64_t j = 0; j < n; j++) { cnt[(size_t)j] = (int64_t)h[(size_t)j]; maxcnt = std::max(maxcnt, cnt[(size_t)j]); }
+        hist.assign((size_t)maxcnt + 1, 0);
+        for (int64_t j = 0; j < n; j++) hist[(size_t)cnt[(size_t)j]]++;
+    } else {
+        double mx = 0.0;
+        for (int64_t j = 0; j < n; j++) mx = std::max(mx, (double)cnt[(size_t)j]);
+        DevBuf<double> d(1);
+        d.upload(&mx, 1, s);
+        comm_allreduce_max(c, d.get(), 1);
+        d.download(&mx, 1, s);
+        IPXK_HIP(hipStreamSynchronize(s));
+        comm_check(c);
+        const int64_t maxcnt = (int64_t)mx;
+        std::vector<double> h((size_t)maxcnt + 1, 0.0);
+        for (int64_t j = 0; j < n; j++) h[(size_t)cnt[(size_t)j]] += 1.0;
+        DevBuf<double> dh;
+        dh.upload(h, s);
+        comm_allreduce_sum(c, dh.get(), h.size());
+        dh.download(h.data(), h.size(), s);
+        IPXK_HIP(hipStreamSynchronize(s));
+        comm_check(c);
+        hist.assign(h.size(), 0);
+        ncols = 0;
+        for (size_t v = 0; v < h.size(); v++) { hist[v] = (int64_t)h[v]; ncols += hist[v]; }
+    }
+    int64_t num_dense = 0, nz_dense = 0;
+    dense_threshold(hist, ncols, c->m_global, &num_dense, &nz_dense);
+    std::vector<ipxint> cols;
+    for (int64_t j = 0; j < n; j++)
+        if (cnt[(size_t)j] >= nz_dense) cols.push_back(j);
+    const bool changed = num_dense != c->num_dense || nz_dense != c->nz_dense || cols != c->dense_cols;
+    c->num_dense = num_dense;
+    c->nz_dense = nz_dense;
+    c->dense_cols = cols;
+    return changed;
 }
 
 static double ms_since(std::chrono::steady_clock::time_point& t0) {

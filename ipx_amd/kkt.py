@@ -684,7 +684,12 @@ class KktContext:
         return bytes(buf)
 
     def comm_init(self, unique_id, rank, nranks, columns=False):
-        """columns=False: the context holds this rank's rows; True: its structural columns."""
+        """columns=False: the context holds this rank's rows; True: its structural columns.
+
+        Collective over the ranks.  It also classifies the dense columns of the whole matrix, so num_dense_cols
+        is the same on every rank, and dense-column (Sherman-Morrison-Woodbury) preconditioning works on either
+        partition: with rows, diag_apply returns this rank's slice and diag_get the local diagonal with the
+        global k x k factor; with columns, both are replicated."""
         buf = (C.c_char * 128).from_buffer_copy(unique_id)
         fn = self.lib.ipxk_comm_init_columns if columns else self.lib.ipxk_comm_init
         self._check(fn(self.h, buf, C.c_int(rank), C.c_int(nranks)))
