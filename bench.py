@@ -1,24 +1,28 @@
 #!/usr/bin/env python3
-"""Headline benchmark (BASELINE.json): KKT solves/sec + A*D*A' SpMV HBM GB/s on the 1M-row
-synthetic LP, 1/2/4/8 GPUs.
+"""Headline benchmark (BASELINE.json): KKT solves/sec on the 1M-row synthetic LP, 1/2/4/8 GPUs;
+with --full also A*D*A' SpMV HBM GB/s and the measurements listed below.
 
-  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one KKTSolver::Solve (reference src/kkt_solver_diag.cc:82-118: right-hand-side
 assembly, preconditioned CR to tol = 0.3*sqrt(mu), solution recovery) on the C3 workload of
 SURVEY.md section 8(d): m = 1M, n = 2M, 8 nnz/col, IPM scaling spread s = 1, inputs resident in
 HBM.  N > 1: the SAME system with the rows of AI partitioned over the N ranks and one RCCL
-all-reduce per NormalMatrix apply (strong scaling; value = solves/s of the joint solve); the
-alternative column partition of SURVEY.md section 8(e) is measured in the same run and reported
-in config.column_partition.
+all-reduce per NormalMatrix apply (strong scaling; value = solves/s of the joint solve).
 
-One JSON line on rank 0:  metric/value/unit/...,
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs,
+and one JSON line on rank 0 (metric/value/unit/..., config of the timed solve, "full": false).
+--full adds every other measurement to the line, each after the timed steps (the --no-* options
+skip single ones):
   "roofline":     the NormalMatrix apply (its two sparse products, kernels named in the line) against the HBM roof:
                   algorithmic bytes 2*nnz*12 + (n+m+2)*4 + 8*(3n+4m) per apply / HIP-event time;
   "cpu_baseline": the same solve on ONE host core, timed in this run, by the reference's own
                   objects (oracle/_ref, kind "reference") when that build is present, else by
-                  this repo's restatement (oracle/, kind "port").
+                  this repo's restatement (oracle/, kind "port");
+  "config":       parity against the CPU, the basis / LU / Maxvolume / Newton paths, the reference's LpSolver
+                  through both KKT solver classes, BASELINE configs 2 and 5, the model upload; N > 1: the
+                  alternative column partition of SURVEY.md section 8(e) and the direct exchange.
 """
 import argparse
 import json
@@ -43,24 +47,28 @@ def parse():
     ap.add_argument("--cols", type=int, default=2000000)
     ap.add_argument("--spread", type=float, default=1.0)
     ap.add_argument("--maxiter", type=int, default=500)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--basis", action="store_true", help="(default at N = 1; kept for compatibility)")
-    ap.add_argument("--no-basis", action="store_true",
-                    help="skip the basis-preconditioned solve on planted LU factors (config.basis_path)")
-    ap.add_argument("--newton", action="store_true", help="(default at N = 1; kept for compatibility)")
-    ap.add_argument("--no-newton", action="store_true",
-                    help="skip the resident Newton step / IPM iteration measurements (config.newton_step)")
-    ap.add_argument("--no-column-partition", action="store_true",
-                    help="N > 1: skip the extra measurement of the column partition (config.column_partition)")
-    ap.add_argument("--no-lu", action="store_true", help="skip the basis LU factorization on the device (config.lu_path)")
-    ap.add_argument("--no-maxvolume", action="store_true", help="skip Maxvolume on the device (config.maxvolume_path)")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the reference's LpSolver through both KKT solver classes (config.dropin_lp_solver)")
-    ap.add_argument("--no-banded", action="store_true", help="skip the banded-matrix probe of the SpMV (extra field of roofline)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2 and 5 (config.other_configs)")
-    ap.add_argument("--no-direct-exchange", action="store_true",
-                    help="N > 1: skip the extra measurement over the direct (hipIpc) exchange (config.direct_exchange)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (x, y of the KKT solve) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take every other measurement of the line (roofline, CPU baseline, "
+                         "other paths and configs); a plain run measures the headline only")
+    fo = ap.add_argument_group("with --full", "skip one of the measurements --full adds")
+    fo.add_argument("--no-cpu-baseline", action="store_true")
+    fo.add_argument("--basis", action="store_true", help="(default at N = 1; kept for compatibility)")
+    fo.add_argument("--no-basis", action="store_true",
+                    help="skip the basis-preconditioned solve on planted LU factors (config.basis_path)")
+    fo.add_argument("--newton", action="store_true", help="(default at N = 1; kept for compatibility)")
+    fo.add_argument("--no-newton", action="store_true",
+                    help="skip the resident Newton step / IPM iteration measurements (config.newton_step)")
+    fo.add_argument("--no-column-partition", action="store_true",
+                    help="N > 1: skip the extra measurement of the column partition (config.column_partition)")
+    fo.add_argument("--no-lu", action="store_true", help="skip the basis LU factorization on the device (config.lu_path)")
+    fo.add_argument("--no-maxvolume", action="store_true", help="skip Maxvolume on the device (config.maxvolume_path)")
+    fo.add_argument("--no-dropin", action="store_true", help="skip the reference's LpSolver through both KKT solver classes (config.dropin_lp_solver)")
+    fo.add_argument("--no-banded", action="store_true", help="skip the banded-matrix probe of the SpMV (extra field of roofline)")
+    fo.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2 and 5 (config.other_configs)")
+    fo.add_argument("--no-direct-exchange", action="store_true",
+                    help="N > 1: skip the extra measurement over the direct (hipIpc) exchange (config.direct_exchange)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -296,35 +304,18 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
+    # ---- from here on a plain run only reports; every further measurement is taken with --full ----
+    full1 = args.full and rank == 0 and world == 1     # the measurements of a single-GPU run with --full
     # parity inputs of THIS system (later measurements re-factorize the context with other states)
     parity_inputs = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full1 and not args.no_cpu_baseline:
         ctx.set_pointer_mode(False)
         parity_inputs = (ctx.kkt_diag_get()[0], x.download(), y.download(),
                          pcr_trajectory_check(ctx, A, st["a"], st["b"], tol))
         ctx.set_pointer_mode(True)
 
-    # ---- roofline of the dominant kernel pair, measured live with HIP events on the ctx stream ----
-    rng = np.random.default_rng(0)
-    rhs_d = ctx.vector(mg, rng.standard_normal(mg))
-    lhs_d = ctx.vector(mg)
-    ctx.time_normal_apply(rhs_d, lhs_d, 5)
-    reps = 50
-    apply_ms = ctx.time_normal_apply(rhs_d, lhs_d, reps) / reps
     nnz = A.nnz
-    bytes_apply = 2 * nnz * 12 + (n + m + 2) * 4 + 8 * (3 * n + 4 * m)   # whole system (all ranks)
-    achieved = bytes_apply / (apply_ms * 1e-3) / 1e9
-    peak = HBM_PEAK_GBS * world
-    # L2<->fabric bytes per apply from the PMC passes of the same command (profiles/, separate
-    # rocprofv3 --pmc runs; bench.py cannot collect counters on itself)
-    layouts, tuned_us = ctx.spmv_layout()
-    kernel_names = {"phased": "spmv_phased_kernel", "sliced": "spmv_sliced_tile_kernel+spmv_sliced_combine_kernel",
-                    "fused": "spmv_sliced_tile_kernel<fused>", "sorted": "spmv_sorted_tile_kernel+spmv_sliced_combine_kernel",
-                    "sortedfused": "spmv_sorted_fused_kernel", "acc": "spmv_acc_tile_kernel+spmv_sliced_combine_kernel",
-                    "plain": "spmv_rowgroup_kernel", "accfused": "spmv_acc_fused_kernel"}
-    traffic, traffic_note = pmc_traffic("pmc_traffic.json", "traffic_bytes_per_apply",
-                                        "C3 m=%d n=%d nnz=%d" % (m, n, nnz) if world == 1 else None, layouts)
-
+    layouts = ctx.spmv_layout()[0]
     out = {
         "metric": "kkt_solves_per_sec",
         "value": args.steps / dt,
@@ -338,37 +329,23 @@ def main():
         "vs_baseline": None,
         "dtype": "f64",
         "data": "synthetic",
+        "full": args.full,
         "config": {"workload": "%ssynthetic LP m=%d n=%d 8 nnz/col (nnz=%d), KKTSolverDiag::Solve = diag-precond CR "
                                "to tol=0.3*sqrt(mu), scaling spread s=%g; rows of AI partitioned over %d GPU(s)"
                                % ("C3 " if (m, n) == (1000000, 2000000) else "", m, n, nnz, args.spread, world),
                    "cr_iterations_per_solve": it, "errflag": errflag,
                    "cr_iterations_per_sec": it * args.steps / dt,
                    "cr_loop_ms_per_solve": cr_time / args.steps * 1e3},
-        "roofline": {"bound": "hbm",
-                     "kernel": "NormalMatrix apply = pass 1 t=W.*(A'y) [%s] + pass 2 lhs=A t [%s]"
-                               % (kernel_names[layouts[0]], kernel_names[layouts[1]]),
-                     "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
-                     "traffic": traffic, "traffic_note": traffic_note, "us_per_apply": apply_ms * 1e3, "algorithmic_bytes": bytes_apply,
-                     "layouts": list(layouts), "layout_tuning_us": tuned_us,
-                     "note_50_percent": "the north star's >= 0.50 is NOT reached on this matrix: its row indices are uniformly random, every pass "
-                                        "gathers 8-byte words from 8 M distinct 128-byte lines, and the chip serves such gathers from L2 / fabric at "
-                                        "the rate this fraction reflects (profiles/r04_ldsacc_microbench.txt, r03_gather_sorted_microbench.txt); no "
-                                        "renumbering helps (an expander: ipxk_create finds half of the rows within 8 levels of any row).  With locality "
-                                        "the same kernels reach it: banded_matrix_probe, and shuffled_banded_probe where the locality is first "
-                                        "recovered by the renumbering of layout_device.hip"},
     }
-    try:
-        ri = ctx.reorder_info()
-        out["roofline"]["renumbering"] = {"active": bool(ri["active"]), "levels": int(ri["levels"]), "ms_in_create": ri["ms"]}
-    except Exception:            # noqa: BLE001
-        pass
+    if args.full:
+        out["roofline"] = bench_roofline(ctx, m, n, nnz, mg, world, layouts)
 
-    if (world > 1 or os.environ.get("IPXK_FORCE_COMM")) and not args.no_column_partition:
+    if args.full and (world > 1 or os.environ.get("IPXK_FORCE_COMM")) and not args.no_column_partition:
         # every rank takes part; reported next to the north-star row partition, never as `value`
         out["config"]["column_partition"] = bench_column_partition(kkt, dist, torch, A, st, tol, args, rank, world,
                                                                    local_rank, tdev)
-    if world > 1 and not args.no_direct_exchange and (os.environ.get("IPXK_COMM") != "direct" or
-                                                       os.environ.get("IPXK_BENCH_DIRECT_AGAIN")):
+    if args.full and world > 1 and not args.no_direct_exchange and (os.environ.get("IPXK_COMM") != "direct" or
+                                                                     os.environ.get("IPXK_BENCH_DIRECT_AGAIN")):
         # the same row-partitioned solve over the library's direct exchange (hipIpc-mapped peer buffers) next to
         # the RCCL measurement above; never `value`.  Any failure is recorded instead of a number.
         out["config"]["direct_exchange"] = bench_direct_exchange(kkt, dist, torch, A, st, tol, args, rank, world,
@@ -384,25 +361,25 @@ def main():
         out["config"]["transport"] = "REHEARSAL: all ranks on one GPU, direct exchange between the rank processes"
     elif world > 1:
         out["config"]["transport"] = "direct exchange over hipIpc-mapped peer buffers" if os.environ.get("IPXK_COMM") == "direct" else "RCCL"
-    if rank == 0 and world == 1:
+    if full1:
         # what a plain streaming kernel reaches on this box (report next to the 8 TB/s spec peak)
         triad = measure_triad(torch)
         out["roofline"]["measured_triad_GBps"] = triad
-        out["roofline"]["frac_of_measured_triad"] = achieved / triad
-    if rank == 0 and world == 1 and not args.no_banded:
+        out["roofline"]["frac_of_measured_triad"] = out["roofline"]["achieved"] / triad
+    if full1 and not args.no_banded:
         out["roofline"]["banded_matrix_probe"] = bench_banded(kkt, synth, m, n)
         out["roofline"]["shuffled_banded_probe"] = bench_banded_shuffled(kkt, synth, m, n)
-    if rank == 0 and world == 1 and not args.no_basis:
+    if full1 and not args.no_basis:
         out["config"]["basis_path"] = bench_basis(kkt, synth, m, n, args)
-    if rank == 0 and world == 1 and not args.no_lu:
+    if full1 and not args.no_lu:
         out["config"]["lu_path"] = bench_lu(kkt, synth, m, n, args)
-    if rank == 0 and world == 1 and not args.no_maxvolume:
+    if full1 and not args.no_maxvolume:
         out["config"]["maxvolume_path"] = bench_maxvolume(kkt, synth, m, n, args)
-    if rank == 0 and world == 1 and not args.no_newton:
+    if full1 and not args.no_newton:
         out["config"]["newton_step"] = bench_newton(kkt, synth, ctx, m, n, args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_dropin and (m, n) == (1000000, 2000000):
+    if full1 and not args.no_cpu_baseline and not args.no_dropin and (m, n) == (1000000, 2000000):
         out["config"]["dropin_lp_solver"] = bench_dropin_lp_solver(m, n)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full1 and not args.no_cpu_baseline:
         ctx.set_pointer_mode(False)
         Wd, xg, yg, traj = parity_inputs
         base, (xc, yc, itc) = cpu_baseline(A, st, tol, args.maxiter)
@@ -417,12 +394,12 @@ def main():
                                                   "80-iteration run is not gated (1 ulp in b moves it by 1e-6)"}
     elif rank == 0:
         out["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if full1 and not args.no_other_configs:
         out["config"]["other_configs"] = {
             "C2": bench_diag_config(kkt, synth, "BASELINE config 2: m=50k n=100k 8 nnz/col, diag-precond CR", 50000, 100000, 0, args, 10),
             "C5": bench_diag_config(kkt, synth, "BASELINE config 5: m=200k n=400k + 32 dense columns (DiagonalPrecond with "
                                                 "Sherman-Morrison-Woodbury, src/diagonal_precond.cc:48-101)", 200000, 400000, 32, args, 3)}
-    if rank == 0 and world == 1:
+    if full1:
         # ipxk_create of THIS run's context (the first in the process: includes the HIP runtime's start-up) and a second
         # one on the warm runtime -- what a solver object pays when no context of its Model exists yet
         t0 = time.perf_counter()
@@ -438,9 +415,12 @@ def main():
     if rank == 0:
         # short copies of the numbers a reader looks for first, at the END of the line (the driver keeps the tail)
         cfg = out["config"]
-        summ = {"headline_solves_per_s": out["value"], "apply_us": out["roofline"]["us_per_apply"], "apply_frac_of_hbm_peak": out["roofline"]["frac"],
-                "apply_traffic_over_algorithmic": (out["roofline"]["traffic"] / bytes_apply) if out["roofline"].get("traffic") else None,
-                "layouts": list(layouts)}
+        summ = {"headline_solves_per_s": out["value"]}
+        rl = out.get("roofline")
+        if rl:
+            summ.update(apply_us=rl["us_per_apply"], apply_frac_of_hbm_peak=rl["frac"],
+                        apply_traffic_over_algorithmic=(rl["traffic"] / rl["algorithmic_bytes"]) if rl.get("traffic") else None)
+        summ["layouts"] = list(layouts)
         bp = cfg.get("basis_path") or {}
         if "roofline" in bp:
             summ["basis_us_per_cr_iteration"] = bp.get("us_per_cr_iteration")
@@ -482,6 +462,45 @@ def main():
     if world > 1:
         dist.destroy_process_group()
 
+
+def bench_roofline(ctx, m, n, nnz, mg, world, layouts):
+    """Roofline of the dominant kernel pair, measured live with HIP events on the ctx stream."""
+    rng = np.random.default_rng(0)
+    rhs_d = ctx.vector(mg, rng.standard_normal(mg))
+    lhs_d = ctx.vector(mg)
+    ctx.time_normal_apply(rhs_d, lhs_d, 5)
+    reps = 50
+    apply_ms = ctx.time_normal_apply(rhs_d, lhs_d, reps) / reps
+    bytes_apply = 2 * nnz * 12 + (n + m + 2) * 4 + 8 * (3 * n + 4 * m)   # whole system (all ranks)
+    achieved = bytes_apply / (apply_ms * 1e-3) / 1e9
+    peak = HBM_PEAK_GBS * world
+    # L2<->fabric bytes per apply from the PMC passes of the same command (profiles/, separate
+    # rocprofv3 --pmc runs; bench.py cannot collect counters on itself)
+    tuned_us = ctx.spmv_layout()[1]
+    kernel_names = {"phased": "spmv_phased_kernel", "sliced": "spmv_sliced_tile_kernel+spmv_sliced_combine_kernel",
+                    "fused": "spmv_sliced_tile_kernel<fused>", "sorted": "spmv_sorted_tile_kernel+spmv_sliced_combine_kernel",
+                    "sortedfused": "spmv_sorted_fused_kernel", "acc": "spmv_acc_tile_kernel+spmv_sliced_combine_kernel",
+                    "plain": "spmv_rowgroup_kernel", "accfused": "spmv_acc_fused_kernel"}
+    traffic, traffic_note = pmc_traffic("pmc_traffic.json", "traffic_bytes_per_apply",
+                                        "C3 m=%d n=%d nnz=%d" % (m, n, nnz) if world == 1 else None, layouts)
+    res = {"bound": "hbm",
+           "kernel": "NormalMatrix apply = pass 1 t=W.*(A'y) [%s] + pass 2 lhs=A t [%s]"
+                     % (kernel_names[layouts[0]], kernel_names[layouts[1]]),
+           "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
+           "traffic": traffic, "traffic_note": traffic_note, "us_per_apply": apply_ms * 1e3, "algorithmic_bytes": bytes_apply,
+           "layouts": list(layouts), "layout_tuning_us": tuned_us,
+           "note_50_percent": "the north star's >= 0.50 is NOT reached on this matrix: its row indices are uniformly random, every pass "
+                              "gathers 8-byte words from 8 M distinct 128-byte lines, and the chip serves such gathers from L2 / fabric at "
+                              "the rate this fraction reflects (profiles/r04_ldsacc_microbench.txt, r03_gather_sorted_microbench.txt); no "
+                              "renumbering helps (an expander: ipxk_create finds half of the rows within 8 levels of any row).  With locality "
+                              "the same kernels reach it: banded_matrix_probe, and shuffled_banded_probe where the locality is first "
+                              "recovered by the renumbering of layout_device.hip"}
+    try:
+        ri = ctx.reorder_info()
+        res["renumbering"] = {"active": bool(ri["active"]), "levels": int(ri["levels"]), "ms_in_create": ri["ms"]}
+    except Exception:            # noqa: BLE001
+        pass
+    return res
 
 def bench_direct_exchange(kkt, dist, torch, A, st, tol, args, rank, world, local_rank, it_rccl, tdev="cuda"):
     """Row partition again, collectives through IPXK_COMM=direct.  Every rank runs the same sequence; an error on
