@@ -236,7 +236,36 @@ int ipxk_kkt_diag_get(const ipxk_context* ctx, double* W, double* resscale);
  * may come in any order as long as U's diagonal is last; a dense trailing block of
  * the factors is cut out of the sweeps (and applied as a blocked solve or an
  * explicit inverse) only when the columns of U that cross it are sorted, as
- * GetLuFactors returns them. */
+ * GetLuFactors returns them.
+ *
+ * Column-partitioned context (ipxk_comm_init_columns; a row-partitioned one gets
+ * IPXK_E_ARGUMENT): the basis path is collective, and every rank obtains the same
+ * m-vectors bit for bit.
+ *  - Replicated arguments: L, U, rowperm, colperm -- the factors of the GLOBAL B,
+ *    from the host -- and basis[m] in the global numbering 0..n_global+m, the same
+ *    on every rank.
+ *  - Local arguments: status, colscale (and a, x of ipxk_kkt_basis_solve) in the
+ *    partition's local form [this rank's structural slice; all m slack entries].
+ *  - Slabs are contiguous and in rank order (rank r holds the global columns
+ *    c0_r .. c0_r + n_r - 1 with c0_r = n_0 + ... + n_{r-1}); the first Prepare
+ *    after ipxk_comm_init_columns learns c0 and n_global by one all-gather of n.
+ *  - The ranks fail or proceed together: the argument checks end in one
+ *    all-reduce of each rank's verdict and a fingerprint of the replicated
+ *    arguments (factors, permutations, basis, slack parts of status and
+ *    colscale).  A failed check on any rank, or fingerprints that differ, make
+ *    every rank return IPXK_E_ARGUMENT.
+ *  - Prepare and ipxk_split_rescale form the status and scale of every basis
+ *    position from the owners' contributions (one all-reduce of 2m); N holds this
+ *    rank's nonbasic structural columns.
+ *  - ipxk_split_apply: U' and L' sweeps, this rank's N_g N_g' partial (the slack
+ *    term on rank 0), one all-reduce of m, L and U sweeps.  The triangular solves
+ *    (ipxk_forward_solve, ipxk_backward_solve, ipxk_solve_dense) run replicated
+ *    and exchange nothing; ipxk_cr_solve exchanges once per Apply plus the
+ *    max-reduce of its loop flags once per 5 iterations.
+ *  - ipxk_kkt_basis_solve: three all-reduces of m (a[basis], the right-hand
+ *    side product, b - N x_N) plus one per CR Apply.  x receives the entries this
+ *    rank holds: its nonbasic and basic structural columns and all slacks.
+ * An operator prepared under another partition is refused until prepared again. */
 int ipxk_split_prepare(ipxk_context* ctx, const ipxint* Lp, const ipxint* Li,
                        const double* Lx, const ipxint* Up, const ipxint* Ui,
                        const double* Ux, const ipxint* rowperm,
@@ -249,7 +278,9 @@ int ipxk_split_prepare(ipxk_context* ctx, const ipxint* Lp, const ipxint* Li,
  * (src/splitted_normal_matrix.cc:30-64).  Reuses the level schedule and the
  * packed factors of the last ipxk_split_prepare (same L, U, permutations and
  * basis) and rebuilds only what depends on status / colscale; the result is
- * bit-identical to a full ipxk_split_prepare with the same arguments. */
+ * bit-identical to a full ipxk_split_prepare with the same arguments.  Column
+ * partition: collective (status / colscale local, their slack parts replicated;
+ * the ranks agree on the verdict as in ipxk_split_prepare). */
 int ipxk_split_rescale(ipxk_context* ctx, const ipxint* status,
                        const double* colscale);
 /* ---- basis LU factorization on the device ------------------
@@ -310,7 +341,10 @@ int ipxk_lu_get_factors(ipxk_context* ctx, ipxint* Lp, ipxint* Li, double* Lx,
                         ipxint* colperm, ipxint* dependent_cols);
 /* B = AI[:, basis[0..m-1]] taken from the matrix resident in the context (slack
  * columns j >= n are unit columns): Basis::Factorize (src/basis.cc:116-156)
- * without B crossing PCIe -- only the m basis indices do. */
+ * without B crossing PCIe -- only the m basis indices do.  Refused
+ * (IPXK_E_ARGUMENT) on a partitioned context, as are ipxk_split_prepare_lu,
+ * ipxk_maxvolume and ipxk_maxvolume_sequential: replicated factors must be the
+ * same bit for bit on every rank; pass host factors to ipxk_split_prepare. */
 int ipxk_lu_factorize_basis(ipxk_context* ctx, const ipxint* basis,
                             double pivottol, int strict_abs_pivottol,
                             ipxk_lu_info* info);
@@ -383,7 +417,8 @@ int ipxk_maxvolume_sequential(ipxk_context* ctx, const ipxint* status,
                               ipxint maxpasses, ipxint max_etas, ipxint* basis_out,
                               ipxint* status_out, ipxk_maxvolume_info* info,
                               ipxint* exchange_log, ipxint log_cap);
-/* _Apply (src/splitted_normal_matrix.cc:90-117) */
+/* _Apply (src/splitted_normal_matrix.cc:90-117); column partition: rhs, lhs
+ * replicated m-vectors, one all-reduce of m (see ipxk_split_prepare) */
 int ipxk_split_apply(ipxk_context* ctx, const double* rhs, double* lhs,
                      double* rhs_dot_lhs);
 /* ForwardSolve / BackwardSolve with the prepared (scaled) factors, in place
@@ -402,7 +437,9 @@ int ipxk_cr_solve(ipxk_context* ctx, const double* rhs, double tol,
                   void* interrupt_user, double* resnorm_hist, ipxint hist_cap,
                   ipxk_times* times);
 
-/* ---- KKTSolverBasis::_Solve (src/kkt_solver_basis.cc:75-194) ------------- */
+/* ---- KKTSolverBasis::_Solve (src/kkt_solver_basis.cc:75-194) -------------
+ * Column partition: a[n+m], x[n+m] local, b, y replicated (see ipxk_split_prepare);
+ * also in the device-pointer (resident) form. */
 int ipxk_kkt_basis_solve(ipxk_context* ctx, const double* a, const double* b,
                          double tol, ipxint maxiter, double* x, double* y,
                          ipxint* iter, ipxint* errflag,
@@ -559,7 +596,9 @@ int ipxk_comm_init(ipxk_context* ctx, const void* id128, int rank, int nranks);
  * Collective: the dense columns are classified from a histogram of the column
  * counts of all ranks (an all-reduce of 1 and one of max count + 1 doubles);
  * each rank keeps the dense columns it owns, and the first Factorize with
- * dense-column preconditioning gathers those of every rank. */
+ * dense-column preconditioning gathers those of every rank.  The basis path
+ * (ipxk_split_prepare and what uses its operator) runs on this partition; see
+ * ipxk_split_prepare for its conventions. */
 int ipxk_comm_init_columns(ipxk_context* ctx, const void* id128, int rank, int nranks);
 /* What the transport itself reports about the communicator of this context:
  * transport 0 = none, 1 = RCCL (nranks / rank from ncclCommCount /

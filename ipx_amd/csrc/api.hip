@@ -821,6 +821,7 @@ int ipxk_maxvolume(ipxk_context* c, const ipxint* status, const double* colscale
     return guarded([&] {
         IPXK_REQUIRE(c && status && colscale, "NULL argument");
         IPXK_REQUIRE(log_cap >= 0 && (exchange_log || log_cap == 0), "bad log arguments");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
         bind_device(c);
         maxvolume_dev(c, status, colscale, params, basis_out, status_out, info, exchange_log, log_cap);
     });
@@ -832,6 +833,7 @@ int ipxk_maxvolume_sequential(ipxk_context* c, const ipxint* status, const doubl
     return guarded([&] {
         IPXK_REQUIRE(c && status && colscale, "NULL argument");
         IPXK_REQUIRE(log_cap >= 0 && (exchange_log || log_cap == 0), "bad log arguments");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
         bind_device(c);
         maxvolume_sequential_dev(c, status, colscale, volume_tol, maxpasses, max_etas, basis_out, status_out, info, exchange_log, log_cap);
     });
@@ -858,6 +860,7 @@ int ipxk_split_apply(ipxk_context* c, const double* rhs, double* lhs, double* rh
     return guarded([&] {
         IPXK_REQUIRE(c && rhs && lhs, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "SplittedNormalMatrix not prepared");
+        split_check_partition(c);
         bind_device(c);
         if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
         const size_t m = (size_t)c->m;
@@ -876,6 +879,7 @@ static int inplace_solve(ipxk_context* c, double* x, bool forward) {
     return guarded([&] {
         IPXK_REQUIRE(c && x, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "SplittedNormalMatrix not prepared");
+        split_check_partition(c);
         bind_device(c);
         const size_t m = (size_t)c->m;
         double* dx = stage_out(c, x, m, c->v_lhs);
@@ -896,6 +900,7 @@ int ipxk_solve_dense(ipxk_context* c, const double* rhs, double* lhs, char trans
     return guarded([&] {
         IPXK_REQUIRE(c && rhs && lhs, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "SplittedNormalMatrix not prepared");
+        split_check_partition(c);
         bind_device(c);
         const size_t m = (size_t)c->m;
         const double* drhs = stage_in(c, rhs, m, c->v_rhs);
@@ -921,6 +926,7 @@ int ipxk_kkt_basis_solve(ipxk_context* c, const double* a, const double* b, doub
     return guarded([&] {
         IPXK_REQUIRE(c && a && b && x && y && iter && errflag, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "KKTSolverBasis not factorized (split operator missing)");
+        split_check_partition(c);
         bind_device(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         const double* da = stage_in(c, a, N, c->k_a);

@@ -413,6 +413,8 @@ void comm_allreduce_sum_staged(Context* c, double* dst, size_t count) {
 }
 
 void comm_destroy(Context* c) {
+    c->col_offset = -1;
+    c->n_global = 0;
     if (c->direct) { destroy_direct(c->direct); c->direct = nullptr; }
     if (c->comm) {
         (void)rccl().comm_destroy(c->comm);

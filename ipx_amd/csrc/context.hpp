@@ -156,6 +156,9 @@ struct Context {
     // true: structural COLUMNS partitioned (m global, n local; every m-vector and every scalar of
     // the CR loop is replicated, the only exchange is the sum of the partial products A_g t_g)
     bool col_partition = false;
+    // column partition, basis path: this rank's first structural column and the structural columns of all ranks
+    // (one all-gather at the first split Prepare after comm_init; -1: not known yet)
+    int64_t col_offset = -1, n_global = 0;
     DevBuf<double> comm_scalars;        // scratch scalars (single-value reductions)
     DevBuf<double> comm_send;           // kNumPartialSlots scalars of this rank
     DevBuf<double> comm_gather;         // nranks * kNumPartialSlots, rank-major
@@ -282,6 +285,12 @@ void split_prepare_host(Context* c, const ipxint* Lp, const ipxint* Li, const do
 // lhs = C rhs (device vectors), dot partials -> part(kPartCdot); returns # partials
 int split_apply_dev(Context* c, const double* rhs, double* lhs, const int* done);
 void split_rescale_host(Context* c, const ipxint* status, const double* colscale);
+// raises unless the split operator was prepared under the context's current partition (trisolve.hip)
+void split_check_partition(const Context* c);
+// the device LU, the Prepare from it and Maxvolume on a partitioned context
+constexpr const char* kDeviceLuRefusal =
+    "the device LU (and the Prepare and Maxvolume that use it) does not run on a partitioned system: factorize the basis "
+    "identically for every rank and pass the factors to ipxk_split_prepare";
 // the operator follows Maxvolume's exchanges without new factors (Context::etas_live): the basis by position (device), its statuses and scaling
 void split_follow_basis(Context* c, const ipxint* basis_dev, const ipxint* status, const double* colscale);
 // out = inverse(B) in / inverse(B') in on the (scaled) factors; in may be out

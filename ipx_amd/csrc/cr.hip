@@ -516,6 +516,7 @@ CrResult cr_solve_dev(Context* c, const double* rhs, double tol, const double* r
                       ipxint maxiter, double* lhs, bool lhs_is_zero, ipxk_interrupt_fn interrupt,
                       void* user, double* hist_host, ipxint hist_cap, ipxk_times* times) {
     IPXK_REQUIRE(c->split != nullptr, "SplittedNormalMatrix not prepared");
+    split_check_partition(c);
     CrOps ops{kModePlain, applyC_split};
     return run_cr<kModePlain>(c, ops, rhs, tol, resscale, maxiter, lhs, lhs_is_zero, interrupt, user,
                               hist_host, hist_cap, times);

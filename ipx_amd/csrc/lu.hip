@@ -2630,8 +2630,8 @@ void lu_factorize_host(Context* c, int64_t dim64, const ipxint* Bbegin, const ip
 }
 
 void lu_factorize_basis(Context* c, const ipxint* basis, double pivottol, bool strict, ipxk_lu_info* info) {
+    IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
     IPXK_REQUIRE(pivottol > 0.0 && pivottol <= 1.0, "pivottol must lie in (0,1]");
-    IPXK_REQUIRE(c->nranks == 1, "the basis path does not shard: run it as independent replicas");
     const int m = (int)c->m, n = (int)c->n;
     hipStream_t s = c->stream;
     LuState* S = lu_state(c);

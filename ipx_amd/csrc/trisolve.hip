@@ -1031,6 +1031,149 @@ __global__ void scaling_pivots_kernel(int m, const int* __restrict__ colperm, co
     }
 }
 
+// ---- column-partitioned contexts (comm_cols) ----
+// L, U, the permutations and basis[] (global column numbers) are replicated; status, colscale, a and x are local
+// ([this rank's structural slice; all m slack entries]).  What a kernel indexed by basis position needs of a column
+// that another rank owns is formed by one all-reduce of the owners' contributions (every other rank adds 0, so the
+// sum is exact); slack positions are filled in locally afterwards, identically on every rank.
+static const char* const kRowPartitionRefusal =
+    "the basis path does not run on a row-partitioned system: partition the structural columns (ipxk_comm_init_columns)";
+
+// an operator prepared under another communicator (or none) is not used: its basis numbering and its exchanges differ
+void split_check_partition(const Context* c) {
+    IPXK_REQUIRE(!comm_rows(c), kRowPartitionRefusal);
+    IPXK_REQUIRE(c->split->part == comm_cols(c), "the split operator was prepared under another partition: Prepare it again");
+}
+
+// this rank's first structural column and the structural columns of all ranks (slabs contiguous, in rank order):
+// one all-gather of n_local, once per communicator
+static void learn_col_offsets(Context* c) {
+    if (c->col_offset >= 0) return;
+    const int R = c->nranks;
+    hipStream_t s = c->stream;
+    DevBuf<double> mine(1), all((size_t)R);
+    const double nl = (double)c->n;
+    mine.upload(&nl, 1, s);
+    comm_allgather(c, mine.get(), all.get(), 1);
+    std::vector<double> h((size_t)R);
+    all.download(h.data(), (size_t)R, s);
+    IPXK_HIP(hipStreamSynchronize(s));
+    comm_check(c);
+    int64_t c0 = 0, total = 0;
+    for (int r = 0; r < R; r++) {
+        if (r < c->rank) c0 += (int64_t)h[(size_t)r];
+        total += (int64_t)h[(size_t)r];
+    }
+    c->col_offset = c0;
+    c->n_global = total;
+}
+
+// fingerprint of the arguments every rank must hold identically
+struct Fingerprint {
+    uint64_t h = 0x9e3779b97f4a7c15ull;
+    void mix(uint64_t w) { h ^= w; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; }
+    template <class T> void add(const T* p, size_t count) {
+        const size_t len = count * sizeof(T);
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(p);
+        size_t i = 0;
+        for (; i + 8 <= len; i += 8) { uint64_t w; memcpy(&w, b + i, 8); mix(w); }
+        if (i < len) { uint64_t w = 0; memcpy(&w, b + i, len - i); mix(w); }
+        mix((uint64_t)len);
+    }
+};
+
+// The ranks fail or proceed together, so that no rank enters a later collective alone: this rank's verdict and the
+// fingerprint go through one all-reduce (max of [failed, hi, lo, -hi, -lo]; max == -max(-.) iff all fingerprints agree).
+static void agree_on_arguments(Context* c, const std::string& err, uint64_t h) {
+    const double hi = (double)(h >> 32), lo = (double)(h & 0xffffffffull);
+    double v[5] = {err.empty() ? 0.0 : 1.0, hi, lo, -hi, -lo};
+    DevBuf<double> d(5);
+    d.upload(v, 5, c->stream);
+    comm_allreduce_max(c, d.get(), 5);
+    d.download(v, 5, c->stream);
+    IPXK_HIP(hipStreamSynchronize(c->stream));
+    comm_check(c);
+    if (!err.empty()) throw Error(IPXK_E_ARGUMENT, err);
+    if (v[0] != 0.0) throw Error(IPXK_E_ARGUMENT, "another rank refused its arguments of the basis path");
+    if (v[1] != -v[3] || v[2] != -v[4])
+        throw Error(IPXK_E_ARGUMENT, "the replicated arguments of the basis path (factors, permutations, basis, slack parts of "
+                                     "status and colscale) differ between the ranks");
+}
+
+// local status entries in range (the scaling kernel's check, made before the ranks agree)
+static void check_status_host(int64_t N, const ipxint* status) {
+    for (int64_t j = 0; j < N; j++)
+        IPXK_REQUIRE(status[j] >= IPXK_NONBASIC_FIXED && status[j] <= IPXK_BASIC_FREE, "status entry out of range");
+}
+
+// dst = sum over the ranks of what produce(out) writes to out: the direct exchange's buffer where it offers one
+template <class F>
+static void allreduce_product(Context* c, double* dst, size_t count, F produce) {
+    double* stage = comm_stage(c, count);
+    produce(stage ? stage : dst);
+    if (stage) comm_allreduce_sum_staged(c, dst, count);
+    else comm_allreduce_sum(c, dst, count);
+}
+
+// out[p] = v[loc[p]] for structural columns of this rank, 0 otherwise (an owner's contribution)
+__global__ void pos_contrib_kernel(int m, int n, const int* __restrict__ loc, const double* __restrict__ v, double* __restrict__ out) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
+        const int l = loc[p];
+        out[p] = l >= 0 && l < n ? v[l] : 0.0;
+    }
+}
+// after the all-reduce: slack positions from the replicated slack part
+__global__ void pos_slack_kernel(int m, int n, const int* __restrict__ loc, const double* __restrict__ v, double* __restrict__ out) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
+        const int l = loc[p];
+        if (l >= n) out[p] = v[l];
+    }
+}
+// pos_status / pos_scale from the summed contributions (status in sum[0..m), colscale in sum[m..2m)) and the slack part
+__global__ void pos_scaling_kernel(int m, int n, const int* __restrict__ loc, const double* __restrict__ sum,
+                                   const int* __restrict__ status32, const double* __restrict__ colscale,
+                                   int* __restrict__ pos_status, double* __restrict__ pos_scale) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
+        const int l = loc[p];
+        pos_status[p] = l >= n ? status32[l] : (int)sum[p];
+        pos_scale[p] = l >= n ? colscale[l] : sum[m + p];
+    }
+}
+// scaling_pivots_kernel by basis position
+__global__ void scaling_pivots_pos_kernel(int m, const int* __restrict__ colperm, const int* __restrict__ pos_status,
+                                          const double* __restrict__ pos_scale, double* __restrict__ uscale,
+                                          unsigned char* __restrict__ fmask, int* num_free) {
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < m; k += gridDim.x * blockDim.x) {
+        const int p = colperm[k];
+        const int st = pos_status[p];
+        uscale[k] = st == IPXK_BASIC ? pos_scale[p] : 1.0;
+        fmask[k] = st == IPXK_BASIC_FREE ? 1 : 0;
+        if (st == IPXK_BASIC_FREE) atomicAdd(num_free, 1);
+    }
+}
+
+// status and scale of every basis position: one all-reduce of 2m, then the slack positions locally
+static void scaling_positions(Context* c, SplitOperator* S, const ipxint* status, const double* colscale) {
+    const int m = S->m, n = (int)c->n;
+    hipStream_t s = c->stream;
+    const size_t mm = (size_t)std::max(m, 1);
+    std::vector<double> h(2 * (size_t)m, 0.0);
+    for (int p = 0; p < m; p++) {
+        const int l = S->h_loc[(size_t)p];
+        if (l >= 0 && l < n) { h[(size_t)p] = (double)status[l]; h[(size_t)m + p] = colscale[l]; }
+    }
+    S->pos_sum.ensure(2 * mm);
+    S->pos_sum.upload(h, s);
+    comm_allreduce_sum(c, S->pos_sum.get(), 2 * (size_t)m);
+    S->pos_status.ensure(mm); S->pos_scale.ensure(mm);
+    if (m > 0) {
+        hipLaunchKernelGGL(pos_scaling_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, n, S->loc.get(), S->pos_sum.get(),
+                           S->status.get(), S->colscale.get(), S->pos_status.get(), S->pos_scale.get());
+        hipLaunchKernelGGL(scaling_pivots_pos_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, S->colperm.get(), S->pos_status.get(),
+                           S->pos_scale.get(), S->uscale.get(), S->free_mask.get(), S->counters.get() + 1);
+    }
+}
+
 static void upload_scaling(Context* c, SplitOperator* S, const ipxint* status, const double* colscale) {
     const int m = S->m, n = (int)c->n;
     const size_t N = (size_t)n + m;
@@ -1043,8 +1186,11 @@ static void upload_scaling(Context* c, SplitOperator* S, const ipxint* status, c
     IPXK_HIP(hipMemsetAsync(S->counters.get(), 0, 2 * sizeof(int), s));
     hipLaunchKernelGGL(scaling_columns_kernel, dim3(vec_grid((int64_t)N)), dim3(kBlock), 0, s, (int64_t)N,
                        S->status_raw.get(), S->colscale.get(), S->Wsplit.get(), S->status.get(), S->counters.get());
-    hipLaunchKernelGGL(scaling_pivots_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, S->colperm.get(), S->basis.get(),
-                       S->status.get(), S->colscale.get(), S->uscale.get(), S->free_mask.get(), S->counters.get() + 1);
+    if (S->part)
+        scaling_positions(c, S, status, colscale);
+    else
+        hipLaunchKernelGGL(scaling_pivots_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, S->colperm.get(), S->basis.get(),
+                           S->status.get(), S->colscale.get(), S->uscale.get(), S->free_mask.get(), S->counters.get() + 1);
     int h[2] = {0, 0};
     S->counters.download(h, 2, s);
     if (h[0]) throw Error(IPXK_E_ARGUMENT, "status entry out of range");
@@ -1497,22 +1643,48 @@ void split_prepare_host(Context* c, const ipxint* Lp, const ipxint* Li, const do
     maxvol_drop_etas(c);
     const int m = (int)c->m, n = (int)c->n;
     hipStream_t s = c->stream;
-    IPXK_REQUIRE(c->nranks == 1, "the basis path does not shard: run it as independent replicas");
-    IPXK_REQUIRE(Lp[m] < (int64_t(1) << 31) && Up[m] < (int64_t(1) << 31), "factor nnz exceeds 32 bits");
-    IPXK_REQUIRE(Lp[0] == 0 && Up[0] == 0, "column pointers must start at 0");
-    for (int k = 0; k < m; k++) {
-        IPXK_REQUIRE(Lp[k + 1] >= Lp[k] && Up[k + 1] > Up[k] && Up[k + 1] <= Up[m] && Lp[k + 1] <= Lp[m],
-                     "factor column pointers not monotone");
-        IPXK_REQUIRE(Ui[Up[k + 1] - 1] == k, "U must hold its diagonal last in each column");
-        IPXK_REQUIRE(basis[k] >= 0 && basis[k] < n + m, "basis entry out of range");
-        IPXK_REQUIRE(rowperm[k] >= 0 && rowperm[k] < m && colperm[k] >= 0 && colperm[k] < m, "permutation entry out of range");
-    }
-    {   // rowperm, colperm are permutations; basis entries distinct is the caller's contract
-        std::vector<unsigned char> seen_r(m, 0), seen_c(m, 0);
+    IPXK_REQUIRE(!comm_rows(c), kRowPartitionRefusal);
+    const bool part = comm_cols(c);
+    if (part) learn_col_offsets(c);
+    const int64_t ncols = part ? c->n_global : n;       // the structural columns basis[] numbers
+    auto check_arguments = [&] {
+        IPXK_REQUIRE(ncols + m < (int64_t(1) << 31), "column count exceeds 32 bits");
+        IPXK_REQUIRE(Lp[m] < (int64_t(1) << 31) && Up[m] < (int64_t(1) << 31), "factor nnz exceeds 32 bits");
+        IPXK_REQUIRE(Lp[0] == 0 && Up[0] == 0, "column pointers must start at 0");
         for (int k = 0; k < m; k++) {
-            IPXK_REQUIRE(!seen_r[rowperm[k]] && !seen_c[colperm[k]], "rowperm / colperm is not a permutation");
-            seen_r[rowperm[k]] = seen_c[colperm[k]] = 1;
+            IPXK_REQUIRE(Lp[k + 1] >= Lp[k] && Up[k + 1] > Up[k] && Up[k + 1] <= Up[m] && Lp[k + 1] <= Lp[m],
+                         "factor column pointers not monotone");
+            IPXK_REQUIRE(Ui[Up[k + 1] - 1] == k, "U must hold its diagonal last in each column");
+            IPXK_REQUIRE(basis[k] >= 0 && basis[k] < ncols + m, "basis entry out of range");
+            IPXK_REQUIRE(rowperm[k] >= 0 && rowperm[k] < m && colperm[k] >= 0 && colperm[k] < m, "permutation entry out of range");
         }
+        {   // rowperm, colperm are permutations; basis entries distinct is the caller's contract
+            std::vector<unsigned char> seen_r(m, 0), seen_c(m, 0);
+            for (int k = 0; k < m; k++) {
+                IPXK_REQUIRE(!seen_r[rowperm[k]] && !seen_c[colperm[k]], "rowperm / colperm is not a permutation");
+                seen_r[rowperm[k]] = seen_c[colperm[k]] = 1;
+            }
+        }
+    };
+    if (part) {
+        // every rank checks its arguments, then all ranks agree on the verdict and on the replicated arguments
+        std::string err;
+        uint64_t fp = 0;
+        try {
+            check_arguments();
+            check_status_host((int64_t)n + m, status);
+            Fingerprint F;
+            F.add(Lp, (size_t)m + 1); F.add(Li, (size_t)Lp[m]); F.add(Lx, (size_t)Lp[m]);
+            F.add(Up, (size_t)m + 1); F.add(Ui, (size_t)Up[m]); F.add(Ux, (size_t)Up[m]);
+            F.add(rowperm, (size_t)m); F.add(colperm, (size_t)m); F.add(basis, (size_t)m);
+            F.add(status + n, (size_t)m); F.add(colscale + n, (size_t)m);
+            fp = F.h;
+        } catch (const Error& e) {
+            err = e.what();
+        }
+        agree_on_arguments(c, err, fp);
+    } else {
+        check_arguments();
     }
     // the operator object (and its device buffers) is reused from one Prepare to the next; while it is
     // being rebuilt the context has no operator, and a failure leaves it that way
@@ -1571,6 +1743,21 @@ void split_prepare_host(Context* c, const ipxint* Lp, const ipxint* Li, const do
         S->rowperm_inv.upload(rpi, s);
         S->colperm.upload(cpm, s);
         S->basis.upload(bs, s);
+        S->part = part;
+        if (part) {     // where each basis position lives in this rank's local vectors (SplitOperator::loc)
+            const int64_t c0 = c->col_offset;
+            S->h_loc.assign((size_t)m, -1);
+            for (int p = 0; p < m; p++) {
+                const int64_t j = basis[p];
+                if (j >= ncols) S->h_loc[(size_t)p] = (int)(n + (j - ncols));
+                else if (j >= c0 && j < c0 + n) S->h_loc[(size_t)p] = (int)(j - c0);
+            }
+            S->loc.upload(S->h_loc, s);
+            const size_t mm = (size_t)std::max(m, 1);
+            S->aB.ensure(mm);
+            S->zeros.ensure(mm);
+            IPXK_HIP(hipMemsetAsync(S->zeros.get(), 0, mm * sizeof(double), s));
+        }
     }
     finish_prepare(c, S.get(), status, colscale);
     if (verbose)
@@ -1596,6 +1783,7 @@ __global__ void perms_from_lu_kernel(int m, const ipxint* __restrict__ rowperm, 
 // SplittedNormalMatrix::Prepare (splitted_normal_matrix.cc:18-66) with L, U and the permutations never leaving the
 // device.
 void split_prepare_lu(Context* c, const ipxint* status, const double* colscale) {
+    IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
     maxvol_drop_etas(c);
     LuView V;
     IPXK_REQUIRE(lu_view(c, &V) && V.from_basis, "no LU factorization of a basis of this context's matrix (ipxk_lu_factorize_basis)");
@@ -1603,12 +1791,12 @@ void split_prepare_lu(Context* c, const ipxint* status, const double* colscale) 
                               "(Basis::AdaptToSingularFactorization, src/basis.cc)");
     const int m = (int)c->m;
     IPXK_REQUIRE(V.dim == m, "dimension mismatch");
-    IPXK_REQUIRE(c->nranks == 1, "the basis path does not shard: run it as independent replicas");
     hipStream_t s = c->stream;
     std::unique_ptr<SplitOperator> S(c->split ? c->split : c->split_spare ? c->split_spare : new SplitOperator);
     if (!c->split) c->split_spare = nullptr;
     c->split = nullptr;
     S->m = m;
+    S->part = false;
     if (const char* e = getenv("IPXK_TRISOLVE")) S->level_launches = std::string(e) == "levels";
     // the dense bump leaves the level-scheduled structure (SplitOperator::bump_*)
     DeviceFactors F = V.F;
@@ -1638,6 +1826,21 @@ void split_prepare_lu(Context* c, const ipxint* status, const double* colscale) 
 // splitted_normal_matrix.cc:30-55).  The level schedule and the packed factors are reused.
 void split_rescale_host(Context* c, const ipxint* status, const double* colscale) {
     SplitOperator* S = c->split;
+    split_check_partition(c);
+    if (S->part) {          // the ranks agree on the verdict and on the slack parts before the collective of the scaling
+        const int m = S->m, n = (int)c->n;
+        std::string err;
+        uint64_t fp = 0;
+        try {
+            check_status_host((int64_t)n + m, status);
+            Fingerprint F;
+            F.add(status + n, (size_t)m); F.add(colscale + n, (size_t)m);
+            fp = F.h;
+        } catch (const Error& e) {
+            err = e.what();
+        }
+        agree_on_arguments(c, err, fp);
+    }
     upload_scaling(c, S, status, colscale);
     IPXK_HIP(hipStreamSynchronize(c->stream));
 }
@@ -1709,19 +1912,25 @@ int split_apply_dev(Context* c, const double* rhs, double* lhs, const int* done)
     run_sweep(c, S->Lt, !etas, S->Ut.y.get(), done, S->row_after_backward.get(), u);
     time_mark(c, kTimeBt, false);
     time_mark(c, kTimeOp, true);
-    // N N' of it: A (M D^2) A'
-    EpiScale e1{{}, S->Wsplit.get(), c->tcols.get()};
-    EpiNormalRows e2{{}, S->Wsplit.get() + n, u, work};
-    if (S->real_N) {
-        nmatrix_apply(c, S->Wsplit.get() + n, u, work, done);
-    } else if (S->masked_values) {
-        // the entries of BASIC / fixed columns have weight zero in both passes: masked value arrays, no gathers for them
-        launch_spmv<EpiScale, true>(c->Acols, u, e1, nullptr, done, s);
-        launch_spmv<EpiNormalRows, true>(c->Arows, c->tcols.get(), e2, nullptr, done, s);
-    } else {
-        launch_spmv(c->Acols, u, e1, nullptr, done, s);
-        launch_spmv(c->Arows, c->tcols.get(), e2, nullptr, done, s);
-    }
+    // N N' of it: A (M D^2) A'.  Column partition: this rank's N_g N_g' (the slack term on rank 0 only), summed over
+    // the ranks by one all-reduce of m -- enqueued whatever `done` says, so that every rank takes part in it
+    auto product = [&](double* out) {
+        const double* wI = S->part && c->rank != 0 ? nullptr : S->Wsplit.get() + n;
+        EpiScale e1{{}, S->Wsplit.get(), c->tcols.get()};
+        EpiNormalRows e2{{}, wI, u, out};
+        if (S->real_N) {
+            nmatrix_apply(c, wI, u, out, done);
+        } else if (S->masked_values) {
+            // the entries of BASIC / fixed columns have weight zero in both passes: masked value arrays, no gathers for them
+            launch_spmv<EpiScale, true>(c->Acols, u, e1, nullptr, done, s);
+            launch_spmv<EpiNormalRows, true>(c->Arows, c->tcols.get(), e2, nullptr, done, s);
+        } else {
+            launch_spmv(c->Acols, u, e1, nullptr, done, s);
+            launch_spmv(c->Arows, c->tcols.get(), e2, nullptr, done, s);
+        }
+    };
+    if (S->part) allreduce_product(c, work, (size_t)m, product);
+    else product(work);
     time_mark(c, kTimeOp, false);
     // inverse(B) * that (the L sweep reads `work` through rowperm)
     time_mark(c, kTimeB, true);
@@ -1838,10 +2047,122 @@ struct EpiBasisResidual : ProdMul {
     __device__ __forceinline__ void finish(int i, double acc, double&) const { out[i] = acc - tI[i]; }
 };
 
+// ---- the same on a column-partitioned context: kernels by basis position (pos_status, pos_scale, aB = a[basis[.]]) ----
+__global__ void basis_free_rhs_pos_kernel(int m, const int* __restrict__ pos_status, const double* __restrict__ aB,
+                                          double* __restrict__ work) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x)
+        work[p] = pos_status[p] == IPXK_BASIC_FREE ? aB[p] : 0.0;
+}
+__global__ void basis_reduce_rhs_pos_kernel(int m, const int* __restrict__ pos_status, const double* __restrict__ pos_scale,
+                                            const double* __restrict__ aB, const double* __restrict__ work,
+                                            double* __restrict__ rhs) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
+        if (pos_status[p] == IPXK_BASIC) {
+            const double d = pos_scale[p];
+            rhs[p] = (rhs[p] - work[p]) / d + aB[p] * d;
+        } else {
+            rhs[p] = 0.0;
+        }
+    }
+}
+__global__ void basis_unscale_y_pos_kernel(int m, const int* __restrict__ pos_status, const double* __restrict__ pos_scale,
+                                           const double* __restrict__ aB, double* __restrict__ y) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x)
+        y[p] = pos_status[p] == IPXK_BASIC ? y[p] / pos_scale[p] : aB[p];
+}
+// x_B into the entries this rank holds: its own structural columns and every slack column
+__global__ void basis_scatter_x_pos_kernel(int m, const int* __restrict__ loc, const double* __restrict__ work,
+                                           double* __restrict__ x) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
+        const int l = loc[p];
+        if (l >= 0) x[l] = work[p];
+    }
+}
+
+// Three all-reduces of m (a_B, the right-hand side product, b - N x_N) plus one per CR Apply.  Structural products
+// are this rank's partials; b and the slack terms enter on rank 0 only.  Every m-vector is then the same on all ranks.
+static CrResult kkt_basis_solve_cols(Context* c, const double* a, const double* b, double tol, ipxint maxiter,
+                                     double* x, double* y, ipxk_interrupt_fn interrupt, void* user, ipxk_times* times) {
+    SplitOperator* S = c->split;
+    const int m = S->m, n = (int)c->n;
+    hipStream_t s = c->stream;
+    const int g = vec_grid(m);
+    const double* W = S->Wsplit.get();
+    double* rhs = S->w2.get();
+    double* work = S->w1.get();
+    if (c->v_lhs.size() < (size_t)std::max(m, 1)) c->v_lhs.resize(std::max(m, 1));
+    if (c->v_rhs.size() < (size_t)std::max(m, 1)) c->v_rhs.resize(std::max(m, 1));
+    double* lhs = c->v_lhs.get();
+    double* crrhs = c->v_rhs.get();
+    const bool lead = c->rank == 0;
+    const double* zeros = S->zeros.get();
+    double* aB = S->aB.get();
+
+    // a_B[p] = a[basis[p]]: the owners' entries, then the slack positions
+    allreduce_product(c, aB, (size_t)m, [&](double* out) {
+        hipLaunchKernelGGL(pos_contrib_kernel, dim3(g), dim3(kBlock), 0, s, m, n, S->loc.get(), a, out);
+    });
+    hipLaunchKernelGGL(pos_slack_kernel, dim3(g), dim3(kBlock), 0, s, m, n, S->loc.get(), a, aB);
+    // :87-99
+    if (S->num_free > 0) {
+        hipLaunchKernelGGL(basis_free_rhs_pos_kernel, dim3(g), dim3(kBlock), 0, s, m, S->pos_status.get(), (const double*)aB,
+                           S->tI.get());
+        solve_dense_dev(c, S->tI.get(), work, 'T');
+    }
+    const double* wk = S->num_free > 0 ? work : nullptr;
+    // :101-121  rhs = sum over nonbasic j of AI[:,j] * d2_j*(a_j - AI[:,j]'work): this rank's columns, slacks on rank 0
+    if (wk) {
+        EpiBasisColumns ec{{}, W, a, c->tcols.get()};
+        launch_spmv(c->Acols, wk, ec, nullptr, nullptr, s);
+    } else {
+        hipLaunchKernelGGL(basis_slack_kernel, dim3(vec_grid(n)), dim3(kBlock), 0, s, n, W, a,
+                           (const double*)nullptr, c->tcols.get());
+    }
+    hipLaunchKernelGGL(basis_slack_kernel, dim3(g), dim3(kBlock), 0, s, m, W + n, a + n, wk, S->tI.get());
+    allreduce_product(c, rhs, (size_t)m, [&](double* out) {
+        EpiBasisRhs er{{}, lead ? S->tI.get() : zeros, out};
+        launch_spmv(c->Arows, c->tcols.get(), er, nullptr, nullptr, s);
+    });
+    solve_dense_dev(c, rhs, rhs, 'N');
+    // :124
+    solve_dense_dev(c, b, work, 'N');
+    // :128-138
+    hipLaunchKernelGGL(basis_reduce_rhs_pos_kernel, dim3(g), dim3(kBlock), 0, s, m, S->pos_status.get(), S->pos_scale.get(),
+                       (const double*)aB, work, rhs);
+    // :141-157
+    hipLaunchKernelGGL(gather_perm_kernel, dim3(g), dim3(kBlock), 0, s, m, rhs, S->colperm.get(), crrhs,
+                       (const int*)nullptr);
+    IPXK_HIP(hipMemsetAsync(lhs, 0, sizeof(double) * m, s));
+    CrResult res = cr_solve_dev(c, crrhs, tol, nullptr, maxiter, lhs, true, interrupt, user, nullptr, 0, times);
+    // :160-175
+    hipLaunchKernelGGL(scatter_perm_kernel, dim3(g), dim3(kBlock), 0, s, m, lhs, S->colperm.get(), y,
+                       (const int*)nullptr);
+    hipLaunchKernelGGL(basis_unscale_y_pos_kernel, dim3(g), dim3(kBlock), 0, s, m, S->pos_status.get(), S->pos_scale.get(),
+                       (const double*)aB, y);
+    solve_dense_dev(c, y, y, 'T');
+    // :178-188  x[nonbasic] of this rank's columns and of the slacks, work = b - N*x[nonbasic] summed over the ranks
+    {
+        EpiBasisColumns ec{{}, W, a, x};
+        launch_spmv(c->Acols, y, ec, nullptr, nullptr, s);
+        hipLaunchKernelGGL(basis_slack_kernel, dim3(g), dim3(kBlock), 0, s, m, W + n, a + n, (const double*)y,
+                           x + n);
+        allreduce_product(c, work, (size_t)m, [&](double* out) {
+            EpiBasisResidual er{{}, lead ? b : zeros, lead ? x + n : zeros, out};
+            launch_spmv(c->Arows, x, er, nullptr, nullptr, s);
+        });
+    }
+    // :191-193
+    solve_dense_dev(c, work, work, 'N');
+    hipLaunchKernelGGL(basis_scatter_x_pos_kernel, dim3(g), dim3(kBlock), 0, s, m, S->loc.get(), work, x);
+    IPXK_HIP(hipGetLastError());
+    return res;
+}
+
 CrResult kkt_basis_solve_dev(Context* c, const double* a, const double* b, double tol, ipxint maxiter,
                              double* x, double* y, ipxk_interrupt_fn interrupt, void* user,
                              ipxk_times* times) {
     SplitOperator* S = c->split;
+    if (S->part) return kkt_basis_solve_cols(c, a, b, tol, maxiter, x, y, interrupt, user, times);
     const int m = S->m, n = (int)c->n;
     hipStream_t s = c->stream;
     const int g = vec_grid(m);

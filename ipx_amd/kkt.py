@@ -553,6 +553,10 @@ class KktContext:
 
     # -- SplittedNormalMatrix / KKTSolverBasis -------------------------------------------
     def split_prepare(self, L, U, rowperm, colperm, basis, status, colscale):
+        """SplittedNormalMatrix::Prepare from host factors.  On a column-partitioned context (comm_init with
+        columns=True) it is collective: L, U, rowperm, colperm and basis (m entries, GLOBAL numbering 0..n_global+m)
+        are the same on every rank, status and colscale are local ([this rank's slice; all m slacks]).  If any rank's
+        arguments are wrong, or the replicated ones differ, every rank raises KktError(IPXK_E_ARGUMENT)."""
         args = [_I(L.p), _I(L.i), _F(L.x), _I(U.p), _I(U.i), _F(U.x), _I(rowperm), _I(colperm),
                 _I(basis), _I(status), _F(colscale)]
         self._check(self.lib.ipxk_split_prepare(
@@ -628,10 +632,13 @@ class KktContext:
         return out
 
     def split_rescale(self, status, colscale):
+        """New scaling for the prepared basis; collective on a column-partitioned context (local status, colscale)."""
         status, colscale = _I(status), _F(colscale)
         self._check(self.lib.ipxk_split_rescale(self.h, _ip(status), _fp(colscale)))
 
     def split_apply(self, rhs, want_dot=True):
+        """lhs = (I + B~^-1 N N' B~^-T) rhs with free positions zeroed.  Column partition: rhs and lhs are m-vectors,
+        replicated; one all-reduce of m per call."""
         rhs = _F(rhs)
         lhs = np.zeros(self.m, f64)
         dot = c_f64(0.0)
@@ -661,6 +668,8 @@ class KktContext:
         return [int(v) for v in lv]
 
     def kkt_basis_solve(self, a, b, tol, maxiter=-1):
+        """KKTSolverBasis::_Solve.  Column partition: a and x are local ([this rank's slice; all m slacks]), b and y
+        replicated; x holds the basic entries this rank owns and all slack entries (partition.assemble_cols)."""
         a, b = _F(a), _F(b)
         x, y = np.zeros(self.n + self.m, f64), np.zeros(self.m, f64)
         it, err, times = c_i64(0), c_i64(0), Times()
@@ -689,7 +698,11 @@ class KktContext:
         Collective over the ranks.  It also classifies the dense columns of the whole matrix, so num_dense_cols
         is the same on every rank, and dense-column (Sherman-Morrison-Woodbury) preconditioning works on either
         partition: with rows, diag_apply returns this rank's slice and diag_get the local diagonal with the
-        global k x k factor; with columns, both are replicated."""
+        global k x k factor; with columns, both are replicated.
+
+        With columns=True the basis path (split_prepare, split_rescale, split_apply, the triangular solves,
+        cr_solve, kkt_basis_solve) runs too, with the slabs of partition.col_slab (contiguous, in rank order) and
+        the global basis numbering; the device LU and Maxvolume do not.  With rows the basis path is refused."""
         buf = (C.c_char * 128).from_buffer_copy(unique_id)
         fn = self.lib.ipxk_comm_init_columns if columns else self.lib.ipxk_comm_init
         self._check(fn(self.h, buf, C.c_int(rank), C.c_int(nranks)))

@@ -79,6 +79,27 @@ def col_slab(A, st, rank, world):
                    st["b"])
 
 
+REPLICATED = -1
+
+
+def col_owner(j, n, world):
+    """Where the global variables j (0..n+m-1; an int or an array) live under col_slab's ranges.
+
+    Returns (rank, local).  A structural column j < n belongs to one rank and sits at index `local` of that rank's
+    slab.  A slack column j >= n is replicated: rank is REPLICATED and local = j - n, its slack index, which is at
+    n_local + j - n of every rank's local (n+m)-vector."""
+    jj = np.asarray(j, dtype=i64)
+    starts = np.array([row_range(n, r, world)[0] for r in range(world)], dtype=i64)
+    # among ranks that start at the same column only the last one can own it (the others are empty)
+    rank = np.searchsorted(starts, jj, side="right").astype(i64) - 1
+    slack = jj >= n
+    rank = np.where(slack, REPLICATED, rank)
+    local = np.where(slack, jj - n, jj - starts[np.clip(rank, 0, world - 1)])
+    if np.ndim(j) == 0:
+        return int(rank), int(local)
+    return rank, local
+
+
 def assemble_cols(m, parts_x):
     """x = [structural slices in rank order ; slack part (identical on every rank)]."""
     return np.concatenate([p[:len(p) - m] for p in parts_x] + [parts_x[0][len(parts_x[0]) - m:]])
