@@ -453,7 +453,10 @@ int ipxk_kkt_basis_solve(ipxk_context* ctx, const double* a, const double* b,
  * solver (use_basis = 1) to tol, and recovers the Newton step dx, dxl, dxu, dzl,
  * dzu [n+m], dy [m].  xl, xu, zl, zu are the iterate's vectors, state[n+m] the
  * IPXK_STATE_* codes.  With device pointers nothing crosses PCIe.  On errflag != 0
- * the step vectors are undefined (ipm.cc:571-573 returns). */
+ * the step vectors are undefined (ipm.cc:571-573 returns).
+ * Column partition (ipxk_comm_init_columns): rb, dy replicated, every (n+m)-vector
+ * local [this rank's structural slice; all m slack entries]; collectives are those
+ * of the KKT solve only.  A row-partitioned context is refused (IPXK_E_ARGUMENT). */
 int ipxk_newton_solve(ipxk_context* ctx, int use_basis, const double* rb,
                       const double* rc, const double* rl, const double* ru,
                       const double* sl, const double* su, const double* xl,
@@ -467,7 +470,18 @@ int ipxk_newton_solve(ipxk_context* ctx, int use_basis, const double* rb,
 /* ---- the IPM iterate on the device -----------
  * Iterate::Initialize / accessors (src/iterate.cc:60-92): the six vectors
  * x, xl, xu, zl, zu [n+m], y [m] and one IPXK_STATE_* byte per variable are
- * copied into the context. */
+ * copied into the context.
+ * Column partition (ipxk_comm_init_columns): the (n+m)-vectors and state are
+ * local [this rank's structural slice; all m slack entries], y is replicated.
+ * The scalars of the calls below (residual norms, complementarity, objectives,
+ * the step lengths and the driver's decisions) are global and bitwise the same
+ * on every rank; with one rank they equal the unpartitioned context's.  Each rank
+ * reduces its own entries, one all-gather carries the per-rank values, every rank
+ * combines them in rank order; the slack terms and b'y count on rank 0 only.
+ * ipxk_iterate_set is collective there: one all-reduce carries each rank's
+ * verdict and a fingerprint of y and the slack parts of x, xl, xu, zl, zu and
+ * state; if any rank's arguments are wrong or they differ, every rank fails
+ * with IPXK_E_ARGUMENT. */
 int ipxk_iterate_set(ipxk_context* ctx, const double* x, const double* xl,
                      const double* xu, const double* y, const double* zl,
                      const double* zu, const unsigned char* state);
@@ -483,18 +497,23 @@ int ipxk_iterate_update(ipxk_context* ctx, double sp, const double* dx,
 /* Iterate::ComputeResiduals (src/iterate.cc:536-588) for the model vectors
  * b[m], c, lb, ub [n+m]: rb = b - AI x, rc = c - AI'y - zl + zu (0 on fixed
  * variables), rl = lb - x + xl, ru = ub - x - xu (0 without that barrier
- * term); presidual = max(|rb|,|rl|,|ru|)_inf, dresidual = |rc|_inf. */
+ * term); presidual = max(|rb|,|rl|,|ru|)_inf, dresidual = |rc|_inf.
+ * Column partition: b, rb replicated, c, lb, ub, rc, rl, ru local; one
+ * all-reduce of m (rb) and one all-gather of 2 per rank.  Row partition: refused. */
 int ipxk_iterate_residuals(ipxk_context* ctx, const double* b, const double* c,
                            const double* lb, const double* ub, double* rb,
                            double* rc, double* rl, double* ru,
                            double* presidual, double* dresidual);
 /* Iterate::ComputeComplementarity (src/iterate.cc:642-670):
- * out4 = {complementarity, mu, mu_min, mu_max} (host memory) */
+ * out4 = {complementarity, mu, mu_min, mu_max} (host memory).  Column partition:
+ * global, one all-gather of 4 per rank (row partition: this rank's terms only). */
 int ipxk_iterate_complementarity(ipxk_context* ctx, double out4[4]);
 /* StepToBoundary (src/ipm.cc:320-339): largest alpha <= alpha0 with
  * x + alpha*dx >= 0, damped by 1 - eps at the blocking index (-1: none).
  * Parallel minimum over the candidates; equals the reference's sequential
- * scan except when alpha lands within one ulp factor of another candidate. */
+ * scan except when alpha lands within one ulp factor of another candidate.
+ * A generic vector primitive: rank-local on a partitioned context (no
+ * collective; the index is local).  ipxk_ipm_step takes the global form. */
 int ipxk_step_to_boundary(ipxk_context* ctx, const double* x, const double* dx,
                           ipxint len, double alpha0, double* alpha,
                           ipxint* blocking_index);
@@ -506,7 +525,17 @@ int ipxk_step_to_boundary(ipxk_context* ctx, const double* x, const double* dx,
  * factorizes for the current iterate first, as IPM::Driver does
  * (ipxk_iterate_factorize_diag for the diag solver).  b[m], c, lb, ub [n+m]
  * are the model's vectors.  On errflag != 0 (from a KKT solve) the iterate is
- * left unchanged. */
+ * left unchanged.
+ * Column partition: b replicated, c, lb, ub local; use_basis = 1 after
+ * ipxk_split_prepare with replicated host factors.  Every field of info is the
+ * same on every rank.  Collectives besides the two KKT solves: one all-reduce of
+ * m (rb), then all-gathers of per-rank rows: 6 (residual norms, complementarity),
+ * 24 twice (the four step-to-boundary problems: alpha, global blocking index
+ * c0 + j or n_global + i, and x, dx, z, dz there; the first gives the
+ * lexicographic minimum of (alpha, index), the reference's first-index rule),
+ * 1 twice (complementarity at the trial point), 4 (mu after the step); the first
+ * call also learns the column offsets (one all-gather of 1).  Row partition:
+ * refused. */
 typedef struct ipxk_ipm_step_info {
     double step_primal, step_dual;   /* IPM::step_primal_, step_dual_ */
     double mu_before, mu_after;      /* Iterate::mu() before / after the update */
@@ -528,7 +557,9 @@ int ipxk_iterate_factorize_diag(ipxk_context* ctx, int precond_dense_cols,
  * the model vectors: out3 = {pobjective, dobjective, offset}; pobjective + offset
  * and dobjective + offset are the objectives after postprocessing (:203-211).
  * Variable states as in ipxk_iterate_set (the implied states of the basis solver's
- * drop procedures do not exist on the device). */
+ * drop procedures do not exist on the device).  Column partition: global, one
+ * all-gather of 4 per rank (offset and the fixed structural x_j A_j'y included).
+ * Row partition: refused. */
 int ipxk_iterate_objectives(ipxk_context* ctx, const double* b, const double* c,
                             const double* lb, const double* ub, double out3[3]);
 
@@ -540,7 +571,15 @@ int ipxk_iterate_objectives(ipxk_context* ctx, const double* b, const double* c,
  * (IPX_STATUS_optimal 1, primal_infeas 3, dual_infeas 4, time_limit 5,
  * iter_limit 6, no_progress 7, failed 8).  A CR failure of the diag solver ends
  * the loop with IPX_STATUS_failed and the CR errflag: that is where LpSolver
- * switches to the basis solver (src/lp_solver.cc:399-418), the caller's move. */
+ * switches to the basis solver (src/lp_solver.cc:399-418), the caller's move.
+ * Column partition: b replicated, c, lb, ub local (ipxk_iterate_set's forms).
+ * At entry one all-reduce carries each rank's verdict and a fingerprint of b and
+ * the slack parts of c, lb, ub (mismatch: IPXK_E_ARGUMENT on every rank).  Every
+ * decision is taken from replicated scalars, and interrupt(user) is agreed once
+ * per iteration (max over the ranks), so all ranks return the same info in the
+ * same iteration.  Per iteration besides the KKT factorize and solves: one
+ * all-reduce of m, all-gathers of 10, 24, 1, 24, 1, 4 doubles per rank and one
+ * all-reduce (max) of 1.  Row partition: refused. */
 typedef struct ipxk_ipm_params {
     double kkt_tol;            /* ipx_parameters::kkt_tol, 0.3 */
     double feasibility_tol;    /* ipm_feasibility_tol, 1e-6 */
@@ -569,7 +608,8 @@ int ipxk_ipm_driver(ipxk_context* ctx, const double* b, const double* c,
  * crash_basis = 0, src/basis.cc:353-385); DropPrimal / DropDual (:36-43) are not taken.  Models whose
  * iterate holds free or fixed variables are refused (IPXK_E_UNSUPPORTED).  basis_out[m] / status_out[n+m]
  * (either may be NULL) return the final basis.  params->kkt_maxiter is ignored (KKTSolverBasis runs CR with
- * maxiter = -1).  Limits of the refactorizations: see ipxk_lu_factorize (dense bump). */
+ * maxiter = -1).  Limits of the refactorizations: see ipxk_lu_factorize (dense bump).  Refused on any partitioned
+ * context (it needs the device LU and Maxvolume). */
 int ipxk_ipm_driver_basis(ipxk_context* ctx, const double* b, const double* c,
                           const double* lb, const double* ub,
                           const ipxk_ipm_params* params, ipxk_ipm_info* info,
@@ -598,7 +638,8 @@ int ipxk_comm_init(ipxk_context* ctx, const void* id128, int rank, int nranks);
  * each rank keeps the dense columns it owns, and the first Factorize with
  * dense-column preconditioning gathers those of every rank.  The basis path
  * (ipxk_split_prepare and what uses its operator) runs on this partition; see
- * ipxk_split_prepare for its conventions. */
+ * ipxk_split_prepare for its conventions.  So does the device IPM (the iterate,
+ * ipxk_newton_solve, ipxk_ipm_step, ipxk_ipm_driver); see ipxk_iterate_set. */
 int ipxk_comm_init_columns(ipxk_context* ctx, const void* id128, int rank, int nranks);
 /* What the transport itself reports about the communicator of this context:
  * transport 0 = none, 1 = RCCL (nranks / rank from ncclCommCount /

@@ -582,22 +582,44 @@ static void copy_out(Context* c, void* dst, const void* src_dev, size_t bytes) {
     else IPXK_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
 }
 
+// Column partition: the ranks agree on the verdict and on the replicated parts (y, the slack parts of x, xl, xu, zl, zu
+// and state) with one all-reduce, so that ranks holding different iterates fail together instead of in a later collective.
 int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const double* xu, const double* y,
                      const double* zl, const double* zu, const unsigned char* state) {
     return guarded([&] {
-        IPXK_REQUIRE(c && x && xl && xu && y && zl && zu && state, "NULL argument");
+        IPXK_REQUIRE(c, "NULL argument");
+        const bool args = x && xl && xu && y && zl && zu && state;
+        if (!comm_cols(c)) IPXK_REQUIRE(args, "NULL argument");
         bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        c->it_set = false;
+        const size_t m = (size_t)c->m, n = (size_t)c->n, N = (size_t)(c->n + c->m);
         DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
         const double* src[6] = {x, xl, xu, y, zl, zu};
-        for (int k = 0; k < 6; k++) {
-            const size_t len = k == 3 ? m : N;
-            dst[k]->resize(std::max<size_t>(len, 1));
-            copy_in(c, dst[k]->get(), src[k], len * sizeof(double));
+        if (args) {
+            for (int k = 0; k < 6; k++) {
+                const size_t len = k == 3 ? m : N;
+                dst[k]->resize(std::max<size_t>(len, 1));
+                copy_in(c, dst[k]->get(), src[k], len * sizeof(double));
+            }
+            c->it_state.resize(std::max<size_t>(N, 1));
+            copy_in(c, c->it_state.get(), state, N);
         }
-        c->it_state.resize(std::max<size_t>(N, 1));
-        copy_in(c, c->it_state.get(), state, N);
         IPXK_HIP(hipStreamSynchronize(c->stream));
+        if (comm_cols(c)) {
+            uint64_t fp = 0;
+            if (args) {
+                std::vector<double> h(6 * m);
+                for (int k = 0; k < 6; k++) staged_d2h(h.data() + k * m, dst[k]->get() + (k == 3 ? 0 : n), m * sizeof(double), c->stream);
+                std::vector<unsigned char> hs(m);
+                staged_d2h(hs.data(), c->it_state.get() + n, m, c->stream);
+                Fingerprint F;
+                F.add(h.data(), h.size());
+                F.add(hs.data(), hs.size());
+                fp = F.h;
+            }
+            agree_on_arguments(c, args ? std::string() : std::string("NULL argument"), fp, "ipxk_iterate_set",
+                               "y and the slack parts of x, xl, xu, zl, zu and state");
+        }
         c->it_set = true;
     });
 }
@@ -678,7 +700,8 @@ int ipxk_ipm_step(ipxk_context* c, int use_basis, const double* b, const double*
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && info, "NULL argument");
         IPXK_REQUIRE(use_basis ? c->split != nullptr : c->kkt_diag_factorized, "KKT solver not factorized");
-        IPXK_REQUIRE(!comm_active(c), "ipxk_ipm_step is not available on a partitioned system");
+        IPXK_REQUIRE(!comm_rows(c), "ipxk_ipm_step does not run on a row-partitioned system: partition the structural columns "
+                                    "(ipxk_comm_init_columns)");
         bind_device(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         const double* db = stage_in(c, b, m, c->nw_in[0]);
@@ -709,7 +732,6 @@ int ipxk_ipm_driver(ipxk_context* c, const double* b, const double* cc, const do
                     const ipxk_ipm_params* params, ipxk_ipm_info* info, ipxk_interrupt_fn interrupt, void* interrupt_user) {
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && params && info, "NULL argument");
-        IPXK_REQUIRE(!comm_active(c), "ipxk_ipm_driver is not available on a partitioned system");
         bind_device(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         const double* db = stage_in(c, b, m, c->nw_in[0]);
@@ -726,7 +748,7 @@ int ipxk_ipm_driver_basis(ipxk_context* c, const double* b, const double* cc, co
                           ipxk_interrupt_fn interrupt, void* interrupt_user) {
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && params && info, "NULL argument");
-        IPXK_REQUIRE(!comm_active(c), "ipxk_ipm_driver_basis is not available on a partitioned system");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // its Factorize runs the device LU and Maxvolume
         bind_device(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         const double* db = stage_in(c, b, m, c->nw_in[0]);

@@ -412,6 +412,33 @@ void comm_allreduce_sum_staged(Context* c, double* dst, size_t count) {
     c->direct->allreduce(c, dst, count, 0, true);
 }
 
+std::vector<double> comm_gather_table(Context* c, const double* row_dev, size_t k) {
+    const size_t R = (size_t)c->nranks;
+    c->it_table.ensure(R * k);
+    comm_allgather(c, row_dev, c->it_table.get(), k);
+    std::vector<double> h(R * k);
+    c->it_table.download(h.data(), h.size(), c->stream);
+    IPXK_HIP(hipStreamSynchronize(c->stream));
+    comm_check(c);
+    return h;
+}
+
+// max of [failed, hi, lo, -hi, -lo] over the ranks; max == -max(-.) iff all fingerprints agree
+void agree_on_arguments(Context* c, const std::string& err, uint64_t h, const char* who, const char* what) {
+    const double hi = (double)(h >> 32), lo = (double)(h & 0xffffffffull);
+    double v[5] = {err.empty() ? 0.0 : 1.0, hi, lo, -hi, -lo};
+    DevBuf<double> d(5);
+    d.upload(v, 5, c->stream);
+    comm_allreduce_max(c, d.get(), 5);
+    d.download(v, 5, c->stream);
+    IPXK_HIP(hipStreamSynchronize(c->stream));
+    comm_check(c);
+    if (!err.empty()) throw Error(IPXK_E_ARGUMENT, err);
+    if (v[0] != 0.0) throw Error(IPXK_E_ARGUMENT, std::string("another rank refused its arguments of ") + who);
+    if (v[1] != -v[3] || v[2] != -v[4])
+        throw Error(IPXK_E_ARGUMENT, std::string("the replicated arguments of ") + who + " (" + what + ") differ between the ranks");
+}
+
 void comm_destroy(Context* c) {
     c->col_offset = -1;
     c->n_global = 0;

@@ -126,6 +126,7 @@ struct Context {
 
     // ---- the IPM iterate (iterate.hip) ----
     DevBuf<double> it_x, it_xl, it_xu, it_y, it_zl, it_zu, it_partials;
+    DevBuf<double> it_row, it_bnd, it_table;   // column partition: this rank's row of scalars, step-to-boundary partials, gathered rows
     DevBuf<unsigned char> it_state;
     bool it_set = false;
     DevBuf<double> ipm[12];            // residuals, complementarity targets and the step of ipxk_ipm_step
@@ -257,14 +258,31 @@ void iterate_update_dev(Context* c, double sp, const double* dx, const double* d
 void iterate_residuals_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
                            double* rb, double* rc, double* rl, double* ru, double* presidual, double* dresidual);
 void iterate_complementarity_dev(Context* c, double out4[4], double* num_terms = nullptr);
+// the scalars of the iterate at one point of the IPM, on a column-partitioned context from ONE all-gather
+enum IterWhat : unsigned { kIterResiduals = 1, kIterComplementarity = 2, kIterObjectives = 4 };
+struct IterScalars {
+    double presidual = 0, dresidual = 0;
+    double comp[4] = {0, 0, 0, 0};      // complementarity, mu, mu_min, mu_max
+    double num_terms = 0;
+    double obj[3] = {0, 0, 0};          // pobjective, dobjective, offset
+};
+void iterate_scalars_dev(Context* c, unsigned what, const double* b, const double* cc, const double* lb, const double* ub,
+                         double* rb, double* rc, double* rl, double* ru, IterScalars* out);
+// column partition: the step-to-boundary problems of xl, xu, zl, zu over all ranks (iterate.hip)
+struct BoundaryVectors { const double *xl, *dxl, *zl, *dzl, *xu, *dxu, *zu, *dzu; };
+struct Boundary { double alpha, index, x, dx, z, dz; };   // index: global, -1 if nothing blocks
+void steps_to_boundary_part(Context* c, const BoundaryVectors& V, double alpha0, Boundary out[4]);
 void iterate_objectives_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double out3[3]);
 void model_norms_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double out2[2]);
 double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64_t len, double alpha0,
                             ipxint* blocking);
 
 // ---- ipm_step.hip ----
+// pre: residuals (in ipm[0..3]) and complementarity of the current iterate when the caller has them; comp_after: the
+// complementarity after the step
 void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc, const double* lb, const double* ub,
-                  double kkt_tol, ipxint maxiter, ipxk_ipm_step_info* info, ipxk_interrupt_fn interrupt, void* user);
+                  double kkt_tol, ipxint maxiter, ipxk_ipm_step_info* info, ipxk_interrupt_fn interrupt, void* user,
+                  const IterScalars* pre = nullptr, double* comp_after = nullptr);
 
 void ipm_driver_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
                     const ipxk_ipm_params* prm, ipxk_ipm_info* info, ipxk_interrupt_fn interrupt, void* user,
@@ -349,6 +367,29 @@ void comm_destroy(Context* c);
 void comm_check(Context* c);             // raises if a collective of the direct transport timed out
 double* comm_stage(Context* c, size_t count);
 void comm_allreduce_sum_staged(Context* c, double* dst, size_t count);
+// all-gather of one row of k doubles per rank (device); returns the nranks x k table, rank-major, on the host
+std::vector<double> comm_gather_table(Context* c, const double* row_dev, size_t k);
+
+// fingerprint of the arguments every rank must hold identically
+struct Fingerprint {
+    uint64_t h = 0x9e3779b97f4a7c15ull;
+    void mix(uint64_t w) { h ^= w; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; }
+    template <class T> void add(const T* p, size_t count) {
+        const size_t len = count * sizeof(T);
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(p);
+        size_t i = 0;
+        for (; i + 8 <= len; i += 8) { uint64_t w; memcpy(&w, b + i, 8); mix(w); }
+        if (i < len) { uint64_t w = 0; memcpy(&w, b + i, len - i); mix(w); }
+        mix((uint64_t)len);
+    }
+};
+// The ranks fail or proceed together, so that no rank enters a later collective alone: this rank's verdict (err empty:
+// accepted) and fingerprint h go through one all-reduce.  Throws IPXK_E_ARGUMENT on every rank if any rank refused or the
+// fingerprints differ; `who` names the call, `what` the replicated arguments.
+void agree_on_arguments(Context* c, const std::string& err, uint64_t h, const char* who, const char* what);
+// column partition: this rank's first structural column and the structural columns of all ranks (Context::col_offset,
+// n_global), one all-gather at the first call that needs them (trisolve.hip)
+void learn_col_offsets(Context* c);
 
 }  // namespace ipxk
 

@@ -60,9 +60,11 @@ __global__ __launch_bounds__(kBlock) void trial_complementarity_kernel(int N, co
     if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 
+// column partition: each rank sums its share (slack terms on rank 0 only), the ranks' sums are added in rank order
 double trial_complementarity(Context* c, const double* dxl, const double* dxu, const double* dzl, const double* dzu,
                              double ap, double ad) {
-    const int N = (int)(c->n + c->m);
+    const bool part = comm_cols(c);
+    const int N = (int)(part && c->rank != 0 ? c->n : c->n + c->m);
     const int g = vec_grid(N);
     c->it_partials.resize((size_t)4 * 1024);
     hipLaunchKernelGGL(trial_complementarity_kernel, dim3(g), dim3(kBlock), 0, c->stream, N, c->it_state.get(),
@@ -72,6 +74,12 @@ double trial_complementarity(Context* c, const double* dxl, const double* dxu, c
     c->it_partials.download(h.data(), h.size(), c->stream);
     double s = 0.0;
     for (double v : h) s += v;
+    if (part) {
+        c->it_row.upload(&s, 1, c->stream);
+        const std::vector<double> T = comm_gather_table(c, c->it_row.get(), 1);
+        s = T[0];
+        for (int r = 1; r < c->nranks; r++) s += T[(size_t)r];
+    }
     return s;
 }
 
@@ -83,9 +91,14 @@ double element(Context* c, const double* dev, ipxint j) {
 
 }  // namespace
 
+// Column partition (comm_cols): the Newton solves are partitioned already; every scalar below is replicated (the
+// reductions of iterate.hip and the step-to-boundary problems over all ranks, whose winners carry the four values
+// StepSizes reads), so every rank takes the same step.
 void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc, const double* lb, const double* ub,
-                  double kkt_tol, ipxint maxiter, ipxk_ipm_step_info* info, ipxk_interrupt_fn interrupt, void* user) {
+                  double kkt_tol, ipxint maxiter, ipxk_ipm_step_info* info, ipxk_interrupt_fn interrupt, void* user,
+                  const IterScalars* pre, double* comp_after) {
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
+    const bool part = comm_cols(c);
     const int n = (int)c->n, m = (int)c->m, N = n + m;
     hipStream_t s = c->stream;
     *info = ipxk_ipm_step_info{};
@@ -97,10 +110,14 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
     const double *xl = c->it_xl.get(), *xu = c->it_xu.get(), *zl = c->it_zl.get(), *zu = c->it_zu.get();
     const unsigned char* state = c->it_state.get();
 
-    iterate_residuals_dev(c, b, cc, lb, ub, rb, rc, rl, ru, &info->presidual, &info->dresidual);
-    double comp[4], num_finite = 0.0;
-    iterate_complementarity_dev(c, comp, &num_finite);
-    const double mu = comp[1];
+    IterScalars S;
+    if (pre) S = *pre;      // the caller's residuals are in ipm[0..3]
+    else iterate_scalars_dev(c, kIterResiduals | kIterComplementarity, b, cc, lb, ub, rb, rc, rl, ru, &S);
+    info->presidual = S.presidual;
+    info->dresidual = S.dresidual;
+    double comp[4];
+    const double num_finite = S.num_terms;
+    const double mu = S.comp[1];
     info->mu_before = mu;
     const double tol = kkt_tol * std::sqrt(mu);           // ipm.cc:572
     const int g = vec_grid(N);
@@ -116,11 +133,19 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
     if (r.errflag) return;
 
     // ---- AddCorrector, :373-435
+    const BoundaryVectors V{xl, dxl, zl, dzl, xu, dxu, zu, dzu};
+    Boundary bd[4];
     ipxint blk;
-    double step_xl = step_to_boundary_dev(c, xl, dxl, N, 1.0, &blk);
-    double step_xu = step_to_boundary_dev(c, xu, dxu, N, 1.0, &blk);
-    double step_zl = step_to_boundary_dev(c, zl, dzl, N, 1.0, &blk);
-    double step_zu = step_to_boundary_dev(c, zu, dzu, N, 1.0, &blk);
+    double step_xl, step_xu, step_zl, step_zu;
+    if (part) {
+        steps_to_boundary_part(c, V, 1.0, bd);
+        step_xl = bd[0].alpha; step_xu = bd[1].alpha; step_zl = bd[2].alpha; step_zu = bd[3].alpha;
+    } else {
+        step_xl = step_to_boundary_dev(c, xl, dxl, N, 1.0, &blk);
+        step_xu = step_to_boundary_dev(c, xu, dxu, N, 1.0, &blk);
+        step_zl = step_to_boundary_dev(c, zl, dzl, N, 1.0, &blk);
+        step_zu = step_to_boundary_dev(c, zu, dzu, N, 1.0, &blk);
+    }
     double maxp = std::min(step_xl, step_xu), maxd = std::min(step_zl, step_zu);
     IPXK_REQUIRE(num_finite > 0.0, "the iterate has no barrier term");
     const double muaff = trial_complementarity(c, dxl, dxu, dzl, dzu, maxp, maxd) / num_finite;
@@ -137,11 +162,16 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
 
     // ---- StepSizes, :437-516
     const double gammaf = 0.9, gammaa = 1.0 / (1.0 - gammaf);
-    ipxint block_xl, block_xu, block_zl, block_zu;
-    step_xl = step_to_boundary_dev(c, xl, dxl, N, 1.0, &block_xl);
-    step_xu = step_to_boundary_dev(c, xu, dxu, N, 1.0, &block_xu);
-    step_zl = step_to_boundary_dev(c, zl, dzl, N, 1.0, &block_zl);
-    step_zu = step_to_boundary_dev(c, zu, dzu, N, 1.0, &block_zu);
+    ipxint block_xl = -1, block_xu = -1, block_zl = -1, block_zu = -1;
+    if (part) {
+        steps_to_boundary_part(c, V, 1.0, bd);
+        step_xl = bd[0].alpha; step_xu = bd[1].alpha; step_zl = bd[2].alpha; step_zu = bd[3].alpha;
+    } else {
+        step_xl = step_to_boundary_dev(c, xl, dxl, N, 1.0, &block_xl);
+        step_xu = step_to_boundary_dev(c, xu, dxu, N, 1.0, &block_xu);
+        step_zl = step_to_boundary_dev(c, zl, dzl, N, 1.0, &block_zl);
+        step_zu = step_to_boundary_dev(c, zu, dzu, N, 1.0, &block_zu);
+    }
     maxp = std::fmin(step_xl, step_xu);
     maxd = std::fmin(step_zl, step_zu);
     double mufull = trial_complementarity(c, dxl, dxu, dzl, dzu, maxp, maxd) / num_finite;
@@ -149,9 +179,15 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
     double alphap = 1.0, alphad = 1.0;
     if (maxp < 1.0) {
         const bool lower = step_xl <= step_xu;
-        const ipxint bp = lower ? block_xl : block_xu;
-        const double z = element(c, lower ? zl : zu, bp), dz = element(c, lower ? dzl : dzu, bp);
-        const double x = element(c, lower ? xl : xu, bp), d = element(c, lower ? dxl : dxu, bp);
+        double z, dz, x, d;
+        if (part) {             // the values at the winner came with it
+            const Boundary& w = bd[lower ? 0 : 1];
+            x = w.x; d = w.dx; z = w.z; dz = w.dz;
+        } else {
+            const ipxint bp = lower ? block_xl : block_xu;
+            z = element(c, lower ? zl : zu, bp); dz = element(c, lower ? dzl : dzu, bp);
+            x = element(c, lower ? xl : xu, bp); d = element(c, lower ? dxl : dxu, bp);
+        }
         const double buffer = mufull / (z + maxd * dz);
         alphap = (x - buffer) / (-d);
         alphap = std::max(alphap, gammaf * maxp);
@@ -159,9 +195,15 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
     }
     if (maxd < 1.0) {
         const bool lower = step_zl <= step_zu;
-        const ipxint bd = lower ? block_zl : block_zu;
-        const double x = element(c, lower ? xl : xu, bd), d = element(c, lower ? dxl : dxu, bd);
-        const double z = element(c, lower ? zl : zu, bd), dz = element(c, lower ? dzl : dzu, bd);
+        double x, d, z, dz;
+        if (part) {
+            const Boundary& w = bd[lower ? 2 : 3];
+            x = w.x; d = w.dx; z = w.z; dz = w.dz;
+        } else {
+            const ipxint bdi = lower ? block_zl : block_zu;
+            x = element(c, lower ? xl : xu, bdi); d = element(c, lower ? dxl : dxu, bdi);
+            z = element(c, lower ? zl : zu, bdi); dz = element(c, lower ? dzl : dzu, bdi);
+        }
         const double buffer = mufull / (x + maxp * d);
         alphad = (z - buffer) / (-dz);
         alphad = std::max(alphad, gammaf * maxd);
@@ -174,6 +216,7 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
     iterate_update_dev(c, info->step_primal, dx, dxl, dxu, info->step_dual, dy, dzl, dzu);
     iterate_complementarity_dev(c, comp);
     info->mu_after = comp[1];
+    if (comp_after) std::copy(comp, comp + 4, comp_after);
     IPXK_HIP(hipGetLastError());
 }
 
@@ -235,9 +278,49 @@ static void basis_factorize_dev(Context* c, std::vector<ipxint>& basis, std::vec
     if (mi.updates == 0 && !first) split_rescale_host(c, status.data(), colscale.data());   // same basis, new scaling (:59-64)
 }
 
+// Column partition (comm_cols): the ranks agree on b and the slack parts of c, lb, ub at entry, every decision below is
+// taken from replicated scalars, and the value of interrupt(user) is agreed once per iteration (max over the ranks), so
+// all ranks leave in the same iteration with the same status.
+static const char* const kDriverRowRefusal =
+    "the device IPM does not run on a row-partitioned system: partition the structural columns (ipxk_comm_init_columns)";
+
+static void driver_agree(Context* c, const double* b, const double* cc, const double* lb, const double* ub) {
+    const size_t m = (size_t)c->m, n = (size_t)c->n;
+    std::string err;
+    uint64_t fp = 0;
+    if (!c->it_set) {
+        err = "no iterate on the device (ipxk_iterate_set)";
+    } else {
+        std::vector<double> h(4 * m);
+        staged_d2h(h.data(), b, m * sizeof(double), c->stream);
+        staged_d2h(h.data() + m, cc + n, m * sizeof(double), c->stream);
+        staged_d2h(h.data() + 2 * m, lb + n, m * sizeof(double), c->stream);
+        staged_d2h(h.data() + 3 * m, ub + n, m * sizeof(double), c->stream);
+        Fingerprint F;
+        F.add(h.data(), h.size());
+        fp = F.h;
+    }
+    agree_on_arguments(c, err, fp, "ipxk_ipm_driver", "b and the slack parts of c, lb and ub");
+}
+
+// max over the ranks of this rank's interrupt value
+static ipxint agree_interrupt(Context* c, ipxint mine) {
+    double v = (double)mine;
+    c->it_row.upload(&v, 1, c->stream);
+    comm_allreduce_max(c, c->it_row.get(), 1);
+    c->it_row.download(&v, 1, c->stream);
+    IPXK_HIP(hipStreamSynchronize(c->stream));
+    comm_check(c);
+    return (ipxint)v;
+}
+
 void ipm_driver_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
                     const ipxk_ipm_params* prm, ipxk_ipm_info* info, ipxk_interrupt_fn interrupt, void* user, bool use_basis,
                     ipxint* basis_out, ipxint* status_out) {
+    IPXK_REQUIRE(!comm_rows(c), kDriverRowRefusal);
+    IPXK_REQUIRE(!(use_basis && comm_active(c)), kDeviceLuRefusal);
+    const bool part = comm_cols(c);
+    if (part) driver_agree(c, b, cc, lb, ub);
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
     std::vector<ipxint> basis, status;
     std::vector<double> colscale;
@@ -254,11 +337,13 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     double best_complementarity = comp[0];               // :315
     ipxint num_bad_iter = 0, errflag = 0;
     while (true) {
-        double obj[3];
-        iterate_residuals_dev(c, b, cc, lb, ub, c->ipm[0].get(), c->ipm[1].get(), c->ipm[2].get(), c->ipm[3].get(),
-                              &info->presidual, &info->dresidual);
-        iterate_complementarity_dev(c, comp);
-        iterate_objectives_dev(c, b, cc, lb, ub, obj);
+        IterScalars S;                                   // residuals, complementarity and objectives: one table
+        iterate_scalars_dev(c, kIterResiduals | kIterComplementarity | kIterObjectives, b, cc, lb, ub, c->ipm[0].get(),
+                            c->ipm[1].get(), c->ipm[2].get(), c->ipm[3].get(), &S);
+        info->presidual = S.presidual;
+        info->dresidual = S.dresidual;
+        std::copy(S.comp, S.comp + 4, comp);
+        const double* obj = S.obj;
         info->pobjective = obj[0] + obj[2];              // after postprocessing, iterate.cc:203-211
         info->dobjective = obj[1] + obj[2];
         info->complementarity = comp[0];
@@ -275,7 +360,11 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
             break;
         }
         if (info->iter >= prm->ipm_maxiter) { info->status_ipm = 6; break; }       // iter_limit
-        if (interrupt && (errflag = interrupt(user)) != 0) break;
+        if (part) {
+            if ((errflag = agree_interrupt(c, interrupt ? interrupt(user) : 0)) != 0) break;
+        } else if (interrupt && (errflag = interrupt(user)) != 0) {
+            break;
+        }
         if (use_basis) {
             basis_factorize_dev(c, basis, status, colscale, first_factorize, info);
             first_factorize = false;
@@ -286,15 +375,15 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
         }
         if (errflag) break;
         ipxk_ipm_step_info st;
-        ipm_step_dev(c, use_basis, b, cc, lb, ub, prm->kkt_tol, use_basis ? -1 : prm->kkt_maxiter, &st, interrupt, user);
+        ipm_step_dev(c, use_basis, b, cc, lb, ub, prm->kkt_tol, use_basis ? -1 : prm->kkt_maxiter, &st, interrupt, user, &S,
+                     comp);
         info->kktiter += st.kktiter_predictor + st.kktiter_corrector;
         errflag = st.errflag;
         if (errflag) break;
         info->step_primal = st.step_primal;
         info->step_dual = st.step_dual;
         if (std::min(st.step_primal, st.step_dual) < 0.05) num_bad_iter++; else num_bad_iter = 0;   // :524-527
-        iterate_complementarity_dev(c, comp);
-        best_complementarity = std::min(best_complementarity, comp[0]);
+        best_complementarity = std::min(best_complementarity, comp[0]);             // comp: after the step
         info->iter++;
     }
     if (errflag) {                                       // :114-121

@@ -190,14 +190,131 @@ __global__ __launch_bounds__(kBlock) void model_norms_kernel(int n, int m, const
     if (threadIdx.x == 0) { out[blockIdx.x] = nb; out[gridDim.x + blockIdx.x] = nc; }
 }
 
-}  // namespace
+// column partition: this rank's share of b - A x (b on rank 0, nullptr elsewhere), summed over the ranks afterwards
+struct EpiIterRbPart : ProdMul {
+    const double* b; double* out;
+    static constexpr bool kNeg = true;
+    __device__ __forceinline__ double init(int r) const { return b ? b[r] : 0.0; }
+    __device__ __forceinline__ void finish(int r, double acc, double&) const { out[r] = acc; }
+};
+// ... then rb[i] = sum[i] - x[n+i]
+__global__ void subtract_slack_kernel(int m, const double* __restrict__ xI, double* __restrict__ rb) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) rb[i] = rb[i] - xI[i];
+}
 
-// out3 = pobjective, dobjective, offset
-void iterate_objectives_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
-                            double out3[3]) {
-    IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
-    IPXK_REQUIRE(!comm_active(c), "the device iterate is not available on a partitioned system");
+// column partition: the four step-to-boundary problems of a step (xl, xu, zl, zu), problem k's block partials at
+// part + 2 g k (alpha, then index).  Lane k reduces them in block order, as step_to_boundary_dev does, and writes
+// row[6k..6k+5] = alpha, GLOBAL blocking index (structural c0 + j, slack n_global + i; -1: none), and the x, dx, z, dz
+// at the candidate that StepSizes reads (the l pair for problems 0 and 2, the u pair for 1 and 3).
+__global__ void boundary_row_kernel(int g, const double* __restrict__ part, double alpha0, int n, double c0, double n_global,
+                                    BoundaryVectors V, double* __restrict__ row) {
+    const int k = threadIdx.x;
+    if (k >= 4) return;
+    const double* a = part + (size_t)2 * g * k;
+    double alpha = alpha0, idx = -1.0;
+    for (int i = 0; i < g; i++)
+        if (a[i] < alpha) { alpha = a[i]; idx = a[g + i]; }
+    double* r = row + 6 * k;
+    r[0] = alpha;
+    if (idx >= 0.0) {
+        const int j = (int)idx;
+        const bool lower = (k & 1) == 0;
+        r[1] = j < n ? c0 + j : n_global + (j - n);
+        r[2] = lower ? V.xl[j] : V.xu[j];
+        r[3] = lower ? V.dxl[j] : V.dxu[j];
+        r[4] = lower ? V.zl[j] : V.zu[j];
+        r[5] = lower ? V.dzl[j] : V.dzu[j];
+    } else {
+        r[1] = -1.0; r[2] = r[3] = r[4] = r[5] = 0.0;
+    }
+}
+
+// ---- column-partitioned contexts (comm_cols) ----
+// Every scalar of the iterate is formed the same way on every rank: each rank reduces its own block partials in block
+// order (as the unpartitioned context does), one all-gather carries the small row of per-rank values, and every rank
+// combines the table in rank order (sums) or in any order (max, min: exact).  The replicated slack entries and b'y enter
+// on rank 0 only, so one rank reproduces the unpartitioned context bit for bit.  Vectors of length n+m are
+// [own structural slice; all m slack entries]; rb is the one m-vector that needs an all-reduce.
+bool with_replicated(const Context* c) { return !comm_cols(c) || c->rank == 0; }
+
+const char* const kIterateRowRefusal =
+    "the device IPM does not run on a row-partitioned system: partition the structural columns (ipxk_comm_init_columns)";
+
+enum CombineOp { kCombineSum, kCombineMax, kCombineMin };
+
+// row[k] (this rank's values) <- the combination over the ranks; one all-gather
+void combine_over_ranks(Context* c, double* row, const CombineOp* ops, int k) {
+    c->it_row.upload(row, (size_t)k, c->stream);
+    const std::vector<double> T = comm_gather_table(c, c->it_row.get(), (size_t)k);
+    for (int f = 0; f < k; f++) {
+        double v = T[(size_t)f];
+        for (int r = 1; r < c->nranks; r++) {
+            const double w = T[(size_t)r * k + f];
+            v = ops[f] == kCombineSum ? v + w : ops[f] == kCombineMax ? std::max(v, w) : std::min(v, w);
+        }
+        row[f] = v;
+    }
+}
+
+// rb, rc, rl, ru of the resident iterate
+void residual_vectors(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double* rb,
+                      double* rc, double* rl, double* ru) {
     const int n = (int)c->n, m = (int)c->m, N = n + m;
+    hipStream_t s = c->stream;
+    if (comm_cols(c)) {
+        // (b - sum_g A_g x_g) - x_slack: the partial sums go straight into the exchange buffer where there is one
+        double* stage = comm_stage(c, (size_t)m);
+        EpiIterRbPart eb{{}, c->rank == 0 ? b : nullptr, stage ? stage : rb};
+        launch_spmv(c->Arows, c->it_x.get(), eb, nullptr, nullptr, s);
+        if (stage) comm_allreduce_sum_staged(c, rb, (size_t)m);
+        else comm_allreduce_sum(c, rb, (size_t)m);
+        hipLaunchKernelGGL(subtract_slack_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, c->it_x.get() + n, rb);
+    } else {
+        EpiIterRb eb{{}, b, c->it_x.get() + n, rb};
+        launch_spmv(c->Arows, c->it_x.get(), eb, nullptr, nullptr, s);
+    }
+    EpiIterRc ec{{}, cc, c->it_zl.get(), c->it_zu.get(), c->it_state.get(), rc};
+    launch_spmv(c->Acols, c->it_y.get(), ec, nullptr, nullptr, s);
+    hipLaunchKernelGGL(iterate_bound_residuals_kernel, dim3(vec_grid(N)), dim3(kBlock), 0, s, n, m, c->it_state.get(),
+                       cc, lb, ub, c->it_x.get(), c->it_xl.get(), c->it_xu.get(), c->it_y.get(), c->it_zl.get(),
+                       c->it_zu.get(), rc, rl, ru);
+}
+
+// this rank's presidual, dresidual (max over its entries; rb is replicated)
+void residual_norms_local(Context* c, const double* rb, const double* rc, const double* rl, const double* ru, double out2[2]) {
+    const int m = (int)c->m, N = (int)(c->n + c->m);
+    const int g = vec_grid(N);
+    c->it_partials.resize((size_t)4 * 1024);
+    hipLaunchKernelGGL(iterate_norms_kernel, dim3(g), dim3(kBlock), 0, c->stream, N, m, rb, rc, rl, ru, c->it_partials.get());
+    std::vector<double> h((size_t)2 * g);
+    c->it_partials.download(h.data(), h.size(), c->stream);
+    IPXK_HIP(hipGetLastError());
+    double p = 0.0, d = 0.0;
+    for (int i = 0; i < g; i++) { p = std::max(p, h[i]); d = std::max(d, h[(size_t)g + i]); }
+    out2[0] = p; out2[1] = d;
+}
+
+// this rank's sum, min, max and count of the barrier products (slack terms if with_replicated)
+void complementarity_local(Context* c, double out4[4]) {
+    const int N = (int)(with_replicated(c) ? c->n + c->m : c->n);
+    const int g = vec_grid(N);
+    c->it_partials.resize((size_t)4 * 1024);
+    hipLaunchKernelGGL(iterate_complementarity_kernel, dim3(g), dim3(kBlock), 0, c->stream, N, c->it_state.get(),
+                       c->it_xl.get(), c->it_xu.get(), c->it_zl.get(), c->it_zu.get(), c->it_partials.get());
+    std::vector<double> h((size_t)4 * g);
+    c->it_partials.download(h.data(), h.size(), c->stream);
+    IPXK_HIP(hipGetLastError());
+    double sum = 0.0, mn = INFINITY, mx = 0.0, cnt = 0.0;
+    for (int i = 0; i < g; i++) {
+        sum += h[i]; mn = std::min(mn, h[(size_t)g + i]); mx = std::max(mx, h[(size_t)2 * g + i]); cnt += h[(size_t)3 * g + i];
+    }
+    out4[0] = sum; out4[1] = mn; out4[2] = mx; out4[3] = cnt;
+}
+
+// this rank's sums pobj, offset, dobj (b'y and the slack terms if with_replicated) and the fixed structural x_j A_j'y
+void objectives_local(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double out4[4]) {
+    // the kernel with m = 0 visits the structural slice only and leaves out b'y
+    const int n = (int)c->n, m = with_replicated(c) ? (int)c->m : 0, N = n + m;
     hipStream_t s = c->stream;
     const int g = vec_grid(N);
     c->it_partials.resize((size_t)4 * 1024);
@@ -213,7 +330,56 @@ void iterate_objectives_dev(Context* c, const double* b, const double* cc, const
     double pobj = 0.0, offset = 0.0, dobj = 0.0, fixed = 0.0;
     for (int i = 0; i < g; i++) { pobj += h[i]; offset += h[(size_t)g + i]; dobj += h[(size_t)2 * g + i]; }
     for (int i = 0; i < np; i++) fixed += hf[i];
-    out3[0] = pobj; out3[1] = dobj - fixed; out3[2] = offset;
+    out4[0] = pobj; out4[1] = offset; out4[2] = dobj; out4[3] = fixed;
+}
+
+}  // namespace
+
+void iterate_scalars_dev(Context* c, unsigned what, const double* b, const double* cc, const double* lb, const double* ub,
+                         double* rb, double* rc, double* rl, double* ru, IterScalars* out) {
+    IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
+    double row[10];
+    CombineOp ops[10];
+    int k = 0;
+    if (what & kIterResiduals) {
+        IPXK_REQUIRE(!comm_rows(c), kIterateRowRefusal);
+        residual_vectors(c, b, cc, lb, ub, rb, rc, rl, ru);
+        residual_norms_local(c, rb, rc, rl, ru, row + k);
+        ops[k++] = kCombineMax; ops[k++] = kCombineMax;
+    }
+    if (what & kIterComplementarity) {
+        complementarity_local(c, row + k);
+        ops[k++] = kCombineSum; ops[k++] = kCombineMin; ops[k++] = kCombineMax; ops[k++] = kCombineSum;
+    }
+    if (what & kIterObjectives) {
+        IPXK_REQUIRE(!comm_rows(c), kIterateRowRefusal);
+        objectives_local(c, b, cc, lb, ub, row + k);
+        for (int f = 0; f < 4; f++) ops[k++] = kCombineSum;
+    }
+    if (comm_cols(c)) combine_over_ranks(c, row, ops, k);
+    k = 0;
+    if (what & kIterResiduals) { out->presidual = row[k++]; out->dresidual = row[k++]; }
+    if (what & kIterComplementarity) {
+        double sum = row[k], mn = row[k + 1], mx = row[k + 2], cnt = row[k + 3];
+        k += 4;
+        // :666-669
+        double mu = 0.0;
+        if (cnt > 0) mu = sum / cnt; else mn = 0.0;
+        out->comp[0] = sum; out->comp[1] = mu; out->comp[2] = mn; out->comp[3] = mx;
+        out->num_terms = cnt;
+    }
+    if (what & kIterObjectives) {
+        const double pobj = row[k], offset = row[k + 1], dobj = row[k + 2], fixed = row[k + 3];
+        out->obj[0] = pobj; out->obj[1] = dobj - fixed; out->obj[2] = offset;
+    }
+}
+
+// out3 = pobjective, dobjective, offset
+void iterate_objectives_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
+                            double out3[3]) {
+    IterScalars S;
+    iterate_scalars_dev(c, kIterObjectives, b, cc, lb, ub, nullptr, nullptr, nullptr, nullptr, &S);
+    std::copy(S.obj, S.obj + 3, out3);
 }
 
 // out2 = norm_bounds, norm_c
@@ -227,6 +393,10 @@ void model_norms_dev(Context* c, const double* b, const double* cc, const double
     IPXK_HIP(hipGetLastError());
     out2[0] = out2[1] = 0.0;
     for (int i = 0; i < g; i++) { out2[0] = std::max(out2[0], h[i]); out2[1] = std::max(out2[1], h[(size_t)g + i]); }
+    if (comm_cols(c)) {
+        const CombineOp ops[2] = {kCombineMax, kCombineMax};
+        combine_over_ranks(c, out2, ops, 2);
+    }
 }
 
 void iterate_update_dev(Context* c, double sp, const double* dx, const double* dxl, const double* dxu, double sd,
@@ -241,50 +411,20 @@ void iterate_update_dev(Context* c, double sp, const double* dx, const double* d
 
 void iterate_residuals_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
                            double* rb, double* rc, double* rl, double* ru, double* presidual, double* dresidual) {
-    IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
-    IPXK_REQUIRE(!comm_active(c), "the device iterate is not available on a partitioned system");
-    const int n = (int)c->n, m = (int)c->m, N = n + m;
-    hipStream_t s = c->stream;
-    EpiIterRb eb{{}, b, c->it_x.get() + n, rb};
-    launch_spmv(c->Arows, c->it_x.get(), eb, nullptr, nullptr, s);
-    EpiIterRc ec{{}, cc, c->it_zl.get(), c->it_zu.get(), c->it_state.get(), rc};
-    launch_spmv(c->Acols, c->it_y.get(), ec, nullptr, nullptr, s);
-    hipLaunchKernelGGL(iterate_bound_residuals_kernel, dim3(vec_grid(N)), dim3(kBlock), 0, s, n, m, c->it_state.get(),
-                       cc, lb, ub, c->it_x.get(), c->it_xl.get(), c->it_xu.get(), c->it_y.get(), c->it_zl.get(),
-                       c->it_zu.get(), rc, rl, ru);
-    const int g = vec_grid(N);
-    c->it_partials.resize((size_t)4 * 1024);
-    hipLaunchKernelGGL(iterate_norms_kernel, dim3(g), dim3(kBlock), 0, s, N, m, rb, rc, rl, ru, c->it_partials.get());
-    std::vector<double> h((size_t)2 * g);
-    c->it_partials.download(h.data(), h.size(), s);
-    IPXK_HIP(hipGetLastError());
-    double p = 0.0, d = 0.0;
-    for (int i = 0; i < g; i++) { p = std::max(p, h[i]); d = std::max(d, h[(size_t)g + i]); }
-    if (presidual) *presidual = p;
-    if (dresidual) *dresidual = d;
+    IterScalars S;
+    iterate_scalars_dev(c, kIterResiduals, b, cc, lb, ub, rb, rc, rl, ru, &S);
+    if (presidual) *presidual = S.presidual;
+    if (dresidual) *dresidual = S.dresidual;
 }
 
 void iterate_complementarity_dev(Context* c, double out4[4], double* num_terms) {
-    IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
-    const int N = (int)(c->n + c->m);
-    const int g = vec_grid(N);
-    c->it_partials.resize((size_t)4 * 1024);
-    hipLaunchKernelGGL(iterate_complementarity_kernel, dim3(g), dim3(kBlock), 0, c->stream, N, c->it_state.get(),
-                       c->it_xl.get(), c->it_xu.get(), c->it_zl.get(), c->it_zu.get(), c->it_partials.get());
-    std::vector<double> h((size_t)4 * g);
-    c->it_partials.download(h.data(), h.size(), c->stream);
-    IPXK_HIP(hipGetLastError());
-    double sum = 0.0, mn = INFINITY, mx = 0.0, cnt = 0.0;
-    for (int i = 0; i < g; i++) {
-        sum += h[i]; mn = std::min(mn, h[(size_t)g + i]); mx = std::max(mx, h[(size_t)2 * g + i]); cnt += h[(size_t)3 * g + i];
-    }
-    // :666-669
-    double mu = 0.0;
-    if (cnt > 0) mu = sum / cnt; else mn = 0.0;
-    out4[0] = sum; out4[1] = mu; out4[2] = mn; out4[3] = mx;
-    if (num_terms) *num_terms = cnt;
+    IterScalars S;
+    iterate_scalars_dev(c, kIterComplementarity, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &S);
+    std::copy(S.comp, S.comp + 4, out4);
+    if (num_terms) *num_terms = S.num_terms;
 }
 
+// rank-local on every context: a generic vector primitive (the IPM step takes its partitioned form, ipm_step.hip)
 double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64_t len, double alpha0,
                             ipxint* blocking) {
     IPXK_REQUIRE(len >= 0 && len < (int64_t(1) << 31), "bad length");
@@ -301,6 +441,38 @@ double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64
         if (h[i] < alpha) { alpha = h[i]; blk = (ipxint)h[(size_t)g + i]; }   // blocks ascend: first index kept
     if (blocking) *blocking = blk;
     return alpha;
+}
+
+// column partition: the four problems over this rank's share (slack entries on rank 0 only), one all-gather of the
+// rows, and per problem the lexicographic minimum of (alpha, global index) over the ranks -- the reference's first-index
+// rule (ipm.cc:320-339) on the whole vector.  The winner's x, dx, z, dz come with it.
+void steps_to_boundary_part(Context* c, const BoundaryVectors& V, double alpha0, Boundary out[4]) {
+    learn_col_offsets(c);
+    const int n = (int)c->n;
+    const int len = with_replicated(c) ? (int)(c->n + c->m) : n;
+    const int g = vec_grid(len);
+    c->it_bnd.ensure((size_t)8 * g);
+    c->it_row.ensure(24);
+    const double* xs[4] = {V.xl, V.xu, V.zl, V.zu};
+    const double* ds[4] = {V.dxl, V.dxu, V.dzl, V.dzu};
+    for (int k = 0; k < 4; k++) {
+        double* part = c->it_bnd.get() + (size_t)2 * g * k;
+        hipLaunchKernelGGL(step_to_boundary_kernel, dim3(g), dim3(kBlock), 0, c->stream, len, xs[k], ds[k], alpha0, part,
+                           part + g);
+    }
+    hipLaunchKernelGGL(boundary_row_kernel, dim3(1), dim3(64), 0, c->stream, g, c->it_bnd.get(), alpha0, n,
+                       (double)c->col_offset, (double)c->n_global, V, c->it_row.get());
+    IPXK_HIP(hipGetLastError());
+    const std::vector<double> T = comm_gather_table(c, c->it_row.get(), 24);
+    for (int k = 0; k < 4; k++) {
+        Boundary b{alpha0, -1.0, 0.0, 0.0, 0.0, 0.0};
+        for (int r = 0; r < c->nranks; r++) {
+            const double* t = T.data() + (size_t)24 * r + 6 * k;
+            if (t[1] < 0.0) continue;
+            if (t[0] < b.alpha || (t[0] == b.alpha && (b.index < 0.0 || t[1] < b.index))) b = Boundary{t[0], t[1], t[2], t[3], t[4], t[5]};
+        }
+        out[k] = b;
+    }
 }
 
 }  // namespace ipxk

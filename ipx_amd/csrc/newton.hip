@@ -106,7 +106,10 @@ CrResult newton_solve_dev(Context* c, bool use_basis, const double* rb, const do
                           const double* zl, const double* zu, const unsigned char* state, double tol,
                           ipxint maxiter, double* dx, double* dxl, double* dxu, double* dy, double* dzl,
                           double* dzu, ipxk_interrupt_fn interrupt, void* user, ipxk_times* times) {
-    IPXK_REQUIRE(!comm_active(c), "ipxk_newton_solve is not available on a partitioned system");
+    // column partition: the right-hand side, the recovery and the A_j'dy shift are local per column, the slack shift reads the
+    // replicated dy, and both KKT solvers run partitioned
+    IPXK_REQUIRE(!comm_rows(c), "ipxk_newton_solve does not run on a row-partitioned system: partition the structural columns "
+                                "(ipxk_comm_init_columns)");
     const int n = (int)c->n, m = (int)c->m, N = n + m;
     hipStream_t s = c->stream;
     c->nw_rhs1.resize((size_t)std::max(N, 1));

@@ -1047,7 +1047,7 @@ void split_check_partition(const Context* c) {
 
 // this rank's first structural column and the structural columns of all ranks (slabs contiguous, in rank order):
 // one all-gather of n_local, once per communicator
-static void learn_col_offsets(Context* c) {
+void learn_col_offsets(Context* c) {
     if (c->col_offset >= 0) return;
     const int R = c->nranks;
     hipStream_t s = c->stream;
@@ -1068,36 +1068,9 @@ static void learn_col_offsets(Context* c) {
     c->n_global = total;
 }
 
-// fingerprint of the arguments every rank must hold identically
-struct Fingerprint {
-    uint64_t h = 0x9e3779b97f4a7c15ull;
-    void mix(uint64_t w) { h ^= w; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; }
-    template <class T> void add(const T* p, size_t count) {
-        const size_t len = count * sizeof(T);
-        const unsigned char* b = reinterpret_cast<const unsigned char*>(p);
-        size_t i = 0;
-        for (; i + 8 <= len; i += 8) { uint64_t w; memcpy(&w, b + i, 8); mix(w); }
-        if (i < len) { uint64_t w = 0; memcpy(&w, b + i, len - i); mix(w); }
-        mix((uint64_t)len);
-    }
-};
-
-// The ranks fail or proceed together, so that no rank enters a later collective alone: this rank's verdict and the
-// fingerprint go through one all-reduce (max of [failed, hi, lo, -hi, -lo]; max == -max(-.) iff all fingerprints agree).
+// the ranks agree on the verdict and on the replicated arguments of the basis path (comm.hip)
 static void agree_on_arguments(Context* c, const std::string& err, uint64_t h) {
-    const double hi = (double)(h >> 32), lo = (double)(h & 0xffffffffull);
-    double v[5] = {err.empty() ? 0.0 : 1.0, hi, lo, -hi, -lo};
-    DevBuf<double> d(5);
-    d.upload(v, 5, c->stream);
-    comm_allreduce_max(c, d.get(), 5);
-    d.download(v, 5, c->stream);
-    IPXK_HIP(hipStreamSynchronize(c->stream));
-    comm_check(c);
-    if (!err.empty()) throw Error(IPXK_E_ARGUMENT, err);
-    if (v[0] != 0.0) throw Error(IPXK_E_ARGUMENT, "another rank refused its arguments of the basis path");
-    if (v[1] != -v[3] || v[2] != -v[4])
-        throw Error(IPXK_E_ARGUMENT, "the replicated arguments of the basis path (factors, permutations, basis, slack parts of "
-                                     "status and colscale) differ between the ranks");
+    agree_on_arguments(c, err, h, "the basis path", "factors, permutations, basis, slack parts of status and colscale");
 }
 
 // local status entries in range (the scaling kernel's check, made before the ranks agree)

@@ -459,6 +459,8 @@ class KktContext:
     IT_KEYS = ("x", "xl", "xu", "y", "zl", "zu")
 
     def iterate_set(self, it, state):
+        """Column partition: it and state in partition.col_slice_iterate's form (y replicated); collective, and every
+        rank raises KktError(IPXK_E_ARGUMENT) if the replicated parts differ between the ranks."""
         st = np.ascontiguousarray(state, dtype=np.uint8)
         vecs = [_F(it[key]) for key in self.IT_KEYS]
         self._check(self.lib.ipxk_iterate_set(self.h, *[_fp(v) for v in vecs],
@@ -524,7 +526,8 @@ class KktContext:
 
     def ipm_driver(self, b, c, lb, ub, kkt_tol=0.3, feasibility_tol=1e-6, optimality_tol=1e-8, kkt_maxiter=-1,
                    ipm_maxiter=300, precond_dense_cols=True, interrupt=None):
-        """IPM::Driver on the resident iterate with the diag solver (host model vectors)."""
+        """IPM::Driver on the resident iterate with the diag solver (host model vectors).  Column partition: b replicated,
+        c, lb, ub local (partition.col_slice_model); collective, every rank returns the same info."""
         prm = IpmParams(kkt_tol, feasibility_tol, optimality_tol, kkt_maxiter, ipm_maxiter, 1 if precond_dense_cols else 0)
         info = IpmInfo()
         cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
@@ -702,7 +705,10 @@ class KktContext:
 
         With columns=True the basis path (split_prepare, split_rescale, split_apply, the triangular solves,
         cr_solve, kkt_basis_solve) runs too, with the slabs of partition.col_slab (contiguous, in rank order) and
-        the global basis numbering; the device LU and Maxvolume do not.  With rows the basis path is refused."""
+        the global basis numbering; the device LU and Maxvolume do not.  So does the device IPM (iterate_set, the
+        iterate's residuals, complementarity and objectives, newton_solve, ipm_step, ipm_driver; not
+        ipm_driver_basis), with partition.col_slice_iterate / col_slice_model / assemble_iterate for its vectors.
+        With rows the basis path and the device IPM are refused."""
         buf = (C.c_char * 128).from_buffer_copy(unique_id)
         fn = self.lib.ipxk_comm_init_columns if columns else self.lib.ipxk_comm_init
         self._check(fn(self.h, buf, C.c_int(rank), C.c_int(nranks)))

@@ -105,6 +105,31 @@ def assemble_cols(m, parts_x):
     return np.concatenate([p[:len(p) - m] for p in parts_x] + [parts_x[0][len(parts_x[0]) - m:]])
 
 
+ITERATE_VECTORS = ("x", "xl", "xu", "zl", "zu")       # (n+m)-vectors of an IPM iterate; y is an m-vector
+
+
+def col_slice_iterate(it, state, n, rank, world):
+    """This rank's share of an IPM iterate under col_slab's ranges: the (n+m)-vectors and state in col_local_vector
+    form, y replicated.  Returns (iterate dict, state)."""
+    c0, c1 = row_range(n, rank, world)
+    loc = {k: col_local_vector(it[k], n, c0, c1) for k in ITERATE_VECTORS}
+    loc["y"] = it["y"]
+    return loc, col_local_vector(state, n, c0, c1)
+
+
+def col_slice_model(b, c, lb, ub, n, rank, world):
+    """This rank's share of the model vectors of the IPM: b replicated, c, lb, ub ((n+m)-vectors) sliced."""
+    c0, c1 = row_range(n, rank, world)
+    return (b,) + tuple(col_local_vector(v, n, c0, c1) for v in (c, lb, ub))
+
+
+def assemble_iterate(m, parts):
+    """The whole iterate from the ranks' iterates (rank order); y from rank 0 (it is replicated)."""
+    out = {k: assemble_cols(m, [p[k] for p in parts]) for k in ITERATE_VECTORS}
+    out["y"] = parts[0]["y"]
+    return out
+
+
 def assemble(n, parts_x, parts_y):
     """Inverse of the partition for results: x = [x_s ; x_I slices], y = concatenated slices.
     parts_x[g] has length n + m_g (structural part identical on every rank)."""
