@@ -157,8 +157,8 @@ struct Context {
     // true: structural COLUMNS partitioned (m global, n local; every m-vector and every scalar of
     // the CR loop is replicated, the only exchange is the sum of the partial products A_g t_g)
     bool col_partition = false;
-    // column partition, basis path: this rank's first structural column and the structural columns of all ranks
-    // (one all-gather at the first split Prepare after comm_init; -1: not known yet)
+    // column partition: this rank's first structural column and the structural columns of all ranks (learn_col_offsets;
+    // -1: not known yet)
     int64_t col_offset = -1, n_global = 0;
     DevBuf<double> comm_scalars;        // scratch scalars (single-value reductions)
     DevBuf<double> comm_send;           // kNumPartialSlots scalars of this rank
@@ -268,10 +268,16 @@ struct IterScalars {
 };
 void iterate_scalars_dev(Context* c, unsigned what, const double* b, const double* cc, const double* lb, const double* ub,
                          double* rb, double* rc, double* rl, double* ru, IterScalars* out);
-// column partition: the step-to-boundary problems of xl, xu, zl, zu over all ranks (iterate.hip)
+// the step-to-boundary problems of xl, xu, zl, zu over all ranks of a column partition (iterate.hip)
 struct BoundaryVectors { const double *xl, *dxl, *zl, *dzl, *xu, *dxu, *zu, *dzu; };
 struct Boundary { double alpha, index, x, dx, z, dz; };   // index: global, -1 if nothing blocks
-void steps_to_boundary_part(Context* c, const BoundaryVectors& V, double alpha0, Boundary out[4]);
+void steps_to_boundary(Context* c, const BoundaryVectors& V, double alpha0, Boundary out[4]);
+// column partition: row[k] (this rank's values) <- their combination over the ranks, one all-gather (iterate.hip); no-op
+// on any other context
+enum CombineOp { kCombineSum, kCombineMax, kCombineMin };
+void combine_over_ranks(Context* c, double* row, const CombineOp* ops, int k);
+// whether this rank's (n+m)-vectors include the replicated slack entries in its reductions (rank 0 of a column partition)
+bool with_replicated(const Context* c);
 void iterate_objectives_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double out3[3]);
 void model_norms_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double out2[2]);
 double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64_t len, double alpha0,
@@ -388,7 +394,7 @@ struct Fingerprint {
 // fingerprints differ; `who` names the call, `what` the replicated arguments.
 void agree_on_arguments(Context* c, const std::string& err, uint64_t h, const char* who, const char* what);
 // column partition: this rank's first structural column and the structural columns of all ranks (Context::col_offset,
-// n_global), one all-gather at the first call that needs them (trisolve.hip)
+// n_global), one all-gather at the first call that needs them (trisolve.hip); 0 and n on any other context
 void learn_col_offsets(Context* c);
 
 }  // namespace ipxk

@@ -37,12 +37,6 @@ struct CrVecs {
     const double* diag;
 };
 
-static int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
-}
-
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------

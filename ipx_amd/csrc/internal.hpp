@@ -142,6 +142,13 @@ constexpr int kMaxWorkgroups = 1024; // 4 per CU: all co-resident (16 waves/CU)
 constexpr int kMaxPartials = 2048; // upper bound on grid size of reducing kernels
 constexpr int kMaxRT = 8;          // rows per thread per round
 
+// grid of a grid-stride elementwise kernel over len entries: one workgroup per kBlock entries, at most 1024
+inline int vec_grid(int64_t len) {
+    int64_t g = (len + kBlock - 1) / kBlock;
+    if (g < 1) g = 1;
+    return (int)(g < 1024 ? g : 1024);
+}
+
 struct GatherView {                // passed to kernels by value
     int nrows, ncols;
     int P, G, RT, Q;               // phases, workgroups, rows/thread, rounds

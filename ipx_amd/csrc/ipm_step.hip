@@ -12,12 +12,6 @@ namespace ipxk {
 
 namespace {
 
-int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
-}
-
 __device__ __forceinline__ bool has_lb(unsigned char st) { return st == IPXK_STATE_BARRIER_LB || st == IPXK_STATE_BARRIER_BOXED; }
 __device__ __forceinline__ bool has_ub(unsigned char st) { return st == IPXK_STATE_BARRIER_UB || st == IPXK_STATE_BARRIER_BOXED; }
 
@@ -63,8 +57,7 @@ __global__ __launch_bounds__(kBlock) void trial_complementarity_kernel(int N, co
 // column partition: each rank sums its share (slack terms on rank 0 only), the ranks' sums are added in rank order
 double trial_complementarity(Context* c, const double* dxl, const double* dxu, const double* dzl, const double* dzu,
                              double ap, double ad) {
-    const bool part = comm_cols(c);
-    const int N = (int)(part && c->rank != 0 ? c->n : c->n + c->m);
+    const int N = (int)(with_replicated(c) ? c->n + c->m : c->n);
     const int g = vec_grid(N);
     c->it_partials.resize((size_t)4 * 1024);
     hipLaunchKernelGGL(trial_complementarity_kernel, dim3(g), dim3(kBlock), 0, c->stream, N, c->it_state.get(),
@@ -74,31 +67,20 @@ double trial_complementarity(Context* c, const double* dxl, const double* dxu, c
     c->it_partials.download(h.data(), h.size(), c->stream);
     double s = 0.0;
     for (double v : h) s += v;
-    if (part) {
-        c->it_row.upload(&s, 1, c->stream);
-        const std::vector<double> T = comm_gather_table(c, c->it_row.get(), 1);
-        s = T[0];
-        for (int r = 1; r < c->nranks; r++) s += T[(size_t)r];
-    }
+    const CombineOp op = kCombineSum;
+    combine_over_ranks(c, &s, &op, 1);
     return s;
-}
-
-double element(Context* c, const double* dev, ipxint j) {
-    double v = 0.0;
-    staged_d2h(&v, dev + j, sizeof(double), c->stream);
-    return v;
 }
 
 }  // namespace
 
 // Column partition (comm_cols): the Newton solves are partitioned already; every scalar below is replicated (the
 // reductions of iterate.hip and the step-to-boundary problems over all ranks, whose winners carry the four values
-// StepSizes reads), so every rank takes the same step.
+// StepSizes reads), so every rank takes the same step.  Without a communicator the same code is one rank's.
 void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc, const double* lb, const double* ub,
                   double kkt_tol, ipxint maxiter, ipxk_ipm_step_info* info, ipxk_interrupt_fn interrupt, void* user,
                   const IterScalars* pre, double* comp_after) {
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
-    const bool part = comm_cols(c);
     const int n = (int)c->n, m = (int)c->m, N = n + m;
     hipStream_t s = c->stream;
     *info = ipxk_ipm_step_info{};
@@ -134,19 +116,9 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
 
     // ---- AddCorrector, :373-435
     const BoundaryVectors V{xl, dxl, zl, dzl, xu, dxu, zu, dzu};
-    Boundary bd[4];
-    ipxint blk;
-    double step_xl, step_xu, step_zl, step_zu;
-    if (part) {
-        steps_to_boundary_part(c, V, 1.0, bd);
-        step_xl = bd[0].alpha; step_xu = bd[1].alpha; step_zl = bd[2].alpha; step_zu = bd[3].alpha;
-    } else {
-        step_xl = step_to_boundary_dev(c, xl, dxl, N, 1.0, &blk);
-        step_xu = step_to_boundary_dev(c, xu, dxu, N, 1.0, &blk);
-        step_zl = step_to_boundary_dev(c, zl, dzl, N, 1.0, &blk);
-        step_zu = step_to_boundary_dev(c, zu, dzu, N, 1.0, &blk);
-    }
-    double maxp = std::min(step_xl, step_xu), maxd = std::min(step_zl, step_zu);
+    Boundary bd[4];         // xl, xu, zl, zu
+    steps_to_boundary(c, V, 1.0, bd);
+    double maxp = std::min(bd[0].alpha, bd[1].alpha), maxd = std::min(bd[2].alpha, bd[3].alpha);
     IPXK_REQUIRE(num_finite > 0.0, "the iterate has no barrier term");
     const double muaff = trial_complementarity(c, dxl, dxu, dzl, dzu, maxp, maxd) / num_finite;
     const double ratio = muaff / mu;
@@ -162,50 +134,23 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
 
     // ---- StepSizes, :437-516
     const double gammaf = 0.9, gammaa = 1.0 / (1.0 - gammaf);
-    ipxint block_xl = -1, block_xu = -1, block_zl = -1, block_zu = -1;
-    if (part) {
-        steps_to_boundary_part(c, V, 1.0, bd);
-        step_xl = bd[0].alpha; step_xu = bd[1].alpha; step_zl = bd[2].alpha; step_zu = bd[3].alpha;
-    } else {
-        step_xl = step_to_boundary_dev(c, xl, dxl, N, 1.0, &block_xl);
-        step_xu = step_to_boundary_dev(c, xu, dxu, N, 1.0, &block_xu);
-        step_zl = step_to_boundary_dev(c, zl, dzl, N, 1.0, &block_zl);
-        step_zu = step_to_boundary_dev(c, zu, dzu, N, 1.0, &block_zu);
-    }
-    maxp = std::fmin(step_xl, step_xu);
-    maxd = std::fmin(step_zl, step_zu);
+    steps_to_boundary(c, V, 1.0, bd);
+    maxp = std::fmin(bd[0].alpha, bd[1].alpha);
+    maxd = std::fmin(bd[2].alpha, bd[3].alpha);
     double mufull = trial_complementarity(c, dxl, dxu, dzl, dzu, maxp, maxd) / num_finite;
     mufull /= gammaa;
     double alphap = 1.0, alphad = 1.0;
     if (maxp < 1.0) {
-        const bool lower = step_xl <= step_xu;
-        double z, dz, x, d;
-        if (part) {             // the values at the winner came with it
-            const Boundary& w = bd[lower ? 0 : 1];
-            x = w.x; d = w.dx; z = w.z; dz = w.dz;
-        } else {
-            const ipxint bp = lower ? block_xl : block_xu;
-            z = element(c, lower ? zl : zu, bp); dz = element(c, lower ? dzl : dzu, bp);
-            x = element(c, lower ? xl : xu, bp); d = element(c, lower ? dxl : dxu, bp);
-        }
-        const double buffer = mufull / (z + maxd * dz);
-        alphap = (x - buffer) / (-d);
+        const Boundary& w = bd[bd[0].alpha <= bd[1].alpha ? 0 : 1];     // the values at the winner came with it
+        const double buffer = mufull / (w.z + maxd * w.dz);
+        alphap = (w.x - buffer) / (-w.dx);
         alphap = std::max(alphap, gammaf * maxp);
         alphap = std::min(alphap, 1.0);
     }
     if (maxd < 1.0) {
-        const bool lower = step_zl <= step_zu;
-        double x, d, z, dz;
-        if (part) {
-            const Boundary& w = bd[lower ? 2 : 3];
-            x = w.x; d = w.dx; z = w.z; dz = w.dz;
-        } else {
-            const ipxint bdi = lower ? block_zl : block_zu;
-            x = element(c, lower ? xl : xu, bdi); d = element(c, lower ? dxl : dxu, bdi);
-            z = element(c, lower ? zl : zu, bdi); dz = element(c, lower ? dzl : dzu, bdi);
-        }
-        const double buffer = mufull / (x + maxp * d);
-        alphad = (z - buffer) / (-dz);
+        const Boundary& w = bd[bd[2].alpha <= bd[3].alpha ? 2 : 3];
+        const double buffer = mufull / (w.x + maxp * w.dx);
+        alphad = (w.z - buffer) / (-w.dz);
         alphad = std::max(alphad, gammaf * maxd);
         alphad = std::min(alphad, 1.0);
     }
@@ -303,8 +248,9 @@ static void driver_agree(Context* c, const double* b, const double* cc, const do
     agree_on_arguments(c, err, fp, "ipxk_ipm_driver", "b and the slack parts of c, lb and ub");
 }
 
-// max over the ranks of this rank's interrupt value
+// max over the ranks of this rank's interrupt value (column partition)
 static ipxint agree_interrupt(Context* c, ipxint mine) {
+    if (!comm_cols(c)) return mine;
     double v = (double)mine;
     c->it_row.upload(&v, 1, c->stream);
     comm_allreduce_max(c, c->it_row.get(), 1);
@@ -319,8 +265,7 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
                     ipxint* basis_out, ipxint* status_out) {
     IPXK_REQUIRE(!comm_rows(c), kDriverRowRefusal);
     IPXK_REQUIRE(!(use_basis && comm_active(c)), kDeviceLuRefusal);
-    const bool part = comm_cols(c);
-    if (part) driver_agree(c, b, cc, lb, ub);
+    if (comm_cols(c)) driver_agree(c, b, cc, lb, ub);
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
     std::vector<ipxint> basis, status;
     std::vector<double> colscale;
@@ -360,11 +305,7 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
             break;
         }
         if (info->iter >= prm->ipm_maxiter) { info->status_ipm = 6; break; }       // iter_limit
-        if (part) {
-            if ((errflag = agree_interrupt(c, interrupt ? interrupt(user) : 0)) != 0) break;
-        } else if (interrupt && (errflag = interrupt(user)) != 0) {
-            break;
-        }
+        if ((errflag = agree_interrupt(c, interrupt ? interrupt(user) : 0)) != 0) break;
         if (use_basis) {
             basis_factorize_dev(c, basis, status, colscale, first_factorize, info);
             first_factorize = false;

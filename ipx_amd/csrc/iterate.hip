@@ -15,12 +15,6 @@ namespace {
 
 constexpr double kBarrierMin = 1e-30;   // Iterate::kBarrierMin, src/iterate.h:204
 
-int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
-}
-
 __device__ __forceinline__ bool has_lb(unsigned char st) { return st == IPXK_STATE_BARRIER_LB || st == IPXK_STATE_BARRIER_BOXED; }
 __device__ __forceinline__ bool has_ub(unsigned char st) { return st == IPXK_STATE_BARRIER_UB || st == IPXK_STATE_BARRIER_BOXED; }
 
@@ -202,18 +196,27 @@ __global__ void subtract_slack_kernel(int m, const double* __restrict__ xI, doub
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) rb[i] = rb[i] - xI[i];
 }
 
-// column partition: the four step-to-boundary problems of a step (xl, xu, zl, zu), problem k's block partials at
-// part + 2 g k (alpha, then index).  Lane k reduces them in block order, as step_to_boundary_dev does, and writes
-// row[6k..6k+5] = alpha, GLOBAL blocking index (structural c0 + j, slack n_global + i; -1: none), and the x, dx, z, dz
-// at the candidate that StepSizes reads (the l pair for problems 0 and 2, the u pair for 1 and 3).
-__global__ void boundary_row_kernel(int g, const double* __restrict__ part, double alpha0, int n, double c0, double n_global,
-                                    BoundaryVectors V, double* __restrict__ row) {
-    const int k = threadIdx.x;
-    if (k >= 4) return;
+// the four step-to-boundary problems of a step (xl, xu, zl, zu), problem k's block partials at part + 2 g k (alpha,
+// then index).  Wave k reduces them to the first block that holds the smallest alpha below alpha0 -- the block-order
+// scan of step_to_boundary_dev -- and writes row[6k..6k+5] = alpha, GLOBAL blocking index (structural c0 + j, slack
+// n_global + i; -1: none), and the x, dx, z, dz at the candidate that StepSizes reads (the l pair for problems 0 and 2,
+// the u pair for 1 and 3).
+__global__ __launch_bounds__(256) void boundary_row_kernel(int g, const double* __restrict__ part, double alpha0, int n,
+                                                           double c0, double n_global, BoundaryVectors V,
+                                                           double* __restrict__ row) {
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const double* a = part + (size_t)2 * g * k;
-    double alpha = alpha0, idx = -1.0;
-    for (int i = 0; i < g; i++)
-        if (a[i] < alpha) { alpha = a[i]; idx = a[g + i]; }
+    double alpha = alpha0;
+    int blk = g;                            // g: none; i ascends per lane, so its first block is kept
+    for (int i = lane; i < g; i += 64)
+        if (a[i] < alpha) { alpha = a[i]; blk = i; }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double oa = __shfl_xor(alpha, off);
+        const int ob = __shfl_xor(blk, off);
+        if (oa < alpha || (oa == alpha && ob < blk)) { alpha = oa; blk = ob; }
+    }
+    if (lane != 0) return;
+    const double idx = blk < g ? a[g + blk] : -1.0;
     double* r = row + 6 * k;
     r[0] = alpha;
     if (idx >= 0.0) {
@@ -235,26 +238,8 @@ __global__ void boundary_row_kernel(int g, const double* __restrict__ part, doub
 // combines the table in rank order (sums) or in any order (max, min: exact).  The replicated slack entries and b'y enter
 // on rank 0 only, so one rank reproduces the unpartitioned context bit for bit.  Vectors of length n+m are
 // [own structural slice; all m slack entries]; rb is the one m-vector that needs an all-reduce.
-bool with_replicated(const Context* c) { return !comm_cols(c) || c->rank == 0; }
-
 const char* const kIterateRowRefusal =
     "the device IPM does not run on a row-partitioned system: partition the structural columns (ipxk_comm_init_columns)";
-
-enum CombineOp { kCombineSum, kCombineMax, kCombineMin };
-
-// row[k] (this rank's values) <- the combination over the ranks; one all-gather
-void combine_over_ranks(Context* c, double* row, const CombineOp* ops, int k) {
-    c->it_row.upload(row, (size_t)k, c->stream);
-    const std::vector<double> T = comm_gather_table(c, c->it_row.get(), (size_t)k);
-    for (int f = 0; f < k; f++) {
-        double v = T[(size_t)f];
-        for (int r = 1; r < c->nranks; r++) {
-            const double w = T[(size_t)r * k + f];
-            v = ops[f] == kCombineSum ? v + w : ops[f] == kCombineMax ? std::max(v, w) : std::min(v, w);
-        }
-        row[f] = v;
-    }
-}
 
 // rb, rc, rl, ru of the resident iterate
 void residual_vectors(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double* rb,
@@ -335,6 +320,22 @@ void objectives_local(Context* c, const double* b, const double* cc, const doubl
 
 }  // namespace
 
+bool with_replicated(const Context* c) { return !comm_cols(c) || c->rank == 0; }
+
+void combine_over_ranks(Context* c, double* row, const CombineOp* ops, int k) {
+    if (!comm_cols(c)) return;
+    c->it_row.upload(row, (size_t)k, c->stream);
+    const std::vector<double> T = comm_gather_table(c, c->it_row.get(), (size_t)k);
+    for (int f = 0; f < k; f++) {
+        double v = T[(size_t)f];
+        for (int r = 1; r < c->nranks; r++) {
+            const double w = T[(size_t)r * k + f];
+            v = ops[f] == kCombineSum ? v + w : ops[f] == kCombineMax ? std::max(v, w) : std::min(v, w);
+        }
+        row[f] = v;
+    }
+}
+
 void iterate_scalars_dev(Context* c, unsigned what, const double* b, const double* cc, const double* lb, const double* ub,
                          double* rb, double* rc, double* rl, double* ru, IterScalars* out) {
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
@@ -356,7 +357,7 @@ void iterate_scalars_dev(Context* c, unsigned what, const double* b, const doubl
         objectives_local(c, b, cc, lb, ub, row + k);
         for (int f = 0; f < 4; f++) ops[k++] = kCombineSum;
     }
-    if (comm_cols(c)) combine_over_ranks(c, row, ops, k);
+    combine_over_ranks(c, row, ops, k);
     k = 0;
     if (what & kIterResiduals) { out->presidual = row[k++]; out->dresidual = row[k++]; }
     if (what & kIterComplementarity) {
@@ -393,10 +394,8 @@ void model_norms_dev(Context* c, const double* b, const double* cc, const double
     IPXK_HIP(hipGetLastError());
     out2[0] = out2[1] = 0.0;
     for (int i = 0; i < g; i++) { out2[0] = std::max(out2[0], h[i]); out2[1] = std::max(out2[1], h[(size_t)g + i]); }
-    if (comm_cols(c)) {
-        const CombineOp ops[2] = {kCombineMax, kCombineMax};
-        combine_over_ranks(c, out2, ops, 2);
-    }
+    const CombineOp ops[2] = {kCombineMax, kCombineMax};
+    combine_over_ranks(c, out2, ops, 2);
 }
 
 void iterate_update_dev(Context* c, double sp, const double* dx, const double* dxl, const double* dxu, double sd,
@@ -424,7 +423,7 @@ void iterate_complementarity_dev(Context* c, double out4[4], double* num_terms) 
     if (num_terms) *num_terms = S.num_terms;
 }
 
-// rank-local on every context: a generic vector primitive (the IPM step takes its partitioned form, ipm_step.hip)
+// rank-local on every context: a generic vector primitive (the IPM step takes steps_to_boundary below)
 double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64_t len, double alpha0,
                             ipxint* blocking) {
     IPXK_REQUIRE(len >= 0 && len < (int64_t(1) << 31), "bad length");
@@ -443,10 +442,10 @@ double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64
     return alpha;
 }
 
-// column partition: the four problems over this rank's share (slack entries on rank 0 only), one all-gather of the
-// rows, and per problem the lexicographic minimum of (alpha, global index) over the ranks -- the reference's first-index
-// rule (ipm.cc:320-339) on the whole vector.  The winner's x, dx, z, dz come with it.
-void steps_to_boundary_part(Context* c, const BoundaryVectors& V, double alpha0, Boundary out[4]) {
+// the four problems over this rank's share (slack entries on rank 0 only), one all-gather of the rows (a download
+// without a communicator), and per problem the lexicographic minimum of (alpha, global index) over the ranks -- the
+// reference's first-index rule (ipm.cc:320-339) on the whole vector.  The winner's x, dx, z, dz come with it.
+void steps_to_boundary(Context* c, const BoundaryVectors& V, double alpha0, Boundary out[4]) {
     learn_col_offsets(c);
     const int n = (int)c->n;
     const int len = with_replicated(c) ? (int)(c->n + c->m) : n;
@@ -460,7 +459,7 @@ void steps_to_boundary_part(Context* c, const BoundaryVectors& V, double alpha0,
         hipLaunchKernelGGL(step_to_boundary_kernel, dim3(g), dim3(kBlock), 0, c->stream, len, xs[k], ds[k], alpha0, part,
                            part + g);
     }
-    hipLaunchKernelGGL(boundary_row_kernel, dim3(1), dim3(64), 0, c->stream, g, c->it_bnd.get(), alpha0, n,
+    hipLaunchKernelGGL(boundary_row_kernel, dim3(1), dim3(256), 0, c->stream, g, c->it_bnd.get(), alpha0, n,
                        (double)c->col_offset, (double)c->n_global, V, c->it_row.get());
     IPXK_HIP(hipGetLastError());
     const std::vector<double> T = comm_gather_table(c, c->it_row.get(), 24);

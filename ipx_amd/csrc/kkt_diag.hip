@@ -11,12 +11,6 @@
 
 namespace ipxk {
 
-static int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
-}
-
 // :34-43  W = 1/g (inf where g == 0); partial min over nonzero g
 __global__ __launch_bounds__(kBlock) void kkt_weights_kernel(int N, const double* __restrict__ xl,
                                                              const double* __restrict__ xu,

@@ -13,12 +13,6 @@ namespace ipxk {
 
 namespace {
 
-int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
-}
-
 __device__ __forceinline__ bool has_lb(unsigned char st) { return st == IPXK_STATE_BARRIER_LB || st == IPXK_STATE_BARRIER_BOXED; }
 __device__ __forceinline__ bool has_ub(unsigned char st) { return st == IPXK_STATE_BARRIER_UB || st == IPXK_STATE_BARRIER_BOXED; }
 __device__ __forceinline__ bool is_barrier(unsigned char st) { return st >= IPXK_STATE_BARRIER_LB; }

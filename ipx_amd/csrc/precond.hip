@@ -345,12 +345,6 @@ __global__ __launch_bounds__(1024) void potrs_blocked_kernel(int k, const double
     for (int i = tid; i < k; i += blockDim.x) b[i] = x[i];
 }
 
-static int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
-}
-
 // ---------------------------------------------------------------------------
 // Factorize
 // ---------------------------------------------------------------------------

@@ -43,12 +43,6 @@ void destroy_split(SplitOperator* s) { delete s; }
 
 static void bump_between(Context* c, bool trans, double* y, const int* done);   // dense bump of an LU from the device (below)
 
-static int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
-}
-
 // ---------------------------------------------------------------------------
 // sweep kernel
 // ---------------------------------------------------------------------------
@@ -1018,24 +1012,12 @@ __global__ void scaling_columns_kernel(int64_t N, const ipxint* __restrict__ sta
         W[j] = st == IPXK_NONBASIC ? colscale[j] * colscale[j] : 0.0;
     }
 }
-// column scaling of U in pivot order (:30-39; nothing for BASIC_FREE) and the free positions (:58-64)
-__global__ void scaling_pivots_kernel(int m, const int* __restrict__ colperm, const int* __restrict__ basis,
-                                      const int* __restrict__ status32, const double* __restrict__ colscale,
-                                      double* __restrict__ uscale, unsigned char* __restrict__ fmask, int* num_free) {
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < m; k += gridDim.x * blockDim.x) {
-        const int j = basis[colperm[k]];
-        const int st = status32[j];
-        uscale[k] = st == IPXK_BASIC ? colscale[j] : 1.0;
-        fmask[k] = st == IPXK_BASIC_FREE ? 1 : 0;
-        if (st == IPXK_BASIC_FREE) atomicAdd(num_free, 1);
-    }
-}
-
-// ---- column-partitioned contexts (comm_cols) ----
-// L, U, the permutations and basis[] (global column numbers) are replicated; status, colscale, a and x are local
-// ([this rank's structural slice; all m slack entries]).  What a kernel indexed by basis position needs of a column
-// that another rank owns is formed by one all-reduce of the owners' contributions (every other rank adds 0, so the
-// sum is exact); slack positions are filled in locally afterwards, identically on every rank.
+// ---- kernels by basis position ----
+// On a column-partitioned context (comm_cols) L, U, the permutations and basis[] (global column numbers) are replicated;
+// status, colscale, a and x are local ([this rank's structural slice; all m slack entries]).  What a kernel indexed by
+// basis position needs of a column is formed through loc (SplitOperator::loc_map) by one all-reduce of the owners'
+// contributions (every other rank adds 0, so the sum is exact); slack positions are filled in locally afterwards,
+// identically on every rank.  Unpartitioned, the all-reduce is no exchange at all and the same kernels read basis[].
 static const char* const kRowPartitionRefusal =
     "the basis path does not run on a row-partitioned system: partition the structural columns (ipxk_comm_init_columns)";
 
@@ -1046,9 +1028,14 @@ void split_check_partition(const Context* c) {
 }
 
 // this rank's first structural column and the structural columns of all ranks (slabs contiguous, in rank order):
-// one all-gather of n_local, once per communicator
+// one all-gather of n_local, once per communicator (comm_destroy forgets them); 0 and n without one
 void learn_col_offsets(Context* c) {
     if (c->col_offset >= 0) return;
+    if (!comm_cols(c)) {
+        c->col_offset = 0;
+        c->n_global = c->n;
+        return;
+    }
     const int R = c->nranks;
     hipStream_t s = c->stream;
     DevBuf<double> mine(1), all((size_t)R);
@@ -1102,7 +1089,17 @@ __global__ void pos_slack_kernel(int m, int n, const int* __restrict__ loc, cons
         if (l >= n) out[p] = v[l];
     }
 }
-// pos_status / pos_scale from the summed contributions (status in sum[0..m), colscale in sum[m..2m)) and the slack part
+// the owner's contributions to pos_status (sum[0..m)) and pos_scale (sum[m..2m))
+__global__ void pos_scaling_contrib_kernel(int m, int n, const int* __restrict__ loc, const int* __restrict__ status32,
+                                           const double* __restrict__ colscale, double* __restrict__ sum) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
+        const int l = loc[p];
+        const bool mine = l >= 0 && l < n;
+        sum[p] = mine ? (double)status32[l] : 0.0;
+        sum[m + p] = mine ? colscale[l] : 0.0;
+    }
+}
+// pos_status / pos_scale from the summed contributions and the slack part
 __global__ void pos_scaling_kernel(int m, int n, const int* __restrict__ loc, const double* __restrict__ sum,
                                    const int* __restrict__ status32, const double* __restrict__ colscale,
                                    int* __restrict__ pos_status, double* __restrict__ pos_scale) {
@@ -1112,7 +1109,7 @@ __global__ void pos_scaling_kernel(int m, int n, const int* __restrict__ loc, co
         pos_scale[p] = l >= n ? colscale[l] : sum[m + p];
     }
 }
-// scaling_pivots_kernel by basis position
+// column scaling of U in pivot order (:30-39; nothing for BASIC_FREE) and the free positions (:58-64)
 __global__ void scaling_pivots_pos_kernel(int m, const int* __restrict__ colperm, const int* __restrict__ pos_status,
                                           const double* __restrict__ pos_scale, double* __restrict__ uscale,
                                           unsigned char* __restrict__ fmask, int* num_free) {
@@ -1125,22 +1122,19 @@ __global__ void scaling_pivots_pos_kernel(int m, const int* __restrict__ colperm
     }
 }
 
-// status and scale of every basis position: one all-reduce of 2m, then the slack positions locally
-static void scaling_positions(Context* c, SplitOperator* S, const ipxint* status, const double* colscale) {
+// status and scale of every basis position (from S->status, S->colscale): one all-reduce of 2m, then the slack
+// positions locally; then the scaling of U and the free positions
+static void scaling_positions(Context* c, SplitOperator* S) {
     const int m = S->m, n = (int)c->n;
     hipStream_t s = c->stream;
     const size_t mm = (size_t)std::max(m, 1);
-    std::vector<double> h(2 * (size_t)m, 0.0);
-    for (int p = 0; p < m; p++) {
-        const int l = S->h_loc[(size_t)p];
-        if (l >= 0 && l < n) { h[(size_t)p] = (double)status[l]; h[(size_t)m + p] = colscale[l]; }
-    }
-    S->pos_sum.ensure(2 * mm);
-    S->pos_sum.upload(h, s);
-    comm_allreduce_sum(c, S->pos_sum.get(), 2 * (size_t)m);
-    S->pos_status.ensure(mm); S->pos_scale.ensure(mm);
+    S->pos_sum.ensure(2 * mm); S->pos_status.ensure(mm); S->pos_scale.ensure(mm);
     if (m > 0) {
-        hipLaunchKernelGGL(pos_scaling_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, n, S->loc.get(), S->pos_sum.get(),
+        allreduce_product(c, S->pos_sum.get(), 2 * (size_t)m, [&](double* out) {
+            hipLaunchKernelGGL(pos_scaling_contrib_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, n, S->loc_map(),
+                               S->status.get(), S->colscale.get(), out);
+        });
+        hipLaunchKernelGGL(pos_scaling_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, n, S->loc_map(), S->pos_sum.get(),
                            S->status.get(), S->colscale.get(), S->pos_status.get(), S->pos_scale.get());
         hipLaunchKernelGGL(scaling_pivots_pos_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, S->colperm.get(), S->pos_status.get(),
                            S->pos_scale.get(), S->uscale.get(), S->free_mask.get(), S->counters.get() + 1);
@@ -1159,11 +1153,7 @@ static void upload_scaling(Context* c, SplitOperator* S, const ipxint* status, c
     IPXK_HIP(hipMemsetAsync(S->counters.get(), 0, 2 * sizeof(int), s));
     hipLaunchKernelGGL(scaling_columns_kernel, dim3(vec_grid((int64_t)N)), dim3(kBlock), 0, s, (int64_t)N,
                        S->status_raw.get(), S->colscale.get(), S->Wsplit.get(), S->status.get(), S->counters.get());
-    if (S->part)
-        scaling_positions(c, S, status, colscale);
-    else
-        hipLaunchKernelGGL(scaling_pivots_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, S->colperm.get(), S->basis.get(),
-                           S->status.get(), S->colscale.get(), S->uscale.get(), S->free_mask.get(), S->counters.get() + 1);
+    scaling_positions(c, S);
     int h[2] = {0, 0};
     S->counters.download(h, 2, s);
     if (h[0]) throw Error(IPXK_E_ARGUMENT, "status entry out of range");
@@ -1197,6 +1187,9 @@ static void finish_prepare(Context* c, SplitOperator* S, const ipxint* status, c
     upload_scaling(c, S, status, colscale);
     const size_t mm = (size_t)std::max(m, 1);
     S->w0.resize(mm); S->w1.resize(mm); S->w2.resize(mm); S->w3.resize(mm); S->tI.resize(mm);
+    S->aB.ensure(mm);
+    S->zeros.ensure(mm);
+    IPXK_HIP(hipMemsetAsync(S->zeros.get(), 0, mm * sizeof(double), s));
     // where every sweep finds its right-hand side: U' in the input vector itself, L' in the result of U'
     // (by position), L in the input vector THROUGH rowperm (the operator's N N' product is formed in the row
     // order of A: the permutation into pivot order is folded into the gather), U in the result of L;
@@ -1618,8 +1611,8 @@ void split_prepare_host(Context* c, const ipxint* Lp, const ipxint* Li, const do
     hipStream_t s = c->stream;
     IPXK_REQUIRE(!comm_rows(c), kRowPartitionRefusal);
     const bool part = comm_cols(c);
-    if (part) learn_col_offsets(c);
-    const int64_t ncols = part ? c->n_global : n;       // the structural columns basis[] numbers
+    learn_col_offsets(c);
+    const int64_t ncols = c->n_global;                  // the structural columns basis[] numbers
     auto check_arguments = [&] {
         IPXK_REQUIRE(ncols + m < (int64_t(1) << 31), "column count exceeds 32 bits");
         IPXK_REQUIRE(Lp[m] < (int64_t(1) << 31) && Up[m] < (int64_t(1) << 31), "factor nnz exceeds 32 bits");
@@ -1717,19 +1710,15 @@ void split_prepare_host(Context* c, const ipxint* Lp, const ipxint* Li, const do
         S->colperm.upload(cpm, s);
         S->basis.upload(bs, s);
         S->part = part;
-        if (part) {     // where each basis position lives in this rank's local vectors (SplitOperator::loc)
+        if (part) {     // where each basis position lives in this rank's local vectors (SplitOperator::loc_map)
             const int64_t c0 = c->col_offset;
-            S->h_loc.assign((size_t)m, -1);
+            std::vector<int> loc((size_t)m, -1);
             for (int p = 0; p < m; p++) {
                 const int64_t j = basis[p];
-                if (j >= ncols) S->h_loc[(size_t)p] = (int)(n + (j - ncols));
-                else if (j >= c0 && j < c0 + n) S->h_loc[(size_t)p] = (int)(j - c0);
+                if (j >= ncols) loc[(size_t)p] = (int)(n + (j - ncols));
+                else if (j >= c0 && j < c0 + n) loc[(size_t)p] = (int)(j - c0);
             }
-            S->loc.upload(S->h_loc, s);
-            const size_t mm = (size_t)std::max(m, 1);
-            S->aB.ensure(mm);
-            S->zeros.ensure(mm);
-            IPXK_HIP(hipMemsetAsync(S->zeros.get(), 0, mm * sizeof(double), s));
+            S->loc.upload(loc, s);
         }
     }
     finish_prepare(c, S.get(), status, colscale);
@@ -1902,8 +1891,7 @@ int split_apply_dev(Context* c, const double* rhs, double* lhs, const int* done)
             launch_spmv(c->Arows, c->tcols.get(), e2, nullptr, done, s);
         }
     };
-    if (S->part) allreduce_product(c, work, (size_t)m, product);
-    else product(work);
+    allreduce_product(c, work, (size_t)m, product);
     time_mark(c, kTimeOp, false);
     // inverse(B) * that (the L sweep reads `work` through rowperm)
     time_mark(c, kTimeB, true);
@@ -1959,14 +1947,6 @@ void solve_dense_dev(Context* c, const double* rhs, double* lhs, char trans) {
 // ---------------------------------------------------------------------------
 // KKTSolverBasis::_Solve                        (kkt_solver_basis.cc:75-194)
 // ---------------------------------------------------------------------------
-// work[p] = a[basis[p]] for BASIC_FREE positions, 0 otherwise            (:87-97)
-__global__ void basis_free_rhs_kernel(int m, const int* __restrict__ basis, const int* __restrict__ status,
-                                      const double* __restrict__ a, double* __restrict__ work) {
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
-        const int j = basis[p];
-        work[p] = status[j] == IPXK_BASIC_FREE ? a[j] : 0.0;
-    }
-}
 // slack columns: tI[i] = W[n+i]*(a[n+i] - work[i])  (work == nullptr: W*a)   (:102-120, :178-188)
 __global__ void basis_slack_kernel(int m, const double* __restrict__ WI, const double* __restrict__ aI,
                                    const double* __restrict__ work, double* __restrict__ tI) {
@@ -1975,36 +1955,6 @@ __global__ void basis_slack_kernel(int m, const double* __restrict__ WI, const d
         tI[i] = s != 0.0 ? (aI[i] - (work ? work[i] : 0.0)) * s : 0.0;
     }
 }
-// rhs[p] = (rhs[p]-work[p])/d + a[j]*d for BASIC, 0 for BASIC_FREE          (:128-138)
-__global__ void basis_reduce_rhs_kernel(int m, const int* __restrict__ basis, const int* __restrict__ status,
-                                        const double* __restrict__ colscale, const double* __restrict__ a,
-                                        const double* __restrict__ work, double* __restrict__ rhs) {
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
-        const int j = basis[p];
-        if (status[j] == IPXK_BASIC) {
-            const double d = colscale[j];
-            rhs[p] = (rhs[p] - work[p]) / d + a[j] * d;
-        } else {
-            rhs[p] = 0.0;
-        }
-    }
-}
-// y[p] = y[p]/d for BASIC, a[j] for BASIC_FREE                               (:164-174)
-__global__ void basis_unscale_y_kernel(int m, const int* __restrict__ basis, const int* __restrict__ status,
-                                       const double* __restrict__ colscale, const double* __restrict__ a,
-                                       double* __restrict__ y) {
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
-        const int j = basis[p];
-        y[p] = status[j] == IPXK_BASIC ? y[p] / colscale[j] : a[j];
-    }
-}
-// x[basis[p]] = work[p]                                                      (:192-193)
-__global__ void basis_scatter_x_kernel(int m, const int* __restrict__ basis, const double* __restrict__ work,
-                                       double* __restrict__ x) {
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x)
-        x[basis[p]] = work[p];
-}
-
 // out[i] = acc + tI[i]  (acc = sum_j a_ij t_j starting from 0)
 struct EpiBasisRhs : ProdMul {
     const double* tI; double* out;
@@ -2020,12 +1970,14 @@ struct EpiBasisResidual : ProdMul {
     __device__ __forceinline__ void finish(int i, double acc, double&) const { out[i] = acc - tI[i]; }
 };
 
-// ---- the same on a column-partitioned context: kernels by basis position (pos_status, pos_scale, aB = a[basis[.]]) ----
+// kernels by basis position p: pos_status, pos_scale and aB hold status, colscale and a of column basis[p]
+// work[p] = aB[p] for BASIC_FREE positions, 0 otherwise                     (:87-97)
 __global__ void basis_free_rhs_pos_kernel(int m, const int* __restrict__ pos_status, const double* __restrict__ aB,
                                           double* __restrict__ work) {
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x)
         work[p] = pos_status[p] == IPXK_BASIC_FREE ? aB[p] : 0.0;
 }
+// rhs[p] = (rhs[p]-work[p])/d + aB[p]*d for BASIC, 0 for BASIC_FREE         (:128-138)
 __global__ void basis_reduce_rhs_pos_kernel(int m, const int* __restrict__ pos_status, const double* __restrict__ pos_scale,
                                             const double* __restrict__ aB, const double* __restrict__ work,
                                             double* __restrict__ rhs) {
@@ -2038,12 +1990,13 @@ __global__ void basis_reduce_rhs_pos_kernel(int m, const int* __restrict__ pos_s
         }
     }
 }
+// y[p] = y[p]/d for BASIC, aB[p] for BASIC_FREE                             (:164-174)
 __global__ void basis_unscale_y_pos_kernel(int m, const int* __restrict__ pos_status, const double* __restrict__ pos_scale,
                                            const double* __restrict__ aB, double* __restrict__ y) {
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x)
         y[p] = pos_status[p] == IPXK_BASIC ? y[p] / pos_scale[p] : aB[p];
 }
-// x_B into the entries this rank holds: its own structural columns and every slack column
+// x_B into the entries this rank holds: its own structural columns and every slack column          (:192-193)
 __global__ void basis_scatter_x_pos_kernel(int m, const int* __restrict__ loc, const double* __restrict__ work,
                                            double* __restrict__ x) {
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < m; p += gridDim.x * blockDim.x) {
@@ -2052,17 +2005,18 @@ __global__ void basis_scatter_x_pos_kernel(int m, const int* __restrict__ loc, c
     }
 }
 
-// Three all-reduces of m (a_B, the right-hand side product, b - N x_N) plus one per CR Apply.  Structural products
-// are this rank's partials; b and the slack terms enter on rank 0 only.  Every m-vector is then the same on all ranks.
-static CrResult kkt_basis_solve_cols(Context* c, const double* a, const double* b, double tol, ipxint maxiter,
-                                     double* x, double* y, ipxk_interrupt_fn interrupt, void* user, ipxk_times* times) {
+// Column partition: three all-reduces of m (a_B, the right-hand side product, b - N x_N) plus one per CR Apply.
+// Structural products are this rank's partials; b and the slack terms enter on rank 0 only.  Every m-vector is then the
+// same on all ranks.  Unpartitioned, the all-reduces are no exchanges: each product is written to its destination.
+CrResult kkt_basis_solve_dev(Context* c, const double* a, const double* b, double tol, ipxint maxiter,
+                             double* x, double* y, ipxk_interrupt_fn interrupt, void* user, ipxk_times* times) {
     SplitOperator* S = c->split;
     const int m = S->m, n = (int)c->n;
     hipStream_t s = c->stream;
     const int g = vec_grid(m);
     const double* W = S->Wsplit.get();
     double* rhs = S->w2.get();
-    double* work = S->w1.get();
+    double* work = S->w1.get();     // note: split_apply_dev uses w0/w1 only inside the CR loop
     if (c->v_lhs.size() < (size_t)std::max(m, 1)) c->v_lhs.resize(std::max(m, 1));
     if (c->v_rhs.size() < (size_t)std::max(m, 1)) c->v_rhs.resize(std::max(m, 1));
     double* lhs = c->v_lhs.get();
@@ -2073,9 +2027,9 @@ static CrResult kkt_basis_solve_cols(Context* c, const double* a, const double* 
 
     // a_B[p] = a[basis[p]]: the owners' entries, then the slack positions
     allreduce_product(c, aB, (size_t)m, [&](double* out) {
-        hipLaunchKernelGGL(pos_contrib_kernel, dim3(g), dim3(kBlock), 0, s, m, n, S->loc.get(), a, out);
+        hipLaunchKernelGGL(pos_contrib_kernel, dim3(g), dim3(kBlock), 0, s, m, n, S->loc_map(), a, out);
     });
-    hipLaunchKernelGGL(pos_slack_kernel, dim3(g), dim3(kBlock), 0, s, m, n, S->loc.get(), a, aB);
+    hipLaunchKernelGGL(pos_slack_kernel, dim3(g), dim3(kBlock), 0, s, m, n, S->loc_map(), a, aB);
     // :87-99
     if (S->num_free > 0) {
         hipLaunchKernelGGL(basis_free_rhs_pos_kernel, dim3(g), dim3(kBlock), 0, s, m, S->pos_status.get(), (const double*)aB,
@@ -2088,6 +2042,7 @@ static CrResult kkt_basis_solve_cols(Context* c, const double* a, const double* 
         EpiBasisColumns ec{{}, W, a, c->tcols.get()};
         launch_spmv(c->Acols, wk, ec, nullptr, nullptr, s);
     } else {
+        // no free variables: alpha_j = d2_j * a_j
         hipLaunchKernelGGL(basis_slack_kernel, dim3(vec_grid(n)), dim3(kBlock), 0, s, n, W, a,
                            (const double*)nullptr, c->tcols.get());
     }
@@ -2126,79 +2081,7 @@ static CrResult kkt_basis_solve_cols(Context* c, const double* a, const double* 
     }
     // :191-193
     solve_dense_dev(c, work, work, 'N');
-    hipLaunchKernelGGL(basis_scatter_x_pos_kernel, dim3(g), dim3(kBlock), 0, s, m, S->loc.get(), work, x);
-    IPXK_HIP(hipGetLastError());
-    return res;
-}
-
-CrResult kkt_basis_solve_dev(Context* c, const double* a, const double* b, double tol, ipxint maxiter,
-                             double* x, double* y, ipxk_interrupt_fn interrupt, void* user,
-                             ipxk_times* times) {
-    SplitOperator* S = c->split;
-    if (S->part) return kkt_basis_solve_cols(c, a, b, tol, maxiter, x, y, interrupt, user, times);
-    const int m = S->m, n = (int)c->n;
-    hipStream_t s = c->stream;
-    const int g = vec_grid(m);
-    const double* W = S->Wsplit.get();
-    double* rhs = S->w2.get();
-    double* work = S->w1.get();     // note: split_apply_dev uses w0/w1 only inside the CR loop
-    if (c->v_lhs.size() < (size_t)std::max(m, 1)) c->v_lhs.resize(std::max(m, 1));
-    if (c->v_rhs.size() < (size_t)std::max(m, 1)) c->v_rhs.resize(std::max(m, 1));
-    double* lhs = c->v_lhs.get();
-    double* crrhs = c->v_rhs.get();
-
-    // :87-99
-    if (S->num_free > 0) {
-        hipLaunchKernelGGL(basis_free_rhs_kernel, dim3(g), dim3(kBlock), 0, s, m, S->basis.get(),
-                           S->status.get(), a, S->tI.get());
-        solve_dense_dev(c, S->tI.get(), work, 'T');
-    }
-    const double* wk = S->num_free > 0 ? work : nullptr;
-    // :101-121  rhs = sum over nonbasic j of AI[:,j] * d2_j*(a_j - AI[:,j]'work)
-    if (wk) {
-        EpiBasisColumns ec{{}, W, a, c->tcols.get()};
-        launch_spmv(c->Acols, wk, ec, nullptr, nullptr, s);
-    } else {
-        // no free variables: alpha_j = d2_j * a_j
-        hipLaunchKernelGGL(basis_slack_kernel, dim3(vec_grid(n)), dim3(kBlock), 0, s, n, W, a,
-                           (const double*)nullptr, c->tcols.get());
-    }
-    hipLaunchKernelGGL(basis_slack_kernel, dim3(g), dim3(kBlock), 0, s, m, W + n, a + n, wk, S->tI.get());
-    {
-        EpiBasisRhs er{{}, S->tI.get(), rhs};
-        launch_spmv(c->Arows, c->tcols.get(), er, nullptr, nullptr, s);
-    }
-    solve_dense_dev(c, rhs, rhs, 'N');
-    // :124
-    solve_dense_dev(c, b, work, 'N');
-    // :128-138
-    hipLaunchKernelGGL(basis_reduce_rhs_kernel, dim3(g), dim3(kBlock), 0, s, m, S->basis.get(),
-                       S->status.get(), S->colscale.get(), a, work, rhs);
-    // :141-143
-    hipLaunchKernelGGL(gather_perm_kernel, dim3(g), dim3(kBlock), 0, s, m, rhs, S->colperm.get(), crrhs,
-                       (const int*)nullptr);
-    // :146-157
-    IPXK_HIP(hipMemsetAsync(lhs, 0, sizeof(double) * m, s));
-    CrResult res = cr_solve_dev(c, crrhs, tol, nullptr, maxiter, lhs, true, interrupt, user, nullptr, 0, times);
-    // :160-161
-    hipLaunchKernelGGL(scatter_perm_kernel, dim3(g), dim3(kBlock), 0, s, m, lhs, S->colperm.get(), y,
-                       (const int*)nullptr);
-    // :164-175
-    hipLaunchKernelGGL(basis_unscale_y_kernel, dim3(g), dim3(kBlock), 0, s, m, S->basis.get(),
-                       S->status.get(), S->colscale.get(), a, y);
-    solve_dense_dev(c, y, y, 'T');
-    // :178-188  x[nonbasic] and work = b - N*x[nonbasic]
-    {
-        EpiBasisColumns ec{{}, W, a, x};
-        launch_spmv(c->Acols, y, ec, nullptr, nullptr, s);
-        hipLaunchKernelGGL(basis_slack_kernel, dim3(g), dim3(kBlock), 0, s, m, W + n, a + n, (const double*)y,
-                           x + n);
-        EpiBasisResidual er{{}, b, x + n, work};
-        launch_spmv(c->Arows, x, er, nullptr, nullptr, s);
-    }
-    // :191-193
-    solve_dense_dev(c, work, work, 'N');
-    hipLaunchKernelGGL(basis_scatter_x_kernel, dim3(g), dim3(kBlock), 0, s, m, S->basis.get(), work, x);
+    hipLaunchKernelGGL(basis_scatter_x_pos_kernel, dim3(g), dim3(kBlock), 0, s, m, S->loc_map(), work, x);
     IPXK_HIP(hipGetLastError());
     return res;
 }

@@ -157,14 +157,15 @@ struct SplitOperator {
     DevBuf<ipxint> in_Lp, in_Li, in_Up, in_Ui, cut_Lp, cut_Up, cut_Ui;
     DevBuf<double> in_Lx, in_Ux, cut_Ux;
     DevBuf<int> cut_cnt, cut_start;
-    // Column-partitioned context (comm_cols): basis[] holds GLOBAL column numbers, replicated on every rank.  loc[p] is
-    // where basis position p lives in this rank's local (n+m)-vectors: 0..n-1 a structural column of this rank, n..n+m-1
-    // a slack column (every rank), -1 a structural column of another rank.  pos_status / pos_scale: status and colscale
-    // of every basis position, formed from the owners' contributions (trisolve.hip).
+    // where basis position p lives in this rank's local (n+m)-vectors (loc_map()): 0..n-1 a structural column of this
+    // rank, n..n+m-1 a slack column (every rank), -1 a structural column of another rank.  Unpartitioned, that is basis[p]
+    // itself; on a column-partitioned context (comm_cols, part) basis[] holds GLOBAL column numbers, replicated on every
+    // rank, and loc is its own array.  pos_status / pos_scale: status and colscale of every basis position, formed from
+    // the owners' contributions (trisolve.hip).
     bool part = false;
-    std::vector<int> h_loc;
     DevBuf<int> loc, pos_status;
     DevBuf<double> pos_sum, pos_scale, aB, zeros;
+    const int* loc_map() const { return part ? loc.get() : basis.get(); }
 };
 
 // Launch plan of a sweep from its level structure (host arithmetic, O(#levels)).
