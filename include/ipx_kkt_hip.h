@@ -600,6 +600,55 @@ int ipxk_ipm_driver(ipxk_context* ctx, const double* b, const double* c,
                     const ipxk_ipm_params* params, ipxk_ipm_info* info,
                     ipxk_interrupt_fn interrupt, void* interrupt_user);
 
+/* IPM::ComputeStartingPoint (src/ipm.cc:125-259) on the device, into the resident
+ * iterate: KKTSolverDiag::Factorize(nullptr) (G = I); x = clamp(0, lb, ub) and the
+ * first KKT solve (a = 0, rhs b - AI x, tol 0.1 |rb|_inf), x += dx; xl = x - lb,
+ * xu = ub - x shifted by 1 + 1.5 xinfeas; if |c|_2 = 0, zl, zu = 1 or 0 by bound
+ * finiteness, else the second solve (a = c, rhs 0, tol 0.1 |c|_inf), zl = c - AI'y,
+ * zl += 0.05 c and y *= 0.95 if |zl|_2 < 0.05 |c|_2, the split into zl, zu by the
+ * bounds shifted by 1 + 1.5 zinfeas; then the leveling shifts (:226-251).  The states
+ * follow Iterate::Initialize (src/iterate.cc:76-88; lb == ub gives BARRIER_BOXED),
+ * so ipxk_ipm_driver can be called right after.  b[m], c, lb, ub [n+m] in the forms of
+ * ipxk_ipm_driver; of params only kkt_maxiter (-1: m + 100) and precond_dense_cols
+ * are read.  NULL arguments, lb > ub, lb = +inf, ub = -inf and NaNs in b, c, lb, ub
+ * are refused (IPXK_E_ARGUMENT, the first such index in the message).
+ * info: status_ipm as ipm.cc:31-41 (errflag 999 from the interrupt: IPX_STATUS_time_limit
+ * 5 and errflag 0; any other errflag: IPX_STATUS_failed 8 with the errflag; else
+ * IPX_STATUS_not_run 0); kktiter = CR iterations of both solves; presidual,
+ * dresidual, complementarity, mu, pobjective, dobjective of the resulting point; the
+ * other fields 0.  An errflag from the factorization or a solve leaves the point of
+ * the Iterate constructor (src/iterate.cc:31-57: x = 0, y = 0, xl / xu / zl / zu =
+ * 1 / inf / 0 by bound kind), as LpSolver expects (src/lp_solver.cc:377-379).  The
+ * interrupt is checked as in ipxk_kkt_diag_solve.  Every reduction is a fixed-order
+ * sum of block partials: two calls on the same inputs give the same bits.
+ * Column partition: collective.  One all-reduce carries each rank's verdict and the
+ * fingerprint of b and the slack parts of c, lb, ub (as ipxk_ipm_driver; mismatch:
+ * IPXK_E_ARGUMENT on every rank).  Besides the factorization, the two KKT solves and
+ * the evaluation of the point (as one driver iteration's: one all-reduce of m and one
+ * all-gather of 10): one all-reduce of m (rb), all-gathers of 3 (xinfeas, |c|^2,
+ * |c|_inf), 1 (|zl|^2), 1 (zinfeas) and 3 (the leveling sums) doubles per rank (the
+ * second and third are skipped when c = 0).  Slack terms count on rank 0 only, so one
+ * rank reproduces the unpartitioned context bit for bit.  Row partition: refused. */
+int ipxk_ipm_starting_point(ipxk_context* ctx, const double* b, const double* c,
+                            const double* lb, const double* ub,
+                            const ipxk_ipm_params* params, ipxk_ipm_info* info,
+                            ipxk_interrupt_fn interrupt, void* interrupt_user);
+/* IPM::LoadStartingPoint (src/ipm.cc:261-316): the caller's point x, xl, xu, zl, zu
+ * [n+m], y [m] becomes the resident iterate after repair.  It must be valid, as the
+ * reference asserts: at a finite bound xl (xu) and zl (zu) finite and nonnegative, at
+ * an infinite one xl (xu) = inf and zl (zu) = 0; otherwise IPXK_E_ARGUMENT with the
+ * first offending index.  mu = the mean of the products with both factors > 0 (1.0 if
+ * there are none); a pair with both entries 0 becomes sqrt(mu), sqrt(mu), one zero
+ * entry becomes mu over the other.  States as Iterate::Initialize.
+ * Column partition: forms of ipxk_iterate_set; collective.  One all-reduce carries
+ * each rank's verdict and a fingerprint of y and the slack parts of x, xl, xu, zl,
+ * zu, lb, ub, one all-gather of 2 the sum and the count (slack pairs on rank 0). */
+int ipxk_ipm_load_starting_point(ipxk_context* ctx, const double* x,
+                                 const double* xl, const double* xu,
+                                 const double* y, const double* zl,
+                                 const double* zu, const double* lb,
+                                 const double* ub);
+
 /* The main IPM phase (LpSolver::RunMainIPM, src/lp_solver.cc:456-462): IPM::Driver around KKTSolverBasis.
  * Every iteration's KKTSolverBasis::_Factorize (src/kkt_solver_basis.cc:20-63) runs on the device: scaling
  * factors from the resident iterate (Iterate::ScalingFactor, src/iterate.cc:183-198), Maxvolume
@@ -639,7 +688,8 @@ int ipxk_comm_init(ipxk_context* ctx, const void* id128, int rank, int nranks);
  * dense-column preconditioning gathers those of every rank.  The basis path
  * (ipxk_split_prepare and what uses its operator) runs on this partition; see
  * ipxk_split_prepare for its conventions.  So does the device IPM (the iterate,
- * ipxk_newton_solve, ipxk_ipm_step, ipxk_ipm_driver); see ipxk_iterate_set. */
+ * ipxk_newton_solve, ipxk_ipm_step, ipxk_ipm_driver, ipxk_ipm_starting_point,
+ * ipxk_ipm_load_starting_point); see ipxk_iterate_set. */
 int ipxk_comm_init_columns(ipxk_context* ctx, const void* id128, int rank, int nranks);
 /* What the transport itself reports about the communicator of this context:
  * transport 0 = none, 1 = RCCL (nranks / rank from ncclCommCount /

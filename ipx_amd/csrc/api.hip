@@ -760,6 +760,51 @@ int ipxk_ipm_driver_basis(ipxk_context* c, const double* b, const double* cc, co
     });
 }
 
+int ipxk_ipm_starting_point(ipxk_context* c, const double* b, const double* cc, const double* lb, const double* ub,
+                            const ipxk_ipm_params* params, ipxk_ipm_info* info, ipxk_interrupt_fn interrupt,
+                            void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(c, "NULL argument");
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* db = stage_in(c, b, m, c->nw_in[0]);
+        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        ipm_starting_point_dev(c, db, dc, dlb, dub, params, info, interrupt, interrupt_user);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+// Column partition: collective like ipxk_iterate_set (the ranks agree on the verdict and the replicated parts).
+int ipxk_ipm_load_starting_point(ipxk_context* c, const double* x, const double* xl, const double* xu, const double* y,
+                                 const double* zl, const double* zu, const double* lb, const double* ub) {
+    return guarded([&] {
+        IPXK_REQUIRE(c, "NULL argument");
+        const bool args = x && xl && xu && y && zl && zu && lb && ub;
+        IPXK_REQUIRE(args || comm_cols(c), "NULL argument");
+        bind_device(c);
+        c->it_set = false;
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        std::string err = args ? std::string() : std::string("NULL argument");
+        if (!args) {
+            agree_on_arguments(c, err, 0, "ipxk_ipm_load_starting_point", "y and the slack parts of x, xl, xu, zl, zu, lb and ub");
+            return;
+        }
+        DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
+        const double* src[6] = {x, xl, xu, y, zl, zu};
+        for (int k = 0; k < 6; k++) {
+            const size_t len = k == 3 ? m : N;
+            dst[k]->resize(std::max<size_t>(len, 1));
+            copy_in(c, dst[k]->get(), src[k], len * sizeof(double));
+        }
+        c->it_state.resize(std::max<size_t>(N, 1));
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        ipm_load_starting_point_dev(c, dlb, dub);
+    });
+}
+
 int ipxk_iterate_factorize_diag(ipxk_context* c, int precond_dense_cols, ipxint* errflag) {
     return guarded([&] {
         IPXK_REQUIRE(c && errflag && c->it_set, "no iterate on the device (ipxk_iterate_set)");

@@ -279,6 +279,8 @@ void combine_over_ranks(Context* c, double* row, const CombineOp* ops, int k);
 // whether this rank's (n+m)-vectors include the replicated slack entries in its reductions (rank 0 of a column partition)
 bool with_replicated(const Context* c);
 void iterate_objectives_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double out3[3]);
+// rb = b - AI x for an (n+m)-vector x on the device (column partition: one all-reduce of m; rb replicated)
+void residual_rb(Context* c, const double* b, const double* x, double* rb);
 void model_norms_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, double out2[2]);
 double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64_t len, double alpha0,
                             ipxint* blocking);
@@ -293,6 +295,16 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
 void ipm_driver_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
                     const ipxk_ipm_params* prm, ipxk_ipm_info* info, ipxk_interrupt_fn interrupt, void* user,
                     bool use_basis = false, ipxint* basis_out = nullptr, ipxint* status_out = nullptr);
+
+// column partition: fingerprint of b and the slack parts of c, lb, ub (device), what the ranks of the device IPM agree on
+uint64_t model_fingerprint(Context* c, const double* b, const double* cc, const double* lb, const double* ub);
+
+// ---- start.hip ----
+// IPM::ComputeStartingPoint (the model vectors on the device; b, c, lb, ub checked) and IPM::LoadStartingPoint (the
+// six iterate vectors already copied into it_*; lb, ub on the device)
+void ipm_starting_point_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
+                            const ipxk_ipm_params* prm, ipxk_ipm_info* info, ipxk_interrupt_fn interrupt, void* user);
+void ipm_load_starting_point_dev(Context* c, const double* lb, const double* ub);
 
 // ---- kkt_diag.hip ----
 void kkt_diag_factorize_dev(Context* c, const double* xl, const double* xu, const double* zl,

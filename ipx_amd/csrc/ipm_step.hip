@@ -229,22 +229,23 @@ static void basis_factorize_dev(Context* c, std::vector<ipxint>& basis, std::vec
 static const char* const kDriverRowRefusal =
     "the device IPM does not run on a row-partitioned system: partition the structural columns (ipxk_comm_init_columns)";
 
-static void driver_agree(Context* c, const double* b, const double* cc, const double* lb, const double* ub) {
+uint64_t model_fingerprint(Context* c, const double* b, const double* cc, const double* lb, const double* ub) {
     const size_t m = (size_t)c->m, n = (size_t)c->n;
+    std::vector<double> h(4 * m);
+    staged_d2h(h.data(), b, m * sizeof(double), c->stream);
+    staged_d2h(h.data() + m, cc + n, m * sizeof(double), c->stream);
+    staged_d2h(h.data() + 2 * m, lb + n, m * sizeof(double), c->stream);
+    staged_d2h(h.data() + 3 * m, ub + n, m * sizeof(double), c->stream);
+    Fingerprint F;
+    F.add(h.data(), h.size());
+    return F.h;
+}
+
+static void driver_agree(Context* c, const double* b, const double* cc, const double* lb, const double* ub) {
     std::string err;
     uint64_t fp = 0;
-    if (!c->it_set) {
-        err = "no iterate on the device (ipxk_iterate_set)";
-    } else {
-        std::vector<double> h(4 * m);
-        staged_d2h(h.data(), b, m * sizeof(double), c->stream);
-        staged_d2h(h.data() + m, cc + n, m * sizeof(double), c->stream);
-        staged_d2h(h.data() + 2 * m, lb + n, m * sizeof(double), c->stream);
-        staged_d2h(h.data() + 3 * m, ub + n, m * sizeof(double), c->stream);
-        Fingerprint F;
-        F.add(h.data(), h.size());
-        fp = F.h;
-    }
+    if (!c->it_set) err = "no iterate on the device (ipxk_iterate_set)";
+    else fp = model_fingerprint(c, b, cc, lb, ub);
     agree_on_arguments(c, err, fp, "ipxk_ipm_driver", "b and the slack parts of c, lb and ub");
 }
 

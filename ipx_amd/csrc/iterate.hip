@@ -246,18 +246,7 @@ void residual_vectors(Context* c, const double* b, const double* cc, const doubl
                       double* rc, double* rl, double* ru) {
     const int n = (int)c->n, m = (int)c->m, N = n + m;
     hipStream_t s = c->stream;
-    if (comm_cols(c)) {
-        // (b - sum_g A_g x_g) - x_slack: the partial sums go straight into the exchange buffer where there is one
-        double* stage = comm_stage(c, (size_t)m);
-        EpiIterRbPart eb{{}, c->rank == 0 ? b : nullptr, stage ? stage : rb};
-        launch_spmv(c->Arows, c->it_x.get(), eb, nullptr, nullptr, s);
-        if (stage) comm_allreduce_sum_staged(c, rb, (size_t)m);
-        else comm_allreduce_sum(c, rb, (size_t)m);
-        hipLaunchKernelGGL(subtract_slack_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, c->it_x.get() + n, rb);
-    } else {
-        EpiIterRb eb{{}, b, c->it_x.get() + n, rb};
-        launch_spmv(c->Arows, c->it_x.get(), eb, nullptr, nullptr, s);
-    }
+    residual_rb(c, b, c->it_x.get(), rb);
     EpiIterRc ec{{}, cc, c->it_zl.get(), c->it_zu.get(), c->it_state.get(), rc};
     launch_spmv(c->Acols, c->it_y.get(), ec, nullptr, nullptr, s);
     hipLaunchKernelGGL(iterate_bound_residuals_kernel, dim3(vec_grid(N)), dim3(kBlock), 0, s, n, m, c->it_state.get(),
@@ -319,6 +308,23 @@ void objectives_local(Context* c, const double* b, const double* cc, const doubl
 }
 
 }  // namespace
+
+void residual_rb(Context* c, const double* b, const double* x, double* rb) {
+    const int n = (int)c->n, m = (int)c->m;
+    hipStream_t s = c->stream;
+    if (comm_cols(c)) {
+        // (b - sum_g A_g x_g) - x_slack: the partial sums go straight into the exchange buffer where there is one
+        double* stage = comm_stage(c, (size_t)m);
+        EpiIterRbPart eb{{}, c->rank == 0 ? b : nullptr, stage ? stage : rb};
+        launch_spmv(c->Arows, x, eb, nullptr, nullptr, s);
+        if (stage) comm_allreduce_sum_staged(c, rb, (size_t)m);
+        else comm_allreduce_sum(c, rb, (size_t)m);
+        hipLaunchKernelGGL(subtract_slack_kernel, dim3(vec_grid(m)), dim3(kBlock), 0, s, m, x + n, rb);
+    } else {
+        EpiIterRb eb{{}, b, x + n, rb};
+        launch_spmv(c->Arows, x, eb, nullptr, nullptr, s);
+    }
+}
 
 bool with_replicated(const Context* c) { return !comm_cols(c) || c->rank == 0; }
 

@@ -34,7 +34,7 @@ EXPORTS = [
     "ipxk_iterate_residuals", "ipxk_iterate_complementarity", "ipxk_step_to_boundary", "ipxk_ipm_step", "ipxk_iterate_objectives", "ipxk_ipm_driver", "ipxk_iterate_factorize_diag", "ipxk_comm_unique_id", "ipxk_comm_init", "ipxk_comm_init_columns", "ipxk_comm_info", "ipxk_maxvolume_sequential",
     "ipxk_time_normal_apply", "ipxk_equilibrate", "ipxk_transpose", "ipxk_lu_factorize", "ipxk_lu_factorize_basis",
     "ipxk_lu_get_factors", "ipxk_lu_generation", "ipxk_split_prepare_lu", "ipxk_maxvolume", "ipxk_ipm_driver_basis",
-    "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
+    "ipxk_ipm_starting_point", "ipxk_ipm_load_starting_point", "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
     "ipxk_dev_download",
 ]
 
@@ -549,6 +549,23 @@ class KktContext:
         out.update(basis=basis, status=status)
         return out
 
+    def ipm_starting_point(self, b, c, lb, ub, kkt_maxiter=-1, precond_dense_cols=True, interrupt=None):
+        """IPM::ComputeStartingPoint on the device into the resident iterate (host model vectors); returns the info
+        dict (status_ipm 0 on success, 5 after an interrupt, 8 with the errflag of a failed factorization or solve).
+        Column partition: the forms of ipm_driver; collective."""
+        prm = IpmParams(0.3, 1e-6, 1e-8, kkt_maxiter, 300, 1 if precond_dense_cols else 0)
+        info = IpmInfo()
+        cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
+        self._check(self.lib.ipxk_ipm_starting_point(self.h, _fp(_F(b)), _fp(_F(c)), _fp(_F(lb)), _fp(_F(ub)),
+                                                     C.byref(prm), C.byref(info), cb, None))
+        return {name: getattr(info, name) for name, _ in IpmInfo._fields_}
+
+    def ipm_load_starting_point(self, it, lb, ub):
+        """IPM::LoadStartingPoint: the point `it` (keys of IT_KEYS) repaired into the resident iterate.  Column
+        partition: the forms of iterate_set; collective."""
+        vecs = [_F(it[key]) for key in self.IT_KEYS]
+        self._check(self.lib.ipxk_ipm_load_starting_point(self.h, *[_fp(v) for v in vecs], _fp(_F(lb)), _fp(_F(ub))))
+
     def kkt_diag_get(self):
         W, rs = np.zeros(self.n + self.m, f64), np.zeros(self.m, f64)
         self._check(self.lib.ipxk_kkt_diag_get(self.h, _fp(W), _fp(rs)))
@@ -706,8 +723,9 @@ class KktContext:
         With columns=True the basis path (split_prepare, split_rescale, split_apply, the triangular solves,
         cr_solve, kkt_basis_solve) runs too, with the slabs of partition.col_slab (contiguous, in rank order) and
         the global basis numbering; the device LU and Maxvolume do not.  So does the device IPM (iterate_set, the
-        iterate's residuals, complementarity and objectives, newton_solve, ipm_step, ipm_driver; not
-        ipm_driver_basis), with partition.col_slice_iterate / col_slice_model / assemble_iterate for its vectors.
+        iterate's residuals, complementarity and objectives, newton_solve, ipm_step, ipm_driver, ipm_starting_point,
+        ipm_load_starting_point; not ipm_driver_basis), with partition.col_slice_iterate / col_slice_model /
+        assemble_iterate for its vectors.
         With rows the basis path and the device IPM are refused."""
         buf = (C.c_char * 128).from_buffer_copy(unique_id)
         fn = self.lib.ipxk_comm_init_columns if columns else self.lib.ipxk_comm_init

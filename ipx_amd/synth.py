@@ -512,3 +512,42 @@ def slack_basis_crash_state(m, n, num_entering, spread=1.0, seed=12345):
     d = np.concatenate([0.3 * 10.0 ** (-spread * rng.uniform(0.0, 1.0, n)), 10.0 ** (spread * rng.uniform(0.0, 1.0, m))])
     d[rng.choice(n, num_entering, replace=False)] = 10.0 ** (2.0 + spread * rng.uniform(0.0, 1.0, num_entering))
     return basis, status, d
+
+
+def mixed_bounds_lp(m, n, seed, per_col=6, num_dense=0, free=True, tail=0):
+    """min c'x, A x + s = b, lb <= (x, s) <= ub with structurals of every bound kind (boxed, lower-only, upper-only,
+    fixed lb == ub and, unless free=False, free) and rows of every type (slack bounds [0, inf) for <, (-inf, 0] for >,
+    [0, 0] for =).  Primal and dual feasible by construction, so an optimum exists.  Returns A, b, c, lb, ub with
+    (n+m)-vectors c, lb, ub (the slack costs 0) and the kind of each structural (0 boxed, 1 lower, 2 upper, 3 fixed,
+    4 free).  The last `tail` structurals are lower-only at 0 with nonnegative entries, lie at that bound in the
+    constructed point (columns at bound)."""
+    rng = np.random.default_rng(seed)
+    A = synthetic_lp(m, n, per_col, seed, num_dense=num_dense)
+    if tail:
+        x = A.x.copy()
+        x[A.p[n - tail]:] = np.abs(x[A.p[n - tail]:])
+        A = CscMatrix(m, n, A.p, A.i, x)
+    S = A.to_scipy()
+    N = n + m
+    kind = rng.integers(0, 5 if free else 4, n)
+    lo, width = rng.uniform(-2.0, 1.0, n), rng.uniform(1.0, 3.0, n)
+    lb, ub = np.full(N, -np.inf), np.full(N, np.inf)
+    lb[:n] = np.where(np.isin(kind, (0, 1, 3)), lo, -np.inf)
+    ub[:n] = np.where(np.isin(kind, (0, 2)), lo + width, np.where(kind == 3, lo, np.inf))
+    x0 = np.select([kind == 0, kind == 1, kind == 2, kind == 3],
+                   [lo + width * rng.uniform(0.2, 0.8, n), lo + rng.uniform(0.5, 2.0, n),
+                    lo + width - rng.uniform(0.5, 2.0, n), lo], rng.uniform(-1.0, 1.0, n))
+    if tail:
+        kind[n - tail:] = 1
+        lb[n - tail:n], ub[n - tail:n], x0[n - tail:] = 0.0, np.inf, 0.0
+    rows = rng.integers(0, 3, m)
+    lb[n:] = np.where(rows == 1, -np.inf, 0.0)
+    ub[n:] = np.where(rows == 0, np.inf, 0.0)
+    s0 = np.select([rows == 0, rows == 1], [rng.uniform(0.5, 2.0, m), -rng.uniform(0.5, 2.0, m)], 0.0)
+    b = S @ x0 + s0
+    # slack duals: 0 - y_i = zl - zu, so y < 0 on < rows and y > 0 on > rows
+    y0 = np.select([rows == 0, rows == 1], [-rng.uniform(0.5, 1.5, m), rng.uniform(0.5, 1.5, m)], rng.uniform(-1.0, 1.0, m))
+    z = rng.uniform(0.5, 2.0, n)
+    zs = np.select([kind == 1, kind == 2, kind == 4], [z, -z, 0.0], rng.uniform(-1.0, 1.0, n))
+    c = np.concatenate([S.T @ y0 + zs, np.zeros(m)])
+    return A, b, c, lb, ub, kind
