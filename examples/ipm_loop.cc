@@ -7,6 +7,9 @@
 // Then -- as LpSolver does when it switches from the initial to the main IPM (src/lp_solver.cc:375-462) -- the
 // basis-preconditioned phase: ipxk_ipm_driver_basis runs IPM::Driver around the basis solver (Maxvolume, LU
 // factorization and Prepare on the device every iteration) from the slack basis until the termination test holds.
+// With a fifth argument p > 0, p percent of the rows are equality rows (slack lb = ub = 0): the run then starts from
+// ipxk_ipm_starting_point, and between the two phases ipxk_ipm_starting_basis (StartingBasis, src/starting_basis.cc) pivots
+// the fixed slacks out of the slack basis, which is where the main phase goes on.
 //
 //   g++ -std=c++14 -O2 -Iinclude examples/ipm_loop.cc -Lipx_amd/lib -lipx_kkt_hip -Wl,-rpath,$PWD/ipx_amd/lib -o ipm_loop
 #include <algorithm>
@@ -27,6 +30,7 @@
 int main(int argc, char** argv) {
     const ipxint m = argc > 1 ? std::atol(argv[1]) : 2000, n = argc > 2 ? std::atol(argv[2]) : 5000;
     const int iterations = argc > 3 ? std::atoi(argv[3]) : 6;
+    const int eq_percent = argc > 5 ? std::atoi(argv[5]) : 0;
     std::mt19937_64 rng(7);
     std::uniform_real_distribution<double> mag(0.5, 4.0), unit(0.0, 1.0);
     // A: 8 entries per column, sorted rows
@@ -54,13 +58,22 @@ int main(int argc, char** argv) {
         for (ipxint p = Ap[j]; p < Ap[j + 1]; p++) { b[Ai[p]] += Ax[p] * x0[j]; c[j] += Ax[p] * y0[Ai[p]]; }
     for (ipxint i = 0; i < m; i++) { b[i] += x0[n + i]; c[n + i] = y0[i]; }
     for (ipxint j = 0; j < N; j++) c[j] += z0[j];
+    for (ipxint i = 0; i < m; i++)
+        if ((int)(rng() % 100) < eq_percent) { b[i] -= x0[n + i]; ub[n + i] = 0.0; c[n + i] = 0.0; }     // row i is '='
 
     ipxk_context* ctx = nullptr;
     CHECK(ipxk_create(m, n, Ap.data(), Ai.data(), Ax.data(), 0, &ctx));
     // interior start away from the solution: x = xl = 1, y = 0, zl = 1 (all variables have a lower bound only)
     std::vector<double> x(N, 1.0), xl(N, 1.0), xu(N, INFINITY), y(m, 0.0), zl(N, 1.0), zu(N, 0.0);
     std::vector<unsigned char> state(N, IPXK_STATE_BARRIER_LB);
-    CHECK(ipxk_iterate_set(ctx, x.data(), xl.data(), xu.data(), y.data(), zl.data(), zu.data(), state.data()));
+    if (eq_percent > 0) {
+        ipxk_ipm_params prm{0.3, 1e-6, 1e-8, -1, 100, 1};
+        ipxk_ipm_info info;
+        CHECK(ipxk_ipm_starting_point(ctx, b.data(), c.data(), lb.data(), ub.data(), &prm, &info, nullptr, nullptr));
+        if (info.errflag) { std::fprintf(stderr, "starting point errflag %ld\n", (long)info.errflag); return 1; }
+    } else {
+        CHECK(ipxk_iterate_set(ctx, x.data(), xl.data(), xu.data(), y.data(), zl.data(), zu.data(), state.data()));
+    }
     std::printf("%4s %10s %10s %10s %8s %8s %6s %6s\n", "iter", "presidual", "dresidual", "mu", "step_p", "step_d", "kkt1", "kkt2");
     for (int it = 0; it < iterations; it++) {
         ipxint errflag = 0;
@@ -78,6 +91,13 @@ int main(int argc, char** argv) {
     if (argc > 4 && std::atoi(argv[4]) != 0) {           // main IPM with the basis solver
         ipxk_ipm_params prm{0.3, 1e-6, 1e-8, -1, 100, 1};
         ipxk_ipm_info info;
+        if (eq_percent > 0) {
+            ipxk_starting_basis_info sb;
+            CHECK(ipxk_ipm_starting_basis(ctx, b.data(), c.data(), lb.data(), ub.data(), nullptr, &sb, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
+            std::printf("starting basis: errflag %ld, %ld exchanges, %ld dependent rows, %ld dependent columns, %.3f s\n", (long)sb.errflag,
+                        (long)sb.updates_start, (long)sb.dependent_rows, (long)sb.dependent_cols, sb.seconds);
+            if (sb.errflag) return 1;
+        }
         CHECK(ipxk_ipm_driver_basis(ctx, b.data(), c.data(), lb.data(), ub.data(), &prm, &info, nullptr, nullptr, nullptr, nullptr));
         std::printf("main IPM: status %ld after %ld iterations, %ld CR iterations, %ld basis updates; pobjective %.10e dobjective %.10e "
                     "presidual %.2e dresidual %.2e\n", (long)info.status_ipm, (long)info.iter, (long)info.kktiter, (long)info.basis_updates,

@@ -655,7 +655,10 @@ int ipxk_ipm_load_starting_point(ipxk_context* ctx, const double* x,
  * (ipxk_maxvolume), fresh factorization, Prepare; then the predictor-corrector step with the basis-
  * preconditioned solves.  The starting basis is the slack basis (ConstructBasisFromWeights with
  * crash_basis = 0, src/basis.cc:353-385); DropPrimal / DropDual (:36-43) are not taken.  Models whose
- * iterate holds free or fixed variables are refused (IPXK_E_UNSUPPORTED).  basis_out[m] / status_out[n+m]
+ * iterate holds free or fixed variables are refused (IPXK_E_UNSUPPORTED) -- unless the context holds a live
+ * starting basis (ipxk_ipm_starting_basis below): then the phase starts from that basis and its four-valued
+ * statuses instead, BASIC_FREE and NONBASIC_FIXED persist through Maxvolume and Prepare, and the scaling
+ * factors 0 / inf of fixed / free variables are taken as they are.  basis_out[m] / status_out[n+m]
  * (either may be NULL) return the final basis.  params->kkt_maxiter is ignored (KKTSolverBasis runs CR with
  * maxiter = -1).  Limits of the refactorizations: see ipxk_lu_factorize (dense bump).  Refused on any partitioned
  * context (it needs the device LU and Maxvolume). */
@@ -664,6 +667,58 @@ int ipxk_ipm_driver_basis(ipxk_context* ctx, const double* b, const double* c,
                           const ipxk_ipm_params* params, ipxk_ipm_info* info,
                           ipxint* basis_out, ipxint* status_out,
                           ipxk_interrupt_fn interrupt, void* interrupt_user);
+
+/* StartingBasis (src/starting_basis.cc:128-185) for crash_basis = 0 on the resident iterate: what LpSolver
+ * calls between the diag iterations and the main phase (src/lp_solver.cc:420-454).
+ *   1. Weights: Iterate::ScalingFactor per variable (src/iterate.cc:183-198), 0 where lb == ub.  A free
+ *      variable must have weight inf and every other one a finite weight, as the reference asserts
+ *      (IPXK_E_ARGUMENT otherwise).
+ *   2. Basis::ConstructBasisFromWeights (src/basis.cc:353-385) from the slack basis:
+ *      PivotFreeVariablesIntoBasis (:676-781) and PivotFixedVariablesOutOfBasis (:783-930) with their
+ *      stability swaps (> 4.0 against < 1.0), the dependency test (<= dependency_tol), the unbounded primal
+ *      / dual ray tests that set cols_inconsistent / rows_inconsistent, the volume-maximizing choice among
+ *      the stable pivots (>= 0.1 of the largest), and Basis::ExchangeIfStable (:286-321): an exchange whose
+ *      pivot from the row and from the column differ by more than 1e-8 relative is refused, the pivot
+ *      tolerance tightened (Basis::TightenLuPivotTol) and the basis refactorized.  Per candidate one
+ *      tableau column and one tableau row (two sweeps each over all m unknowns); the exchanges are kept as
+ *      product-form etas behind the factors (max_etas as in ipxk_maxvolume_sequential) and one block of
+ *      scalars per candidate reaches the host.
+ *   3. starting_basis.cc:153-173: basic variables of weight 0 / inf become BASIC_FREE, nonbasic ones
+ *      NONBASIC_FIXED; a lb == ub variable that ended NONBASIC_FIXED is fixed in the iterate (x = lb,
+ *      xl = xu = zl = zu = 0, IPXK_STATE_FIXED).
+ *   4. PostprocessDependencies (:52-126): dependent free columns are fixed at 0 with the basic variables
+ *      moved so that AI x is unchanged; the y_i of dependent equality rows go to 0 without altering AI'y
+ *      and their slacks become implied (xl = xu = inf, zl = zu = 0, IPXK_STATE_FREE).
+ * On return the context holds a fresh factorization of the starting basis and its operator, and
+ * ipxk_ipm_driver_basis goes on from them ("live starting basis"); ipxk_iterate_set,
+ * ipxk_ipm_starting_point, ipxk_ipm_load_starting_point and ipxk_reset_solver_state end that state.
+ * b[m], c, lb, ub [n+m] in the forms of ipxk_ipm_driver.  params may be NULL (dependency_tol 1e-6,
+ * include/ipx_parameters.h:68; max_etas 0 = 100).  basis_out[m], status_out[n+m] (IPXK_BASIC* / IPXK_NONBASIC*)
+ * and exchange_log (pairs jb, jn of the first log_cap exchanges, info->updates_start of them) may be NULL.
+ * What an inconsistent flag means is the caller's decision (src/lp_solver.cc:437-450).  info->errflag: 999
+ * from the interrupt (polled once per candidate), 301 / 306 from a refactorization (singular / too ill
+ * conditioned); then the iterate is unchanged and no starting basis is live.  Every reduction is a
+ * fixed-order tree over block partials with ties to the lowest index: two calls from the same iterate
+ * give the same bits.  Refused on any partitioned context (it needs the device LU). */
+typedef struct {
+    double dependency_tol;     /* dependency_tol, 1e-6; negative values count as 0 */
+    ipxint max_etas;           /* as ipxk_maxvolume_sequential */
+} ipxk_starting_basis_params;
+typedef struct {
+    ipxint errflag;
+    ipxint dependent_rows, dependent_cols;         /* Info::dependent_rows / dependent_cols */
+    ipxint rows_inconsistent, cols_inconsistent;   /* Info::rows_inconsistent / cols_inconsistent (0 / 1) */
+    ipxint updates_start;                          /* Info::updates_start: exchanges */
+    ipxint stability_pivots;                       /* of them: swaps of two free / two fixed variables */
+    ipxint factorizations;                         /* the slack basis and the final basis included */
+    double seconds;
+} ipxk_starting_basis_info;
+int ipxk_ipm_starting_basis(ipxk_context* ctx, const double* b, const double* c,
+                            const double* lb, const double* ub,
+                            const ipxk_starting_basis_params* params,
+                            ipxk_starting_basis_info* info, ipxint* basis_out,
+                            ipxint* status_out, ipxint* exchange_log, ipxint log_cap,
+                            ipxk_interrupt_fn interrupt, void* interrupt_user);
 
 /* ---- multi-GPU: rows of AI partitioned over ranks, one RCCL all-reduce per
  *      NormalMatrix apply ---------------------------- */

@@ -269,6 +269,7 @@ int ipxk_reset_solver_state(ipxk_context* c, double lu_pivottol) {
         // factors, N, the tightened pivot tolerance.  The buffers stay (grow-only workspaces); nothing of their content is used again.
         c->W = nullptr;
         c->normal_prepared = c->diag_factorized = c->kkt_diag_factorized = c->it_set = false;
+        c->sb_live = false;
         c->kdense = 0;
         if (c->split) {
             if (c->split_spare) destroy_split(c->split_spare);
@@ -592,6 +593,7 @@ int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const d
         if (!comm_cols(c)) IPXK_REQUIRE(args, "NULL argument");
         bind_device(c);
         c->it_set = false;
+        c->sb_live = false;                 // a starting basis belongs to the iterate it was built from
         const size_t m = (size_t)c->m, n = (size_t)c->n, N = (size_t)(c->n + c->m);
         DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
         const double* src[6] = {x, xl, xu, y, zl, zu};
@@ -771,7 +773,27 @@ int ipxk_ipm_starting_point(ipxk_context* c, const double* b, const double* cc, 
         const double* dc = stage_in(c, cc, N, c->nw_in[1]);
         const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
         const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        c->sb_live = false;
         ipm_starting_point_dev(c, db, dc, dlb, dub, params, info, interrupt, interrupt_user);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_ipm_starting_basis(ipxk_context* c, const double* b, const double* cc, const double* lb, const double* ub,
+                            const ipxk_starting_basis_params* params, ipxk_starting_basis_info* info, ipxint* basis_out,
+                            ipxint* status_out, ipxint* exchange_log, ipxint log_cap, ipxk_interrupt_fn interrupt,
+                            void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && b && cc && lb && ub && info, "NULL argument");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // it runs the device LU
+        IPXK_REQUIRE(log_cap >= 0 && (exchange_log || log_cap == 0), "exchange_log is NULL");
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* db = stage_in(c, b, m, c->nw_in[0]);
+        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        ipm_starting_basis_dev(c, db, dc, dlb, dub, params, info, basis_out, status_out, exchange_log, log_cap, interrupt, interrupt_user);
         IPXK_HIP(hipStreamSynchronize(c->stream));
     });
 }
@@ -785,6 +807,7 @@ int ipxk_ipm_load_starting_point(ipxk_context* c, const double* x, const double*
         IPXK_REQUIRE(args || comm_cols(c), "NULL argument");
         bind_device(c);
         c->it_set = false;
+        c->sb_live = false;                 // a starting basis belongs to the iterate it was built from
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         std::string err = args ? std::string() : std::string("NULL argument");
         if (!args) {

@@ -146,6 +146,11 @@ struct Context {
     MaxvolState* maxvol = nullptr;         // workspaces of ipxk_maxvolume (maxvolume.hip)
     bool etas_live = false;                // the operator `split` stands for a LATER basis than its factors: Maxvolume's last exchanges are applied as etas behind them (maxvolume.hip)
     NMatrix* nmat = nullptr;               // N of the split operator as a matrix of its own (nmatrix.hip)
+    // the factors, the operator and these statuses are the result of ipxk_ipm_starting_basis (starting_basis.hip): the main phase
+    // (ipm_driver_dev with use_basis) goes on from them instead of the slack basis
+    bool sb_live = false;
+    long sb_lu_generation = -1;            // of those factors: another factorization in the context ends the state
+    std::vector<ipxint> sb_basis, sb_status;
 
     // ---- multi-GPU ----
     ncclComm* comm = nullptr;
@@ -299,6 +304,13 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
 // column partition: fingerprint of b and the slack parts of c, lb, ub (device), what the ranks of the device IPM agree on
 uint64_t model_fingerprint(Context* c, const double* b, const double* cc, const double* lb, const double* ub);
 
+// ---- starting_basis.hip ----
+void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,
+                            const ipxk_starting_basis_params* prm, ipxk_starting_basis_info* info, ipxint* basis_out,
+                            ipxint* status_out, ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* user);
+// Iterate::ScalingFactor of every variable into d[n+m] (device); *nonbarrier (device) is set when a variable is fixed or free
+void iterate_scaling_factors_dev(Context* c, double* d, int* nonbarrier);
+
 // ---- start.hip ----
 // IPM::ComputeStartingPoint (the model vectors on the device; b, c, lb, ub checked) and IPM::LoadStartingPoint (the
 // six iterate vectors already copied into it_*; lb, ub on the device)
@@ -358,6 +370,10 @@ void maxvolume_sequential_dev(Context* c, const ipxint* status, const double* co
                               ipxint max_etas, ipxint* basis_out, ipxint* status_out, ipxk_maxvolume_info* info, ipxint* log,
                               ipxint log_cap);
 void destroy_maxvol(MaxvolState*);
+bool tighten_pivottol(double& pivottol);                            // Basis::TightenLuPivotTol; false at the top of the ladder
+void mv_scatter_column(Context* c, const MvScalars* S, double* rhs);       // rhs[m] = column S->jn of AI
+void mv_unit_vector(Context* c, const MvScalars* S, double* v);            // v[m] = e_(S->pmax)
+void mv_pivot_from_row(Context* c, const double* btran, MvScalars* S);     // S->pivot_row = btran' a_(S->jn)
 void maxvol_apply_etas(Context* c, bool transposed, double* v);     // v (by basis position) <- inverse(E_K ... E_1) v  /  its transpose
 const ipxint* maxvol_current_basis(Context* c);                     // device, by basis position: the basis factors + etas stand for
 void maxvol_drop_etas(Context* c);                                  // a new factorization / operator: the eta file is history

@@ -455,6 +455,82 @@ struct CrState {
     int mode;                            // CrMode of the run (cr.hip)
 };
 
+// ---------------------------------------------------------------------------
+// the basis exchanges of maxvolume.hip and starting_basis.hip
+// ---------------------------------------------------------------------------
+// the scalars of one exchange step, written by the device, read by the host
+struct MvScalars {
+    int jn;                  // FindLargest
+    double weight;
+    int pmax, jb;            // ScaleFtran
+    double vmax, weight_recomp, colscale_jn, invscale_pmax, pivot_col;
+    int used_pmax, eta_nnz;
+    double pivot_row;        // row[jn]
+    int eta_total;           // entries of all etas after the last exchange
+};
+
+struct MvPart { double v; int i; double s; int c; };     // per-workgroup partial of the reductions
+
+struct MaxvolState {
+    DevBuf<double> colscale, invscale, colweights, row, mask, rhs, lhs, unit, btran, work;
+    DevBuf<int> map2basis, slice_of, flag, rank, eta_ptr, eta_pos, eta_idx;
+    DevBuf<double> eta_piv, eta_val;
+    // the etas as dense vectors (mv_eta_dense_*): E [cap][m], T / Tt [cap][cap], multipliers, dots, links between the exchanges of a position
+    DevBuf<double> etaE, etaT, etaTt, eta_alpha, eta_d;
+    DevBuf<int> eta_prev, eta_next, eta_last;
+    DevBuf<double> etaF, etaG, eta_w;      // the triangular systems of a kept eta file as matrices (mv_eta_*_matrix_kernel)
+    DevBuf<int> eta_first, eta_jof;
+    DevBuf<ipxint> basis, status;
+    DevBuf<MvPart> part;
+    DevBuf<MvScalars> scalars;
+    DevBuf<unsigned char> tmp;
+    MvScalars* h = nullptr;    // pinned
+    // the eta file kept BEHIND the resident factors between two calls (Context::etas_live): what EtaFile needs to go on, and the basis
+    // the factors + etas represent (by basis position; the device copy is `basis`)
+    struct Saved {
+        bool live = false, dense = false, have_history = false;
+        int K = 0, cap = 0, m = 0;
+        int64_t sparse_used = 0, seg_nnz = 0;
+        double overhead_s = 0.0, refactor_s = 0.0;
+        long lu_generation = -1;       // of the factors the etas stand behind (a later factorization in the context: no resuming)
+        int Kd = 0;                    // > 0: etaF / etaG hold the matrices of the two triangular systems (Kd etas are the first at their position)
+    } saved;
+    std::vector<ipxint> basis_h;
+    ~MaxvolState() { if (h) (void)hipHostFree(h); }
+};
+
 struct Context;
+
+// The etas of the exchanges since the last refactorization (maxvolume.hip has the methods and what they cost)
+struct EtaFile {
+    Context* c;
+    MaxvolState& M;
+    int m;
+    hipStream_t s;
+    bool dense = false, dense_possible = false, adaptive = false;
+    int cap = 100;                 // most etas the buffers hold
+    int limit = 100;               // fixed mode: refactorize after so many
+    int64_t sparse_cap = 0, sparse_used = 0;
+    int K = 0;
+    double overhead_s = 0.0, refactor_s = 0.0;
+    int64_t seg_nnz = 0;           // entries of the etas of the current segment (decides the next segment's form)
+    bool have_history = false;
+    bool resumed = false;
+
+    // cost of one eta in one application (seconds): the list kernels spend two workgroup barriers and a dependent load per eta plus
+    // its entries through one workgroup; the dense form a barrier of the triangular solve plus the eta's row of E in the one pass
+    double cost_list(double nnz) const { return 2.5e-6 + 0.5e-9 * nnz; }
+    double cost_dense() const { return 0.6e-6 + 8.0 * (double)m / 2e12; }
+
+    EtaFile(Context* ctx, MaxvolState& state, int rows, ipxint max_etas_in, bool resume = false);
+    void save();
+    bool worth_keeping() const;
+    void reset(int block_rows);
+    // the eta of the exchange described by *S (pmax) from the tableau column lhs; eta_nnz: its number of nonzeros
+    void append(const MvScalars* S, const double* lhs, int eta_nnz);
+    bool full() const;
+    void apply(bool transposed, double* v);
+    static void apply_etas(MaxvolState& M, int m, int K, int cap, bool dense, bool transposed, double* v, hipStream_t s, int Kd = 0);
+};
 
 }  // namespace ipxk

@@ -187,11 +187,19 @@ __global__ void scaling_factor_kernel(int N, const unsigned char* __restrict__ s
     }
 }
 
+void iterate_scaling_factors_dev(Context* c, double* d, int* nonbarrier) {
+    const int N = (int)(c->n + c->m);
+    hipLaunchKernelGGL(scaling_factor_kernel, dim3(vec_grid(N)), dim3(kBlock), 0, c->stream, N, c->it_state.get(), c->it_xl.get(),
+                       c->it_xu.get(), c->it_zl.get(), c->it_zu.get(), d, nonbarrier);
+}
+
 // KKTSolverBasis::_Factorize (src/kkt_solver_basis.cc:20-63) on the device: scaling factors from the iterate,
 // Maxvolume, fresh factorization, Prepare.  DropPrimal / DropDual (:36-43) are not taken (they move nearly
 // degenerate variables out of the barrier problem; leaving them in is a valid, if slower, interior point step).
 // The first call builds the slack basis (Basis::SetToSlackBasis; ConstructBasisFromWeights with crash_basis = 0,
-// src/basis.cc:353-385, for a model without free or fixed variables).
+// src/basis.cc:353-385, for a model without free or fixed variables).  With a live starting basis
+// (ipxk_ipm_starting_basis) there is no first call: basis and status are its result, fixed and free variables
+// keep their scaling factors 0 and inf, and Maxvolume and Prepare carry BASIC_FREE / NONBASIC_FIXED along.
 static void basis_factorize_dev(Context* c, std::vector<ipxint>& basis, std::vector<ipxint>& status, std::vector<double>& colscale,
                                 bool first, ipxk_ipm_info* info) {
     const int m = (int)c->m, n = (int)c->n, N = n + m;
@@ -199,13 +207,12 @@ static void basis_factorize_dev(Context* c, std::vector<ipxint>& basis, std::vec
     DevBuf<double> d((size_t)N);
     DevBuf<int> flag(1);
     IPXK_HIP(hipMemsetAsync(flag.get(), 0, sizeof(int), s));
-    hipLaunchKernelGGL(scaling_factor_kernel, dim3(vec_grid(N)), dim3(kBlock), 0, s, N, c->it_state.get(), c->it_xl.get(), c->it_xu.get(),
-                       c->it_zl.get(), c->it_zu.get(), d.get(), flag.get());
+    iterate_scaling_factors_dev(c, d.get(), flag.get());
     int nonbarrier = 0;
     flag.download(&nonbarrier, 1, s);
     d.download(colscale.data(), (size_t)N, s);
     IPXK_HIP(hipStreamSynchronize(s));
-    if (nonbarrier) throw Error(IPXK_E_UNSUPPORTED, "the basis phase of ipxk_ipm_driver handles barrier variables only (no free or fixed ones)");
+    if (nonbarrier && !c->sb_live) throw Error(IPXK_E_UNSUPPORTED, "the basis phase of ipxk_ipm_driver handles barrier variables only (no free or fixed ones)");
     if (first) {
         for (int j = 0; j < n; j++) status[j] = IPXK_NONBASIC;
         for (int i = 0; i < m; i++) { status[n + i] = IPXK_BASIC; basis[i] = n + i; }
@@ -272,6 +279,9 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     std::vector<double> colscale;
     if (use_basis) { basis.resize((size_t)c->m); status.resize((size_t)(c->n + c->m)); colscale.resize((size_t)(c->n + c->m)); }
     bool first_factorize = true;
+    if (use_basis && c->sb_live && c->sb_lu_generation != lu_generation(c)) c->sb_live = false;    // the factors are no longer its
+    const bool from_starting_basis = use_basis && c->sb_live;
+    if (from_starting_basis) { basis = c->sb_basis; status = c->sb_status; first_factorize = false; }
     constexpr double kDivergeTol = 1e6;                  // src/ipm.h:55
     *info = ipxk_ipm_info{};
     const int N = (int)(c->n + c->m);
@@ -331,6 +341,11 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     if (errflag) {                                       // :114-121
         if (errflag == 999) { info->status_ipm = 5; info->errflag = 0; }           // IPX_ERROR_interrupt_time -> time_limit
         else { info->status_ipm = 8; info->errflag = errflag; }                    // failed
+    }
+    if (from_starting_basis) {
+        // a later call goes on from the basis this one ended with -- unless it ended inside a Factorize
+        c->sb_live = info->errflag == 0 && info->status_ipm != 8;
+        if (c->sb_live) { c->sb_basis = basis; c->sb_status = status; c->sb_lu_generation = lu_generation(c); }
     }
     if (use_basis && !first_factorize) {
         if (basis_out) std::copy(basis.begin(), basis.end(), basis_out);

@@ -46,18 +46,8 @@ constexpr double kPivotZeroTol = 1e-7;   // src/maxvolume.h:34
 int grid_for(int64_t n) { return (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
 #define IPXK_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
-// the scalars of one step, written by the device, read by the host
-struct Scalars {
-    int jn;                  // FindLargest
-    double weight;
-    int pmax, jb;            // ScaleFtran
-    double vmax, weight_recomp, colscale_jn, invscale_pmax, pivot_col;
-    int used_pmax, eta_nnz;
-    double pivot_row;        // row[jn]
-    int eta_total;           // entries of all etas after the last exchange
-};
-
-struct Part { double v; int i; double s; int c; };     // per-workgroup partial of the reductions
+using Scalars = MvScalars;     // the scalars of one step (internal.hpp)
+using Part = MvPart;
 
 // ---- FindLargest (src/maxvolume.cc:179-200): first index of the largest |w| ----------------------------------
 __global__ __launch_bounds__(kBlock) void mv_argmax_kernel(int64_t N, const double* __restrict__ w, Part* part) {
@@ -660,33 +650,6 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 
 }  // namespace
 
-struct MaxvolState {
-    DevBuf<double> colscale, invscale, colweights, row, mask, rhs, lhs, unit, btran, work;
-    DevBuf<int> map2basis, slice_of, flag, rank, eta_ptr, eta_pos, eta_idx;
-    DevBuf<double> eta_piv, eta_val;
-    // the etas as dense vectors (mv_eta_dense_*): E [cap][m], T / Tt [cap][cap], multipliers, dots, links between the exchanges of a position
-    DevBuf<double> etaE, etaT, etaTt, eta_alpha, eta_d;
-    DevBuf<int> eta_prev, eta_next, eta_last;
-    DevBuf<double> etaF, etaG, eta_w;      // the triangular systems of a kept eta file as matrices (mv_eta_*_matrix_kernel)
-    DevBuf<int> eta_first, eta_jof;
-    DevBuf<ipxint> basis, status;
-    DevBuf<Part> part;
-    DevBuf<Scalars> scalars;
-    DevBuf<unsigned char> tmp;
-    Scalars* h = nullptr;      // pinned
-    // the eta file kept BEHIND the resident factors between two calls (Context::etas_live): what EtaFile needs to go on, and the basis
-    // the factors + etas represent (by basis position; the device copy is `basis`)
-    struct Saved {
-        bool live = false, dense = false, have_history = false;
-        int K = 0, cap = 0, m = 0;
-        int64_t sparse_used = 0, seg_nnz = 0;
-        double overhead_s = 0.0, refactor_s = 0.0;
-        long lu_generation = -1;       // of the factors the etas stand behind (a later factorization in the context: no resuming)
-        int Kd = 0;                    // > 0: etaF / etaG hold the matrices of the two triangular systems (Kd etas are the first at their position)
-    } saved;
-    std::vector<ipxint> basis_h;
-    ~MaxvolState() { if (h) (void)hipHostFree(h); }
-};
 void destroy_maxvol(MaxvolState* M) { delete M; }
 
 // The etas of the exchanges since the last refactorization (both Maxvolume variants): dense rows (mv_eta_dense_*) where the
@@ -698,179 +661,180 @@ void destroy_maxvol(MaxvolState* M) { delete M; }
 // 0.16 s at 7350 rows, 1.2 s at 15 000), an application of K etas K x (0.6 us + 8 m bytes at 2 TB/s), three applications per
 // exchange; at least 100, at most 1024 etas.  (Measured on the 24 000 x 60 000 LP: 40 refactorizations of 0.15 s inside
 // Maxvolume with the fixed limit of 100.)
-struct EtaFile {
-    Context* c;
-    MaxvolState& M;
-    int m;
-    hipStream_t s;
-    bool dense = false, dense_possible = false, adaptive = false;
-    int cap = 100;                 // most etas the buffers hold
-    int limit = 100;               // fixed mode: refactorize after so many
-    int64_t sparse_cap = 0, sparse_used = 0;
-    int K = 0;
-    double overhead_s = 0.0, refactor_s = 0.0;
-    int64_t seg_nnz = 0;           // entries of the etas of the current segment (decides the next segment's form)
-    bool have_history = false;
-
-    // cost of one eta in one application (seconds): the list kernels spend two workgroup barriers and a dependent load per eta plus
-    // its entries through one workgroup; the dense form a barrier of the triangular solve plus the eta's row of E in the one pass
-    double cost_list(double nnz) const { return 2.5e-6 + 0.5e-9 * nnz; }
-    double cost_dense() const { return 0.6e-6 + 8.0 * (double)m / 2e12; }
-
-    EtaFile(Context* ctx, MaxvolState& state, int rows, ipxint max_etas_in, bool resume = false) : c(ctx), M(state), m(rows), s(ctx->stream) {
-        adaptive = max_etas_in < 0;
-        limit = (int)std::max<ipxint>(1, max_etas_in > 0 ? max_etas_in : 100);
-        static const bool dense_off = getenv("IPXK_MAXVOL_DENSE_ETAS") && getenv("IPXK_MAXVOL_DENSE_ETAS")[0] == '0';
-        const int64_t fit = (int64_t(1) << 28) / std::max(m, 1);                   // 2 GiB of etas
-        cap = adaptive ? (int)std::min<int64_t>(kEtaDenseMax, std::max<int64_t>(limit, fit)) : limit;
-        dense_possible = !dense_off && cap <= kEtaDenseMax && (int64_t)cap <= std::max<int64_t>(fit, 1);
-        if (!dense_possible) { cap = limit; adaptive = false; }
-        sparse_cap = std::max<int64_t>(4 * (int64_t)m, int64_t(1) << 20);
-        M.eta_pos.ensure((size_t)cap); M.eta_piv.ensure((size_t)cap);
-        const MaxvolState::Saved& sv = M.saved;
-        if (resume && sv.live && sv.cap == cap && sv.m == m && (sv.dense ? dense_possible : true)) {
-            // the etas of the previous call are still behind the factors: go on where it stopped
-            dense = sv.dense; have_history = sv.have_history; K = sv.K; sparse_used = sv.sparse_used; seg_nnz = sv.seg_nnz;
-            overhead_s = sv.overhead_s; refactor_s = sv.refactor_s;
-            resumed = true;
-        } else {
-            reset(0);
-        }
+// (the struct itself: internal.hpp -- the starting basis, starting_basis.hip, keeps its exchanges in the same file)
+EtaFile::EtaFile(Context* ctx, MaxvolState& state, int rows, ipxint max_etas_in, bool resume) : c(ctx), M(state), m(rows), s(ctx->stream) {
+    adaptive = max_etas_in < 0;
+    limit = (int)std::max<ipxint>(1, max_etas_in > 0 ? max_etas_in : 100);
+    static const bool dense_off = getenv("IPXK_MAXVOL_DENSE_ETAS") && getenv("IPXK_MAXVOL_DENSE_ETAS")[0] == '0';
+    const int64_t fit = (int64_t(1) << 28) / std::max(m, 1);                   // 2 GiB of etas
+    cap = adaptive ? (int)std::min<int64_t>(kEtaDenseMax, std::max<int64_t>(limit, fit)) : limit;
+    dense_possible = !dense_off && cap <= kEtaDenseMax && (int64_t)cap <= std::max<int64_t>(fit, 1);
+    if (!dense_possible) { cap = limit; adaptive = false; }
+    sparse_cap = std::max<int64_t>(4 * (int64_t)m, int64_t(1) << 20);
+    M.eta_pos.ensure((size_t)cap); M.eta_piv.ensure((size_t)cap);
+    const MaxvolState::Saved& sv = M.saved;
+    if (resume && sv.live && sv.cap == cap && sv.m == m && (sv.dense ? dense_possible : true)) {
+        // the etas of the previous call are still behind the factors: go on where it stopped
+        dense = sv.dense; have_history = sv.have_history; K = sv.K; sparse_used = sv.sparse_used; seg_nnz = sv.seg_nnz;
+        overhead_s = sv.overhead_s; refactor_s = sv.refactor_s;
+        resumed = true;
+    } else {
+        reset(0);
     }
-    bool resumed = false;
-    void save() {
-        MaxvolState::Saved& sv = M.saved;
-        sv.live = true; sv.dense = dense; sv.have_history = have_history; sv.K = K; sv.cap = cap; sv.m = m; sv.sparse_used = sparse_used;
-        sv.seg_nnz = seg_nnz; sv.overhead_s = overhead_s; sv.refactor_s = refactor_s;
-        sv.lu_generation = lu_generation(c);
-        sv.Kd = 0;
-        static const bool matrices_off = getenv("IPXK_MAXVOL_ETA_MATRICES") && getenv("IPXK_MAXVOL_ETA_MATRICES")[0] == '0';
-        if (dense && K > 0 && !matrices_off) {
-            // the two triangular systems as matrices, for the applications inside the KKT solve (mv_eta_*_matrix_kernel)
-            std::vector<int> prev_h((size_t)K), pos_h((size_t)K), first, jof((size_t)K, -1);
-            M.eta_prev.download(prev_h.data(), (size_t)K, s);
-            M.eta_pos.download(pos_h.data(), (size_t)K, s);
-            IPXK_HIP(hipStreamSynchronize(s));
-            for (int t = 0; t < K; t++) {
-                if (prev_h[t] < 0) { jof[t] = (int)first.size(); first.push_back(t); }
-                else jof[t] = jof[prev_h[t]];
-            }
-            const int Kd = (int)first.size();
-            M.eta_first.upload(first, s); M.eta_jof.upload(jof, s);
-            M.etaF.ensure((size_t)K * Kd); M.etaG.ensure((size_t)K * (K + Kd)); M.eta_w.ensure((size_t)K);
-            hipLaunchKernelGGL(mv_eta_forward_matrix_kernel, dim3(Kd), dim3(std::min(kEtaDenseMax, (K + 63) / 64 * 64)), 0, s, K, Kd, cap, M.eta_first.get(), M.eta_piv.get(),
-                               M.eta_prev.get(), M.etaTt.get(), M.etaF.get());
-            hipLaunchKernelGGL(mv_eta_backward_matrix_kernel, dim3(K + Kd), dim3(std::min(kEtaDenseMax, (K + 63) / 64 * 64)), 0, s, K, Kd, cap, M.eta_jof.get(), M.eta_piv.get(),
-                               M.eta_prev.get(), M.eta_next.get(), M.etaT.get(), M.etaG.get());
-            IPXK_HIP(hipStreamSynchronize(s));               // (the host vectors go out of scope)
-            IPXK_HIP(hipGetLastError());
-            sv.Kd = Kd;
+}
+void EtaFile::save() {
+    MaxvolState::Saved& sv = M.saved;
+    sv.live = true; sv.dense = dense; sv.have_history = have_history; sv.K = K; sv.cap = cap; sv.m = m; sv.sparse_used = sparse_used;
+    sv.seg_nnz = seg_nnz; sv.overhead_s = overhead_s; sv.refactor_s = refactor_s;
+    sv.lu_generation = lu_generation(c);
+    sv.Kd = 0;
+    static const bool matrices_off = getenv("IPXK_MAXVOL_ETA_MATRICES") && getenv("IPXK_MAXVOL_ETA_MATRICES")[0] == '0';
+    if (dense && K > 0 && !matrices_off) {
+        // the two triangular systems as matrices, for the applications inside the KKT solve (mv_eta_*_matrix_kernel)
+        std::vector<int> prev_h((size_t)K), pos_h((size_t)K), first, jof((size_t)K, -1);
+        M.eta_prev.download(prev_h.data(), (size_t)K, s);
+        M.eta_pos.download(pos_h.data(), (size_t)K, s);
+        IPXK_HIP(hipStreamSynchronize(s));
+        for (int t = 0; t < K; t++) {
+            if (prev_h[t] < 0) { jof[t] = (int)first.size(); first.push_back(t); }
+            else jof[t] = jof[prev_h[t]];
         }
+        const int Kd = (int)first.size();
+        M.eta_first.upload(first, s); M.eta_jof.upload(jof, s);
+        M.etaF.ensure((size_t)K * Kd); M.etaG.ensure((size_t)K * (K + Kd)); M.eta_w.ensure((size_t)K);
+        hipLaunchKernelGGL(mv_eta_forward_matrix_kernel, dim3(Kd), dim3(std::min(kEtaDenseMax, (K + 63) / 64 * 64)), 0, s, K, Kd, cap, M.eta_first.get(), M.eta_piv.get(),
+                           M.eta_prev.get(), M.etaTt.get(), M.etaF.get());
+        hipLaunchKernelGGL(mv_eta_backward_matrix_kernel, dim3(K + Kd), dim3(std::min(kEtaDenseMax, (K + 63) / 64 * 64)), 0, s, K, Kd, cap, M.eta_jof.get(), M.eta_piv.get(),
+                           M.eta_prev.get(), M.eta_next.get(), M.etaT.get(), M.etaG.get());
+        IPXK_HIP(hipStreamSynchronize(s));               // (the host vectors go out of scope)
+        IPXK_HIP(hipGetLastError());
+        sv.Kd = Kd;
     }
-    // what the K etas cost in the solves of one KKT solve (~ 100 CR iterations, one application per direction and iteration, a few dense
-    // solves around them) against what a refactorization costs: whether the etas stay behind the factors when Maxvolume is over
-    bool worth_keeping() const {
-        if (K == 0 || full()) return false;
-        // (dense form: the triangular systems go through their matrices inside the KKT solve -- what is left per eta is its row of E)
-        const double per_eta = dense ? 8.0 * (double)m / 2e12 + 0.05e-6 : cost_list(K > 0 ? (double)seg_nnz / K : 0.0);
-        return 220.0 * ((double)K * per_eta + 40e-6) < refactor_s;          // (40 us: the seven extra launches of an application)
+}
+// what the K etas cost in the solves of one KKT solve (~ 100 CR iterations, one application per direction and iteration, a few dense
+// solves around them) against what a refactorization costs: whether the etas stay behind the factors when Maxvolume is over
+bool EtaFile::worth_keeping() const {
+    if (K == 0 || full()) return false;
+    // (dense form: the triangular systems go through their matrices inside the KKT solve -- what is left per eta is its row of E)
+    const double per_eta = dense ? 8.0 * (double)m / 2e12 + 0.05e-6 : cost_list(K > 0 ? (double)seg_nnz / K : 0.0);
+    return 220.0 * ((double)K * per_eta + 40e-6) < refactor_s;          // (40 us: the seven extra launches of an application)
+}
+// after a (re)factorization whose dense block has `block_rows` rows: the next segment's etas as dense rows or as lists, whichever
+// the previous segment's etas would have cost less in (no segment yet: from m alone -- the lists only pay beyond ~ 475 000 rows)
+void EtaFile::reset(int block_rows) {
+    if (dense_possible) {
+        const double avg = have_history && K > 0 ? (double)seg_nnz / K : 0.0;
+        dense = cost_dense() < cost_list(avg);
+        static const bool force = getenv("IPXK_MAXVOL_DENSE_ETAS") && getenv("IPXK_MAXVOL_DENSE_ETAS")[0] == '1';
+        if (force) dense = true;
+    } else {
+        dense = false;
     }
-    // after a (re)factorization whose dense block has `block_rows` rows: the next segment's etas as dense rows or as lists, whichever
-    // the previous segment's etas would have cost less in (no segment yet: from m alone -- the lists only pay beyond ~ 475 000 rows)
-    void reset(int block_rows) {
-        if (dense_possible) {
-            const double avg = have_history && K > 0 ? (double)seg_nnz / K : 0.0;
-            dense = cost_dense() < cost_list(avg);
-            static const bool force = getenv("IPXK_MAXVOL_DENSE_ETAS") && getenv("IPXK_MAXVOL_DENSE_ETAS")[0] == '1';
-            if (force) dense = true;
-        } else {
-            dense = false;
-        }
-        if (K > 0) have_history = true;
-        K = 0;
-        sparse_used = 0;
-        seg_nnz = 0;
-        overhead_s = 0.0;
-        refactor_s = 0.025 + 3.5e-13 * (double)block_rows * (double)block_rows * (double)block_rows;
-        if (dense) {
-            M.etaE.ensure((size_t)cap * m); M.etaT.ensure((size_t)cap * cap); M.etaTt.ensure((size_t)cap * cap);
-            M.eta_alpha.ensure((size_t)cap); M.eta_d.ensure((size_t)cap);
-            M.eta_prev.ensure((size_t)cap); M.eta_next.ensure((size_t)cap);
-            M.eta_last.ensure((size_t)m);
-            IPXK_HIP(hipMemsetAsync(M.eta_last.get(), 0xff, (size_t)m * sizeof(int), s));
-        } else {
-            M.flag.ensure((size_t)m); M.rank.ensure((size_t)m);
-            M.eta_ptr.ensure((size_t)cap + 1);
-            M.eta_idx.ensure((size_t)sparse_cap + m); M.eta_val.ensure((size_t)sparse_cap + m);
-            IPXK_HIP(hipMemsetAsync(M.eta_ptr.get(), 0, sizeof(int), s));
-        }
+    if (K > 0) have_history = true;
+    K = 0;
+    sparse_used = 0;
+    seg_nnz = 0;
+    overhead_s = 0.0;
+    refactor_s = 0.025 + 3.5e-13 * (double)block_rows * (double)block_rows * (double)block_rows;
+    if (dense) {
+        M.etaE.ensure((size_t)cap * m); M.etaT.ensure((size_t)cap * cap); M.etaTt.ensure((size_t)cap * cap);
+        M.eta_alpha.ensure((size_t)cap); M.eta_d.ensure((size_t)cap);
+        M.eta_prev.ensure((size_t)cap); M.eta_next.ensure((size_t)cap);
+        M.eta_last.ensure((size_t)m);
+        IPXK_HIP(hipMemsetAsync(M.eta_last.get(), 0xff, (size_t)m * sizeof(int), s));
+    } else {
+        M.flag.ensure((size_t)m); M.rank.ensure((size_t)m);
+        M.eta_ptr.ensure((size_t)cap + 1);
+        M.eta_idx.ensure((size_t)sparse_cap + m); M.eta_val.ensure((size_t)sparse_cap + m);
+        IPXK_HIP(hipMemsetAsync(M.eta_ptr.get(), 0, sizeof(int), s));
     }
-    // the eta of the exchange described by *S (pmax) from the tableau column lhs; eta_nnz: its number of nonzeros
-    void append(const Scalars* S, const double* lhs, int eta_nnz) {
-        const int gm = grid_for(m);
-        if (dense) {
-            hipLaunchKernelGGL(mv_eta_dense_append_kernel, dim3(gm), dim3(kBlock), 0, s, m, K, cap, S, lhs, M.etaE.get(), M.eta_pos.get(), M.eta_piv.get(),
-                               M.eta_prev.get(), M.eta_next.get(), M.eta_last.get(), M.etaT.get(), M.etaTt.get());
-        } else {
-            hipLaunchKernelGGL(mv_eta_flag_kernel, dim3(gm), dim3(kBlock), 0, s, m, S, lhs, M.flag.get());
-            size_t bytes = 0;
-            IPXK_HIP(rocprim::exclusive_scan(nullptr, bytes, M.flag.get(), M.rank.get(), 0, (size_t)m, rocprim::plus<int>(), s));
-            if (M.tmp.size() < bytes) M.tmp.resize(bytes);
-            IPXK_HIP(rocprim::exclusive_scan(M.tmp.get(), bytes, M.flag.get(), M.rank.get(), 0, (size_t)m, rocprim::plus<int>(), s));
-            hipLaunchKernelGGL(mv_eta_store_kernel, dim3(gm), dim3(kBlock), 0, s, m, K, S, lhs, M.flag.get(), M.rank.get(), M.eta_ptr.get(), M.eta_pos.get(),
-                               M.eta_piv.get(), M.eta_idx.get(), M.eta_val.get(), M.scalars.get());
-            sparse_used += eta_nnz;
-        }
-        K++;
-        seg_nnz += eta_nnz;
-        overhead_s += 3.0 * (dense ? (double)K * cost_dense() : (double)K * 2.5e-6 + 0.5e-9 * (double)seg_nnz);
+}
+// the eta of the exchange described by *S (pmax) from the tableau column lhs; eta_nnz: its number of nonzeros
+void EtaFile::append(const MvScalars* S, const double* lhs, int eta_nnz) {
+    const int gm = grid_for(m);
+    if (dense) {
+        hipLaunchKernelGGL(mv_eta_dense_append_kernel, dim3(gm), dim3(kBlock), 0, s, m, K, cap, S, lhs, M.etaE.get(), M.eta_pos.get(), M.eta_piv.get(),
+                           M.eta_prev.get(), M.eta_next.get(), M.eta_last.get(), M.etaT.get(), M.etaTt.get());
+    } else {
+        hipLaunchKernelGGL(mv_eta_flag_kernel, dim3(gm), dim3(kBlock), 0, s, m, S, lhs, M.flag.get());
+        size_t bytes = 0;
+        IPXK_HIP(rocprim::exclusive_scan(nullptr, bytes, M.flag.get(), M.rank.get(), 0, (size_t)m, rocprim::plus<int>(), s));
+        if (M.tmp.size() < bytes) M.tmp.resize(bytes);
+        IPXK_HIP(rocprim::exclusive_scan(M.tmp.get(), bytes, M.flag.get(), M.rank.get(), 0, (size_t)m, rocprim::plus<int>(), s));
+        hipLaunchKernelGGL(mv_eta_store_kernel, dim3(gm), dim3(kBlock), 0, s, m, K, S, lhs, M.flag.get(), M.rank.get(), M.eta_ptr.get(), M.eta_pos.get(),
+                           M.eta_piv.get(), M.eta_idx.get(), M.eta_val.get(), M.scalars.get());
+        sparse_used += eta_nnz;
     }
-    bool full() const {                                                             // NeedFreshFactorization (src/maxvolume.cc:318-319)
-        if (K >= cap) return true;
-        if (!dense && sparse_used + m > sparse_cap) return true;
-        if (adaptive) return K >= 100 && overhead_s >= refactor_s;
-        return K >= limit;
-    }
-    void apply(bool transposed, double* v) { apply_etas(M, m, K, cap, dense, transposed, v, s); }
-    // Kd > 0: the triangular systems through their matrices (a kept file inside the KKT solve); 0: the sequential, bit-reproducible form
-    static void apply_etas(MaxvolState& M, int m, int K, int cap, bool dense, bool transposed, double* v, hipStream_t s, int Kd = 0) {
-        if (K == 0) return;
-        if (dense && Kd > 0) {
-            const int gk = (K + kBlock / 64 - 1) / (kBlock / 64);
-            if (transposed) {
-                hipLaunchKernelGGL(mv_eta_dense_dots_kernel, dim3(K), dim3(kBlock), 0, s, m, M.etaE.get(), v, M.eta_d.get());
-                hipLaunchKernelGGL(mv_eta_backward_gemv_kernel, dim3(gk), dim3(kBlock), 0, s, K, Kd, M.etaG.get(), M.eta_first.get(), M.eta_pos.get(),
-                                   M.eta_d.get(), v, M.eta_w.get());
-                hipLaunchKernelGGL(mv_eta_backward_scatter_kernel, dim3(grid_for(Kd)), dim3(kBlock), 0, s, Kd, M.eta_first.get(), M.eta_pos.get(),
-                                   M.eta_w.get(), v);
-            } else {
-                hipLaunchKernelGGL(mv_eta_forward_gemv_kernel, dim3(gk), dim3(kBlock), 0, s, K, Kd, M.etaF.get(), M.eta_first.get(), M.eta_pos.get(), v,
-                                   M.eta_alpha.get());
-                hipLaunchKernelGGL(mv_eta_dense_ftran_apply_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, K, M.etaE.get(), M.eta_alpha.get(),
-                                   M.eta_last.get(), v);
-            }
-            return;
-        }
-        // (the one-workgroup solves: only as many wavefronts as there are etas -- their two barriers per eta cost by the wavefront)
-        const int solve_threads = std::min(kEtaDenseMax, (K + 63) / 64 * 64);
-        if (dense && transposed) {
+    K++;
+    seg_nnz += eta_nnz;
+    overhead_s += 3.0 * (dense ? (double)K * cost_dense() : (double)K * 2.5e-6 + 0.5e-9 * (double)seg_nnz);
+}
+bool EtaFile::full() const {                                                             // NeedFreshFactorization (src/maxvolume.cc:318-319)
+    if (K >= cap) return true;
+    if (!dense && sparse_used + m > sparse_cap) return true;
+    if (adaptive) return K >= 100 && overhead_s >= refactor_s;
+    return K >= limit;
+}
+void EtaFile::apply(bool transposed, double* v) { apply_etas(M, m, K, cap, dense, transposed, v, s); }
+// Kd > 0: the triangular systems through their matrices (a kept file inside the KKT solve); 0: the sequential, bit-reproducible form
+void EtaFile::apply_etas(MaxvolState& M, int m, int K, int cap, bool dense, bool transposed, double* v, hipStream_t s, int Kd) {
+    if (K == 0) return;
+    if (dense && Kd > 0) {
+        const int gk = (K + kBlock / 64 - 1) / (kBlock / 64);
+        if (transposed) {
             hipLaunchKernelGGL(mv_eta_dense_dots_kernel, dim3(K), dim3(kBlock), 0, s, m, M.etaE.get(), v, M.eta_d.get());
-            hipLaunchKernelGGL(mv_eta_dense_btran_solve_kernel, dim3(1), dim3(solve_threads), 0, s, K, cap, v, M.eta_pos.get(), M.eta_piv.get(),
-                               M.eta_prev.get(), M.eta_next.get(), M.etaT.get(), M.eta_d.get());
-        } else if (dense) {
-            hipLaunchKernelGGL(mv_eta_dense_ftran_solve_kernel, dim3(1), dim3(solve_threads), 0, s, K, cap, v, M.eta_pos.get(), M.eta_piv.get(),
-                               M.eta_prev.get(), M.etaTt.get(), M.eta_alpha.get());
+            hipLaunchKernelGGL(mv_eta_backward_gemv_kernel, dim3(gk), dim3(kBlock), 0, s, K, Kd, M.etaG.get(), M.eta_first.get(), M.eta_pos.get(),
+                               M.eta_d.get(), v, M.eta_w.get());
+            hipLaunchKernelGGL(mv_eta_backward_scatter_kernel, dim3(grid_for(Kd)), dim3(kBlock), 0, s, Kd, M.eta_first.get(), M.eta_pos.get(),
+                               M.eta_w.get(), v);
+        } else {
+            hipLaunchKernelGGL(mv_eta_forward_gemv_kernel, dim3(gk), dim3(kBlock), 0, s, K, Kd, M.etaF.get(), M.eta_first.get(), M.eta_pos.get(), v,
+                               M.eta_alpha.get());
             hipLaunchKernelGGL(mv_eta_dense_ftran_apply_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, K, M.etaE.get(), M.eta_alpha.get(),
                                M.eta_last.get(), v);
-        } else if (transposed) {
-            hipLaunchKernelGGL(mv_eta_btran_kernel, dim3(1), dim3(kEtaThreads), 0, s, K, M.eta_ptr.get(), M.eta_pos.get(), M.eta_piv.get(), M.eta_idx.get(),
-                               M.eta_val.get(), v);
-        } else {
-            hipLaunchKernelGGL(mv_eta_ftran_kernel, dim3(1), dim3(kEtaThreads), 0, s, K, M.eta_ptr.get(), M.eta_pos.get(), M.eta_piv.get(), M.eta_idx.get(),
-                               M.eta_val.get(), v);
         }
+        return;
     }
-};
+    // (the one-workgroup solves: only as many wavefronts as there are etas -- their two barriers per eta cost by the wavefront)
+    const int solve_threads = std::min(kEtaDenseMax, (K + 63) / 64 * 64);
+    if (dense && transposed) {
+        hipLaunchKernelGGL(mv_eta_dense_dots_kernel, dim3(K), dim3(kBlock), 0, s, m, M.etaE.get(), v, M.eta_d.get());
+        hipLaunchKernelGGL(mv_eta_dense_btran_solve_kernel, dim3(1), dim3(solve_threads), 0, s, K, cap, v, M.eta_pos.get(), M.eta_piv.get(),
+                           M.eta_prev.get(), M.eta_next.get(), M.etaT.get(), M.eta_d.get());
+    } else if (dense) {
+        hipLaunchKernelGGL(mv_eta_dense_ftran_solve_kernel, dim3(1), dim3(solve_threads), 0, s, K, cap, v, M.eta_pos.get(), M.eta_piv.get(),
+                           M.eta_prev.get(), M.etaTt.get(), M.eta_alpha.get());
+        hipLaunchKernelGGL(mv_eta_dense_ftran_apply_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, K, M.etaE.get(), M.eta_alpha.get(),
+                           M.eta_last.get(), v);
+    } else if (transposed) {
+        hipLaunchKernelGGL(mv_eta_btran_kernel, dim3(1), dim3(kEtaThreads), 0, s, K, M.eta_ptr.get(), M.eta_pos.get(), M.eta_piv.get(), M.eta_idx.get(),
+                           M.eta_val.get(), v);
+    } else {
+        hipLaunchKernelGGL(mv_eta_ftran_kernel, dim3(1), dim3(kEtaThreads), 0, s, K, M.eta_ptr.get(), M.eta_pos.get(), M.eta_piv.get(), M.eta_idx.get(),
+                           M.eta_val.get(), v);
+    }
+}
+
+// Basis::TightenLuPivotTol (src/basis.cc:490-503): the next step of the reference's ladder, false at its top
+bool tighten_pivottol(double& pivottol) {
+    if (pivottol <= 0.05) pivottol = 0.1;
+    else if (pivottol <= 0.25) pivottol = 0.3;
+    else if (pivottol <= 0.5) pivottol = 0.9;
+    else return false;
+    return true;
+}
+
+// the small kernels of an exchange that starting_basis.hip launches too
+void mv_scatter_column(Context* c, const MvScalars* S, double* rhs) {
+    IPXK_HIP(hipMemsetAsync(rhs, 0, (size_t)c->m * sizeof(double), c->stream));
+    hipLaunchKernelGGL(mv_scatter_column_kernel, dim3(4), dim3(kBlock), 0, c->stream, (int)c->n, S, c->pl_Ap.get(), c->pl_Ai.get(), c->pl_Ax.get(), rhs);
+}
+void mv_unit_vector(Context* c, const MvScalars* S, double* v) {
+    hipLaunchKernelGGL(mv_unit_kernel, dim3(grid_for(c->m)), dim3(kBlock), 0, c->stream, (int)c->m, S, v);
+}
+void mv_pivot_from_row(Context* c, const double* btran, MvScalars* S) {
+    hipLaunchKernelGGL(mvs_pivot_row_kernel, dim3(1), dim3(kBlock), 0, c->stream, (int)c->n, c->pl_Ap.get(), c->pl_Ai.get(), c->pl_Ax.get(), btran, S);
+}
 
 // ---- the etas behind the resident factors (Context::etas_live) -------------------------------------------------------------
 // When Maxvolume is over and its last exchanges are few, the fresh factorization of the final basis that the reference asks for
@@ -983,13 +947,6 @@ void maxvolume_dev(Context* c, const ipxint* status_in, const double* colscale_i
     auto apply_etas = [&](bool transposed, double* v) { etas.apply(transposed, v); };
     // the reference's ladder for the LU pivot tolerance (Basis::TightenLuPivotTol, src/basis.cc:490-503); the value is the context's
     double& pivottol = c->maxvol_pivottol;
-    auto tighten_pivottol = [&]() {
-        if (pivottol <= 0.05) pivottol = 0.1;
-        else if (pivottol <= 0.25) pivottol = 0.3;
-        else if (pivottol <= 0.5) pivottol = 0.9;
-        else return false;
-        return true;
-    };
     auto refactorize = [&]() {                   // Basis::Factorize (src/basis.cc:116-156) + the operator of the sweeps
         ipxk_lu_info li{};
         lu_factorize_basis(c, basis_h.data(), pivottol, false, &li);
@@ -1059,7 +1016,7 @@ void maxvolume_dev(Context* c, const ipxint* status_in, const double* colscale_i
                 // Basis::ExchangeIfStable (src/basis.cc:299-306): on fresh factors the pivot tolerance is tightened
                 // first, and only when that is no longer possible the basis is declared too ill conditioned
                 I.refused++;
-                if (K == 0 && !tighten_pivottol()) { I.errflag = 306; break; }      // IPX_ERROR_basis_too_ill_conditioned
+                if (K == 0 && !tighten_pivottol(pivottol)) { I.errflag = 306; break; }      // IPX_ERROR_basis_too_ill_conditioned
                 if (!refactorize()) break;
                 continue;                                                           // "try again" (:290-291)
             }
@@ -1164,13 +1121,6 @@ void maxvolume_sequential_dev(Context* c, const ipxint* status_in, const double*
     lu_plain_matrix(c, &Ap, &Ai, &Ax);
     ipxk_maxvolume_info I{};
     double& pivottol = c->maxvol_pivottol;
-    auto tighten_pivottol = [&]() {                   // Basis::TightenLuPivotTol, src/basis.cc:490-503
-        if (pivottol <= 0.05) pivottol = 0.1;
-        else if (pivottol <= 0.25) pivottol = 0.3;
-        else if (pivottol <= 0.5) pivottol = 0.9;
-        else return false;
-        return true;
-    };
     auto apply_etas = [&](bool transposed, double* v) { etas.apply(transposed, v); };
     auto refactorize = [&]() {
         ipxk_lu_info li{};
@@ -1222,7 +1172,7 @@ void maxvolume_sequential_dev(Context* c, const ipxint* status_in, const double*
             const bool stable = a.pivot_col != 0.0 && std::abs(a.pivot_col - pivot) <= 1e-8 * std::abs(a.pivot_col);
             if (!stable) {
                 I.refused++;
-                if (K == 0 && !tighten_pivottol()) { I.errflag = 306; break; }
+                if (K == 0 && !tighten_pivottol(pivottol)) { I.errflag = 306; break; }
                 if (!refactorize()) break;
                 continue;                                                           // "try again" (:86-87)
             }

@@ -34,7 +34,7 @@ EXPORTS = [
     "ipxk_iterate_residuals", "ipxk_iterate_complementarity", "ipxk_step_to_boundary", "ipxk_ipm_step", "ipxk_iterate_objectives", "ipxk_ipm_driver", "ipxk_iterate_factorize_diag", "ipxk_comm_unique_id", "ipxk_comm_init", "ipxk_comm_init_columns", "ipxk_comm_info", "ipxk_maxvolume_sequential",
     "ipxk_time_normal_apply", "ipxk_equilibrate", "ipxk_transpose", "ipxk_lu_factorize", "ipxk_lu_factorize_basis",
     "ipxk_lu_get_factors", "ipxk_lu_generation", "ipxk_split_prepare_lu", "ipxk_maxvolume", "ipxk_ipm_driver_basis",
-    "ipxk_ipm_starting_point", "ipxk_ipm_load_starting_point", "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
+    "ipxk_ipm_starting_point", "ipxk_ipm_load_starting_point", "ipxk_ipm_starting_basis", "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
     "ipxk_dev_download",
 ]
 
@@ -80,6 +80,16 @@ class IpmInfo(C.Structure):
     _fields_ = [("status_ipm", c_i64), ("iter", c_i64), ("errflag", c_i64), ("kktiter", c_i64), ("pobjective", c_f64),
                 ("dobjective", c_f64), ("presidual", c_f64), ("dresidual", c_f64), ("complementarity", c_f64),
                 ("mu", c_f64), ("step_primal", c_f64), ("step_dual", c_f64), ("basis_updates", c_i64)]
+
+
+class StartingBasisParams(C.Structure):
+    _fields_ = [("dependency_tol", c_f64), ("max_etas", c_i64)]
+
+
+class StartingBasisInfo(C.Structure):
+    _fields_ = [("errflag", c_i64), ("dependent_rows", c_i64), ("dependent_cols", c_i64), ("rows_inconsistent", c_i64),
+                ("cols_inconsistent", c_i64), ("updates_start", c_i64), ("stability_pivots", c_i64),
+                ("factorizations", c_i64), ("seconds", c_f64)]
 
 
 class Times(C.Structure):
@@ -559,6 +569,21 @@ class KktContext:
         self._check(self.lib.ipxk_ipm_starting_point(self.h, _fp(_F(b)), _fp(_F(c)), _fp(_F(lb)), _fp(_F(ub)),
                                                      C.byref(prm), C.byref(info), cb, None))
         return {name: getattr(info, name) for name, _ in IpmInfo._fields_}
+
+    def ipm_starting_basis(self, b, c, lb, ub, dependency_tol=1e-6, max_etas=100, log_cap=100000, interrupt=None):
+        """StartingBasis (crash_basis = 0) on the resident iterate: free variables pivoted into the slack basis, fixed
+        slacks out of it, statuses, make_fixed and PostprocessDependencies.  Returns the info fields plus the basis, the
+        four-valued statuses and the exchange log (jb, jn); ipm_driver_basis goes on from the result."""
+        prm = StartingBasisParams(dependency_tol, max_etas)
+        info = StartingBasisInfo()
+        basis, status = np.zeros(self.m, i64), np.zeros(self.n + self.m, i64)
+        log = np.zeros(2 * max(log_cap, 1), i64)
+        cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
+        self._check(self.lib.ipxk_ipm_starting_basis(self.h, _fp(_F(b)), _fp(_F(c)), _fp(_F(lb)), _fp(_F(ub)), C.byref(prm),
+                                                     C.byref(info), _ip(basis), _ip(status), _ip(log), c_i64(log_cap), cb, None))
+        out = {name: getattr(info, name) for name, _ in StartingBasisInfo._fields_}
+        out.update(basis=basis, status=status, exchanges=log[: 2 * min(info.updates_start, log_cap)].reshape(-1, 2))
+        return out
 
     def ipm_load_starting_point(self, it, lb, ub):
         """IPM::LoadStartingPoint: the point `it` (keys of IT_KEYS) repaired into the resident iterate.  Column
