@@ -298,7 +298,6 @@ struct DirectComm {
         if (seg) { (void)hipHostUnregister(seg); munmap(seg, seg_bytes); }
         if (owner) shm_unlink(name.c_str());
     }
-    static int grid_for(int64_t n) { return (int)std::min<int64_t>(512, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
 
     void signal(Context* c, unsigned* flag_of_mine) {
         IPXK_HIP(hipStreamWriteValue32(c->stream, flag_of_mine, epoch, 0));
@@ -311,10 +310,10 @@ struct DirectComm {
         if (!staged) IPXK_HIP(hipMemcpyAsync(S, buf, count * sizeof(double), hipMemcpyDeviceToDevice, s));
         signal(c, ready_dev() + (size_t)rank * 16);
         const int64_t seg_len = ((int64_t)count + nranks - 1) / nranks;
-        hipLaunchKernelGGL(direct_reduce_kernel, dim3(grid_for(seg_len)), dim3(kBlock), 0, s, peers, rank, nranks, seg_len,
+        hipLaunchKernelGGL(direct_reduce_kernel, dim3(grid_for(seg_len, 512)), dim3(kBlock), 0, s, peers, rank, nranks, seg_len,
                            (int64_t)count, op, T, ready_dev(), epoch, abort_flag.get());
         signal(c, reduced_dev() + (size_t)rank * 16);
-        hipLaunchKernelGGL(direct_gather_kernel, dim3(grid_for((int64_t)count)), dim3(kBlock), 0, s, peers, nranks, seg_len,
+        hipLaunchKernelGGL(direct_gather_kernel, dim3(grid_for((int64_t)count, 512)), dim3(kBlock), 0, s, peers, nranks, seg_len,
                            (int64_t)count, buf, reduced_dev(), epoch, abort_flag.get());
     }
     void allgather(Context* c, const double* send, double* recv, size_t count) {
@@ -323,7 +322,7 @@ struct DirectComm {
         epoch++;
         IPXK_HIP(hipMemcpyAsync(S, send, count * sizeof(double), hipMemcpyDeviceToDevice, s));
         signal(c, ready_dev() + (size_t)rank * 16);
-        hipLaunchKernelGGL(direct_allgather_kernel, dim3(grid_for((int64_t)count * nranks)), dim3(kBlock), 0, s, peers, nranks,
+        hipLaunchKernelGGL(direct_allgather_kernel, dim3(grid_for((int64_t)count * nranks, 512)), dim3(kBlock), 0, s, peers, nranks,
                            (int64_t)count, recv, ready_dev(), epoch, abort_flag.get());
         // S is reused by the next collective: its `ready` store must not overtake a peer that still reads this
         // round's S.  A second flag round closes that window (the gather kernel of an all-reduce does the same).

@@ -325,7 +325,7 @@ CrResult kkt_diag_solve_dev(Context* c, const double* a, const double* b, double
                             ipxint maxiter, double* x, double* y, ipxk_interrupt_fn interrupt,
                             void* user, ipxk_times* times);
 
-// ---- trisolve.hip / kkt_basis.hip ----
+// ---- trisolve.hip ----
 void split_prepare_host(Context* c, const ipxint* Lp, const ipxint* Li, const double* Lx,
                         const ipxint* Up, const ipxint* Ui, const double* Ux, const ipxint* rowperm,
                         const ipxint* colperm, const ipxint* basis, const ipxint* status,

@@ -4,9 +4,17 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 #include "internal.hpp"
 
+// grid-stride loop of an elementwise kernel (the grid: grid_for / vec_grid, internal.hpp)
+#define IPXK_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+
 namespace ipxk {
+
+template <class T>
+__global__ void fill_kernel(int64_t n, T v, T* __restrict__ a) { IPXK_GRID_STRIDE(i, n) a[i] = v; }
 
 struct SumOp {
     static __device__ __forceinline__ double identity() { return 0.0; }
@@ -29,6 +37,110 @@ __device__ __forceinline__ double wave_reduce(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = Op::apply(v, __shfl_xor(v, off, 64));
     return v;
+}
+
+// The same butterfly (offset kWidth/2 down to 1, v = op(v, other)) for any element type, over the kWidth consecutive lanes
+// that share the lane index's high bits (64: the wavefront; 32 / 16: the sub-wave groups of the triangular solves).
+struct AddOp {
+    template <class T> static __device__ __forceinline__ T apply(T a, T b) { return a + b; }
+};
+struct PlainMaxOp {       // the overloaded max of the element type: unlike MaxOp, a NaN does not propagate
+    template <class T> static __device__ __forceinline__ T apply(T a, T b) { return max(a, b); }
+};
+struct FmaxOp {
+    static __device__ __forceinline__ double apply(double a, double b) { return fmax(a, b); }
+};
+template <class Op, int kWidth, class T>
+__device__ __forceinline__ T wave_reduce(T v) {
+#pragma unroll
+    for (int off = kWidth / 2; off > 0; off >>= 1) v = Op::apply(v, __shfl_xor(v, off, 64));
+    return v;
+}
+template <int kWidth = 64, class T>
+__device__ __forceinline__ T wave_sum(T v) { return wave_reduce<AddOp, kWidth>(v); }
+// several sums at once, in place, the butterflies interleaved step by step
+template <int kWidth = 64, class... T>
+__device__ __forceinline__ void wave_sum_each(T&... v) {
+#pragma unroll
+    for (int off = kWidth / 2; off > 0; off >>= 1) ((v += __shfl_xor(v, off, 64)), ...);
+}
+template <int kWidth = 64, class T>
+__device__ __forceinline__ T wave_max(T v) { return wave_reduce<PlainMaxOp, kWidth>(v); }
+
+// The indexed best: (value, index), larger value wins, equal values: smaller index wins -- every pivot search and arg max of
+// the project (the reference's loops take the first strictly larger entry).  take_smaller is its mirror for the step to the
+// boundary.  "No candidate" is (0.0, INT_MAX) resp. (the bound, one past the last index).
+__device__ __forceinline__ void take_larger(double& v, int& i, double ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+__device__ __forceinline__ void take_smaller(double& v, int& i, double ov, int oi) {
+    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+template <int kWidth = 64>
+__device__ __forceinline__ void wave_argmax(double& v, int& i) {
+#pragma unroll
+    for (int d = kWidth / 2; d >= 1; d >>= 1) {
+        const double ov = __shfl_xor(v, d, 64);
+        const int oi = __shfl_xor(i, d, 64);
+        take_larger(v, i, ov, oi);
+    }
+}
+__device__ __forceinline__ void wave_argmin(double& v, int& i) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double ov = __shfl_xor(v, d, 64);
+        const int oi = __shfl_xor(i, d, 64);
+        take_smaller(v, i, ov, oi);
+    }
+}
+
+// The partial of a two-stage reduction (Partial<kBest>, internal.hpp: kBest indexed bests, a sum and a count).  Stage one: every workgroup writes
+// block_partial of its threads' values to part[blockIdx.x]; stage two: one workgroup whose thread k holds partial k
+// (load_partial) calls block_partial again.  The number of workgroups of stage one is part of the summation order.
+template <int kBest>
+__device__ __forceinline__ Partial<kBest> partial_identity() {
+    Partial<kBest> p;
+#pragma unroll
+    for (int b = 0; b < kBest; b++) { p.v[b] = 0.0; p.i[b] = INT_MAX; }
+    p.s = 0.0;
+    p.c = 0;
+    return p;
+}
+// the workgroup's partial: wavefront trees, then the wavefronts in order; valid in thread 0.  (The shared array is one per
+// instantiation: a barrier between two calls in one kernel.)
+template <int kThreads, int kBest>
+__device__ __forceinline__ Partial<kBest> block_partial(Partial<kBest> p) {
+    __shared__ Partial<kBest> sh[kThreads / 64];
+#pragma unroll
+    for (int b = 0; b < kBest; b++) wave_argmax(p.v[b], p.i[b]);
+    p.s = wave_sum(p.s);
+    p.c = wave_sum(p.c);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = p;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 1; k < kThreads / 64; k++) {
+#pragma unroll
+            for (int b = 0; b < kBest; b++) take_larger(p.v[b], p.i[b], sh[k].v[b], sh[k].i[b]);
+            p.s += sh[k].s;
+            p.c += sh[k].c;
+        }
+    return p;
+}
+// the indexed best alone
+template <int kThreads>
+__device__ __forceinline__ void block_argmax(double& v, int& i) {
+    __shared__ double sv[kThreads / 64];
+    __shared__ int si[kThreads / 64];
+    wave_argmax(v, i);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; si[threadIdx.x >> 6] = i; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 1; k < kThreads / 64; k++) take_larger(v, i, sv[k], si[k]);
+}
+// thread k holds partial k, the identity beyond nparts
+template <int kBest>
+__device__ __forceinline__ Partial<kBest> load_partial(int nparts, const Partial<kBest>* part) {
+    return (int)threadIdx.x < nparts ? part[threadIdx.x] : partial_identity<kBest>();
 }
 
 // All kBlock threads call; every thread receives the result.  `scratch` is a

@@ -142,12 +142,14 @@ constexpr int kMaxWorkgroups = 1024; // 4 per CU: all co-resident (16 waves/CU)
 constexpr int kMaxPartials = 2048; // upper bound on grid size of reducing kernels
 constexpr int kMaxRT = 8;          // rows per thread per round
 
-// grid of a grid-stride elementwise kernel over len entries: one workgroup per kBlock entries, at most 1024
-inline int vec_grid(int64_t len) {
-    int64_t g = (len + kBlock - 1) / kBlock;
+// grid of a grid-stride kernel over n entries: one workgroup per kBlock entries, at least one, at most cap.  The cap is part
+// of a result wherever the workgroups write partials of a two-stage sum: a call site keeps the one it has.
+inline int grid_for(int64_t n, int cap = 4096) {
+    int64_t g = (n + kBlock - 1) / kBlock;
     if (g < 1) g = 1;
-    return (int)(g < 1024 ? g : 1024);
+    return (int)(g < cap ? g : cap);
 }
+inline int vec_grid(int64_t len) { return grid_for(len, 1024); }
 
 struct GatherView {                // passed to kernels by value
     int nrows, ncols;
@@ -469,7 +471,10 @@ struct MvScalars {
     int eta_total;           // entries of all etas after the last exchange
 };
 
-struct MvPart { double v; int i; double s; int c; };     // per-workgroup partial of the reductions
+// per-workgroup partial of the two-stage reductions (device_utils.hpp): kBest x (largest value, its smallest index), a sum, a count
+template <int kBest>
+struct Partial { double v[kBest]; int i[kBest]; double s; int c; };
+using MvPart = Partial<1>;
 
 struct MaxvolState {
     DevBuf<double> colscale, invscale, colweights, row, mask, rhs, lhs, unit, btran, work;

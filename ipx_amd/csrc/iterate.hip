@@ -210,11 +210,7 @@ __global__ __launch_bounds__(256) void boundary_row_kernel(int g, const double* 
     int blk = g;                            // g: none; i ascends per lane, so its first block is kept
     for (int i = lane; i < g; i += 64)
         if (a[i] < alpha) { alpha = a[i]; blk = i; }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double oa = __shfl_xor(alpha, off);
-        const int ob = __shfl_xor(blk, off);
-        if (oa < alpha || (oa == alpha && ob < blk)) { alpha = oa; blk = ob; }
-    }
+    wave_argmin(alpha, blk);
     if (lane != 0) return;
     const double idx = blk < g ? a[g + blk] : -1.0;
     double* r = row + 6 * k;

@@ -52,11 +52,6 @@ __global__ void recover_x_kernel(int n, const double* __restrict__ w, const doub
         x[j] = w[j] * (a[j] - aty[j]);
 }
 
-__global__ void fill_kernel(int len, double value, double* __restrict__ out) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x)
-        out[i] = value;
-}
-
 __global__ void multiply_kernel(int len, const double* __restrict__ x, const double* __restrict__ y,
                                 double* __restrict__ out) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x)
@@ -101,7 +96,7 @@ void kkt_diag_factorize_dev(Context* c, const double* xl, const double* xu, cons
                            c->W_own.get(), c->resscale.get());
     } else {
         // :50-52 Factorize(nullptr): G = identity
-        hipLaunchKernelGGL(fill_kernel, dim3(g), dim3(kBlock), 0, s, n + m, 1.0, c->W_own.get());
+        hipLaunchKernelGGL(fill_kernel<double>, dim3(g), dim3(kBlock), 0, s, n + m, 1.0, c->W_own.get());
         hipLaunchKernelGGL(kkt_regularize_kernel, dim3(g), dim3(kBlock), 0, s, n, m, 1.0,
                            PartRef{nullptr, 0, 1}, c->W_own.get(), c->resscale.get());
     }

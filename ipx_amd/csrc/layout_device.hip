@@ -27,13 +27,12 @@ namespace ipxk {
 namespace {
 
 using u64 = unsigned long long;
-#define IPXK_GS(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
-int gridn(int64_t n) { return (int)std::min<int64_t>(8192, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
+int gridn(int64_t n) { return grid_for(n, 8192); }
 int bits_for(u64 maxval) { int b = 1; while (b < 64 && (maxval >> b) != 0) b++; return b; }
 
 __global__ void narrow_kernel(int64_t nz, const ipxint* __restrict__ in, int* __restrict__ out, int limit, int* bad) {
-    IPXK_GS(p, nz) {
+    IPXK_GRID_STRIDE(p, nz) {
         const ipxint v = in[p];
         if (v < 0 || v >= limit) *bad = 1;
         out[p] = (int)v;
@@ -41,12 +40,12 @@ __global__ void narrow_kernel(int64_t nz, const ipxint* __restrict__ in, int* __
 }
 // column (row of the gather matrix) and position of every entry, enumerated row by row
 __global__ void rowof_kernel(int nrows, const int* __restrict__ ptr, int* __restrict__ rowof, unsigned* __restrict__ pos) {
-    IPXK_GS(r, nrows)
+    IPXK_GRID_STRIDE(r, nrows)
         for (int p = ptr[r]; p < ptr[r + 1]; p++) { rowof[p] = (int)r; if (pos) pos[p] = (unsigned)p; }
 }
 __global__ void gather_transposed_kernel(int64_t nz, const unsigned* __restrict__ perm, const int* __restrict__ colof,
                                          const double* __restrict__ Ax, int* __restrict__ Ti, double* __restrict__ Tx) {
-    IPXK_GS(t, nz) {
+    IPXK_GRID_STRIDE(t, nz) {
         const unsigned p = perm[t];
         Ti[t] = colof[p];
         Tx[t] = Ax[p];
@@ -55,7 +54,7 @@ __global__ void gather_transposed_kernel(int64_t nz, const unsigned* __restrict_
 template <class K>
 __global__ void lower_bounds_kernel(int64_t count, int64_t nz, const K* __restrict__ sorted, u64 stride, int shift, unsigned* __restrict__ out) {
     // out[t] = first position whose key is >= t * stride (shift: keys are compared after >> shift)
-    IPXK_GS(t, count) {
+    IPXK_GRID_STRIDE(t, count) {
         const u64 want = (u64)t * stride;
         int64_t lo = 0, hi = nz;
         while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (((u64)sorted[mid] >> shift) < want) lo = mid + 1; else hi = mid; }
@@ -63,7 +62,7 @@ __global__ void lower_bounds_kernel(int64_t count, int64_t nz, const K* __restri
     }
 }
 __global__ void row_pointers_kernel(int64_t m, int64_t nz, const unsigned* __restrict__ sorted_rows, int* __restrict__ Tp) {
-    IPXK_GS(i, m + 1) {
+    IPXK_GRID_STRIDE(i, m + 1) {
         int64_t lo = 0, hi = nz;
         while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (sorted_rows[mid] < (unsigned)i) lo = mid + 1; else hi = mid; }
         Tp[i] = (int)lo;
@@ -71,18 +70,17 @@ __global__ void row_pointers_kernel(int64_t m, int64_t nz, const unsigned* __res
 }
 __global__ void max_len_kernel(int nrows, const int* __restrict__ ptr, int* out) {
     int best = 0;
-    IPXK_GS(r, nrows) best = max(best, ptr[r + 1] - ptr[r]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) best = max(best, __shfl_xor(best, d, 64));
+    IPXK_GRID_STRIDE(r, nrows) best = max(best, ptr[r + 1] - ptr[r]);
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(out, best);
 }
 __global__ void row_extent_kernel(int n, const int* __restrict__ rows, const int* __restrict__ ptr, int* __restrict__ ext) {
-    IPXK_GS(l, n) { ext[2 * l] = ptr[rows[l]]; ext[2 * l + 1] = ptr[rows[l] + 1]; }
+    IPXK_GRID_STRIDE(l, n) { ext[2 * l] = ptr[rows[l]]; ext[2 * l + 1] = ptr[rows[l] + 1]; }
 }
 // key of the sliced layout: (tile, row in tile), tile = row block * ns + slice of the gathered index
 __global__ void sliced_keys_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int R, int ns, int slice,
                                    unsigned* __restrict__ key, unsigned* __restrict__ pos) {
-    IPXK_GS(r, nrows) {
+    IPXK_GRID_STRIDE(r, nrows) {
         const unsigned base = (unsigned)(r / R) * (unsigned)ns, rr = (unsigned)(r % R);
         for (int p = ptr[r]; p < ptr[r + 1]; p++) {
             key[p] = (base + (unsigned)(idx[p] / slice)) * (unsigned)R + rr;
@@ -93,7 +91,7 @@ __global__ void sliced_keys_kernel(int nrows, const int* __restrict__ ptr, const
 // key of the sorted layout's first sort: (sub-tile, row in row block)
 __global__ void sorted_keys1_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, int ns, int nsub, int slice,
                                     int half, unsigned* __restrict__ key, unsigned* __restrict__ pos) {
-    IPXK_GS(r, nrows) {
+    IPXK_GRID_STRIDE(r, nrows) {
         const unsigned tile0 = (unsigned)(r / RB) * (unsigned)ns, rr = (unsigned)(r % RB);
         for (int p = ptr[r]; p < ptr[r + 1]; p++) {
             const int sl = idx[p] / slice, off = idx[p] - sl * slice;
@@ -106,7 +104,7 @@ __global__ void sorted_keys1_kernel(int nrows, const int* __restrict__ ptr, cons
 // second sort: (sub-tile, offset in the slice), enumerated in slot order
 __global__ void sorted_keys2_kernel(int64_t nz, const unsigned* __restrict__ key1s, const unsigned* __restrict__ perm1, const int* __restrict__ idx,
                                     int RB, int ns, int nsub, int slice, u64* __restrict__ key2, unsigned* __restrict__ pos) {
-    IPXK_GS(e, nz) {
+    IPXK_GRID_STRIDE(e, nz) {
         const unsigned sub = key1s[e] / (unsigned)RB;
         const int sl = (int)((sub / (unsigned)nsub) % (unsigned)ns);
         const int off = idx[perm1[e]] - sl * slice;
@@ -117,7 +115,7 @@ __global__ void sorted_keys2_kernel(int64_t nz, const unsigned* __restrict__ key
 __global__ void sorted_fill_kernel(int64_t nz, const u64* __restrict__ key2s, const unsigned* __restrict__ perm2, const unsigned* __restrict__ perm1,
                                    const unsigned* __restrict__ sub_ptr, const double* __restrict__ val, unsigned* __restrict__ pack,
                                    double* __restrict__ out_val) {
-    IPXK_GS(f, nz) {
+    IPXK_GRID_STRIDE(f, nz) {
         const u64 k = key2s[f];
         const unsigned e = perm2[f], sub = (unsigned)(k >> kSortedOffBits), off = (unsigned)(k & ((1u << kSortedOffBits) - 1u));
         pack[f] = ((e - sub_ptr[sub]) << kSortedOffBits) | off;
@@ -126,7 +124,7 @@ __global__ void sorted_fill_kernel(int64_t nz, const u64* __restrict__ key2s, co
 }
 // byte counts per key from the runs of equal keys (cnt is zero on entry); a run of more than 255 raises *overflow
 __global__ void run_counts_kernel(int64_t nz, const unsigned* __restrict__ sorted, unsigned char* __restrict__ cnt, int* overflow) {
-    IPXK_GS(e, nz) {
+    IPXK_GRID_STRIDE(e, nz) {
         const unsigned k = sorted[e];
         if (e > 0 && sorted[e - 1] == k) continue;
         int len = 1;
@@ -137,7 +135,7 @@ __global__ void run_counts_kernel(int64_t nz, const unsigned* __restrict__ sorte
 }
 __global__ void gather_entries_kernel(int64_t nz, const unsigned* __restrict__ perm, const int* __restrict__ idx, const double* __restrict__ val,
                                       int* __restrict__ out_idx, double* __restrict__ out_val) {
-    IPXK_GS(e, nz) {
+    IPXK_GRID_STRIDE(e, nz) {
         const unsigned p = perm[e];
         out_idx[e] = idx[p];
         out_val[e] = val[p];
@@ -147,14 +145,14 @@ __global__ void gather_entries_kernel(int64_t nz, const unsigned* __restrict__ p
 __global__ void tile_stats_kernel(int nrb, int ns, const unsigned* __restrict__ tile_ptr, int* out) {
     int best_tile = 0;
     u64 dom = 0;
-    IPXK_GS(rb, nrb) {
+    IPXK_GRID_STRIDE(rb, nrb) {
         unsigned best = 0;
         for (int sl = 0; sl < ns; sl++) best = max(best, tile_ptr[(size_t)rb * ns + sl + 1] - tile_ptr[(size_t)rb * ns + sl]);
         best_tile = max(best_tile, (int)best);
         dom += best;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { best_tile = max(best_tile, __shfl_xor(best_tile, d, 64)); dom += __shfl_xor(dom, d, 64); }
+    best_tile = wave_max(best_tile);
+    dom = wave_sum(dom);
     if ((threadIdx.x & 63) == 0) {
         atomicMax(out, best_tile);
         if (dom) atomicAdd(reinterpret_cast<u64*>(out + 2), dom);
@@ -162,9 +160,8 @@ __global__ void tile_stats_kernel(int nrb, int ns, const unsigned* __restrict__ 
 }
 __global__ void max_range_kernel(int64_t count, const unsigned* __restrict__ ptr, int* out) {
     int best = 0;
-    IPXK_GS(t, count) best = max(best, (int)(ptr[t + 1] - ptr[t]));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) best = max(best, __shfl_xor(best, d, 64));
+    IPXK_GRID_STRIDE(t, count) best = max(best, (int)(ptr[t + 1] - ptr[t]));
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(out, best);
 }
 // entries of a list of columns, one after the other (dense columns: precond.hip)
@@ -175,13 +172,13 @@ __global__ void gather_columns_kernel(int k, const int* __restrict__ cols, const
     const int j = cols[kk], p0 = Ap[j], len = Ap[j + 1] - p0, o = off[kk];
     for (int t = threadIdx.x; t < len; t += blockDim.x) { out_i[o + t] = Ai[p0 + t]; out_x[o + t] = Ax[p0 + t]; }
 }
-__global__ void widen_kernel(int64_t nz, const int* __restrict__ in, ipxint* __restrict__ out) { IPXK_GS(p, nz) out[p] = in[p]; }
+__global__ void widen_kernel(int64_t nz, const int* __restrict__ in, ipxint* __restrict__ out) { IPXK_GRID_STRIDE(p, nz) out[p] = in[p]; }
 
 // ---- accumulated tiles -----------------------------------------------------------------------
 // key = (tile << 18 | offset in the slice), enumerated in storage order (a stable sort keeps that order among ties)
 __global__ void acc_keys_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, int ns, int slice,
                                 u64* __restrict__ key, unsigned* __restrict__ pos, int* __restrict__ rowof) {
-    IPXK_GS(r, nrows) {
+    IPXK_GRID_STRIDE(r, nrows) {
         const u64 tile0 = (u64)(r / RB) * (u64)ns;
         for (int p = ptr[r]; p < ptr[r + 1]; p++) {
             const int sl = idx[p] / slice, off = idx[p] - sl * slice;
@@ -194,7 +191,7 @@ __global__ void acc_keys_kernel(int nrows, const int* __restrict__ ptr, const in
 // the entry words in sorted order: row in block << 18 | offset
 __global__ void acc_words_kernel(int64_t nz, const u64* __restrict__ keys, const unsigned* __restrict__ perm, const int* __restrict__ rowof, int RB,
                                  unsigned* __restrict__ word) {
-    IPXK_GS(e, nz) word[e] = ((unsigned)(rowof[perm[e]] % RB) << kSortedOffBits) | (unsigned)(keys[e] & ((1u << kSortedOffBits) - 1u));
+    IPXK_GRID_STRIDE(e, nz) word[e] = ((unsigned)(rowof[perm[e]] % RB) << kSortedOffBits) | (unsigned)(keys[e] & ((1u << kSortedOffBits) - 1u));
 }
 // The batches of one tile, by ONE wavefront: the tile's entries are walked in address order, 64 candidates at a time
 // (the entries that waited from the previous batch first, then the stream); a candidate is taken unless its row
@@ -263,7 +260,7 @@ __global__ __launch_bounds__(64) void acc_batch_kernel(int RB, const unsigned* _
 }
 __global__ void acc_scatter_kernel(int64_t nz, const unsigned* __restrict__ dst, const unsigned* __restrict__ word, const unsigned* __restrict__ perm,
                                    const double* __restrict__ val, unsigned* __restrict__ pack, double* __restrict__ out_val) {
-    IPXK_GS(e, nz) {
+    IPXK_GRID_STRIDE(e, nz) {
         const unsigned d = dst[e];
         pack[d] = word[e];
         out_val[d] = val[perm[e]];
@@ -306,7 +303,7 @@ __global__ void acc_bptr_kernel(int ntiles, const unsigned* __restrict__ tile_pt
 // smallest / largest gathered index per tile, the rows' count bytes (optional), a flag for rows with descending / repeated indices
 __global__ void tile_window_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, int* __restrict__ lo,
                                    int* __restrict__ hi, unsigned char* __restrict__ cnt, int* flags) {
-    IPXK_GS(r, nrows) {
+    IPXK_GRID_STRIDE(r, nrows) {
         const int p0 = ptr[r], p1 = ptr[r + 1];
         if (cnt) { if (p1 - p0 > 255) flags[0] = 1; cnt[r] = (unsigned char)(p1 - p0); }
         if (p1 == p0) continue;
@@ -323,7 +320,7 @@ __global__ void tile_window_kernel(int nrows, const int* __restrict__ ptr, const
 // [0] widest window (hi - lo) of a tile, [1] most entries of a tile; empty tiles get lo = 0
 __global__ void tile_window_stats_kernel(int nrb, int nrows, int RB, const int* __restrict__ ptr, int* __restrict__ lo, const int* __restrict__ hi,
                                          int* out) {
-    IPXK_GS(t, nrb) {
+    IPXK_GRID_STRIDE(t, nrb) {
         const int r0 = (int)t * RB, r1 = min(nrows, r0 + RB);
         const int ne = ptr[r1] - ptr[r0];
         if (ne == 0) { lo[t] = 0; continue; }
@@ -334,7 +331,7 @@ __global__ void tile_window_stats_kernel(int nrb, int nrows, int RB, const int* 
 // key = tile << 18 | (index - the tile's smallest index), enumerated in storage order
 __global__ void fused_keys_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, const int* __restrict__ lo,
                                   u64* __restrict__ key, unsigned* __restrict__ pos, int* __restrict__ rowof) {
-    IPXK_GS(r, nrows) {
+    IPXK_GRID_STRIDE(r, nrows) {
         const u64 t = (u64)(r / RB);
         const int base = lo[r / RB];
         for (int p = ptr[r]; p < ptr[r + 1]; p++) {
@@ -347,7 +344,7 @@ __global__ void fused_keys_kernel(int nrows, const int* __restrict__ ptr, const 
 // sorted fused tiles: slot = place of the entry in the tile's row-major (= storage) order
 __global__ void sorted_fused_fill_kernel(int64_t nz, const u64* __restrict__ keys, const unsigned* __restrict__ perm, const int* __restrict__ ptr, int RB,
                                          const double* __restrict__ val, unsigned* __restrict__ pack, double* __restrict__ out_val) {
-    IPXK_GS(f, nz) {
+    IPXK_GRID_STRIDE(f, nz) {
         const u64 k = keys[f];
         const unsigned p = perm[f], t = (unsigned)(k >> kSortedOffBits);
         pack[f] = ((p - (unsigned)ptr[(size_t)t * RB]) << kSortedOffBits) | (unsigned)(k & ((1u << kSortedOffBits) - 1u));
@@ -355,7 +352,7 @@ __global__ void sorted_fused_fill_kernel(int64_t nz, const u64* __restrict__ key
     }
 }
 __global__ void tile_ptr_from_rows_kernel(int nrb, int nrows, int RB, const int* __restrict__ ptr, unsigned* __restrict__ out) {
-    IPXK_GS(t, (int64_t)nrb + 1) out[t] = (unsigned)ptr[min((int64_t)nrows, t * RB)];
+    IPXK_GRID_STRIDE(t, (int64_t)nrb + 1) out[t] = (unsigned)ptr[min((int64_t)nrows, t * RB)];
 }
 
 struct Tmp {
@@ -506,7 +503,7 @@ namespace {
 constexpr int kMaxLongRowsDevice = 1 << 16;
 __global__ void long_flag_kernel(int nrows, const int* __restrict__ ptr, unsigned char* __restrict__ flag, int* __restrict__ slen, int* counters,
                                  int* __restrict__ list, int cap) {
-    IPXK_GS(r, (int64_t)nrows + 1) {
+    IPXK_GRID_STRIDE(r, (int64_t)nrows + 1) {
         if (r == nrows) { slen[r] = 0; continue; }
         const int len = ptr[r + 1] - ptr[r];
         const bool lg = len > kMaxRowLen;
@@ -923,7 +920,7 @@ namespace {
 constexpr int kMaxComponents = 64;
 __global__ void bfs_expand_kernel(int nf, const int* __restrict__ frontier, const int* __restrict__ ptr, const int* __restrict__ idx,
                                   int* level_of, int level, int* __restrict__ next, int* next_count) {
-    IPXK_GS(t, nf) {
+    IPXK_GRID_STRIDE(t, nf) {
         const int v = frontier[t];
         for (int p = ptr[v]; p < ptr[v + 1]; p++) {
             const int w = idx[p];
@@ -932,41 +929,41 @@ __global__ void bfs_expand_kernel(int nf, const int* __restrict__ frontier, cons
     }
 }
 __global__ void first_unvisited_kernel(int n, const int* __restrict__ level_of, const int* __restrict__ ptr, int* out) {
-    IPXK_GS(i, n) if (level_of[i] < 0 && ptr[i + 1] > ptr[i]) atomicMin(out, (int)i);
+    IPXK_GRID_STRIDE(i, n) if (level_of[i] < 0 && ptr[i + 1] > ptr[i]) atomicMin(out, (int)i);
 }
 __global__ void min_of_list_kernel(int nf, const int* __restrict__ list, int* out) {
-    IPXK_GS(t, nf) atomicMin(out, list[t]);
+    IPXK_GRID_STRIDE(t, nf) atomicMin(out, list[t]);
 }
 __global__ void level_keys_kernel(int n, const int* __restrict__ level_of, u64* __restrict__ keys, unsigned* __restrict__ vals) {
-    IPXK_GS(i, n) {
+    IPXK_GRID_STRIDE(i, n) {
         const unsigned lv = level_of[i] < 0 ? 0x7fffffffu : (unsigned)level_of[i];       // never reached (empty rows / columns): last
         keys[i] = ((u64)lv << 32) | (u64)i;
         vals[i] = (unsigned)i;
     }
 }
 __global__ void invert_perm_kernel(int n, const unsigned* __restrict__ perm, int* __restrict__ perm_out, int* __restrict__ inv) {
-    IPXK_GS(i, n) { perm_out[i] = (int)perm[i]; inv[perm[i]] = (int)i; }
+    IPXK_GRID_STRIDE(i, n) { perm_out[i] = (int)perm[i]; inv[perm[i]] = (int)i; }
 }
 __global__ void permuted_keys_kernel(int64_t nz, const int* __restrict__ colof, const int* __restrict__ Ai, const int* __restrict__ colinv,
                                      const int* __restrict__ rowinv, u64* __restrict__ keys, unsigned* __restrict__ pos) {
-    IPXK_GS(e, nz) {
+    IPXK_GRID_STRIDE(e, nz) {
         keys[e] = ((u64)(unsigned)colinv[colof[e]] << 32) | (u64)(unsigned)rowinv[Ai[e]];
         pos[e] = (unsigned)e;
     }
 }
 __global__ void permuted_fill_kernel(int64_t nz, const u64* __restrict__ keys, const unsigned* __restrict__ pos, const double* __restrict__ Ax,
                                      int* __restrict__ Ai_new, double* __restrict__ Ax_new, unsigned* __restrict__ col_new) {
-    IPXK_GS(e, nz) {
+    IPXK_GRID_STRIDE(e, nz) {
         Ai_new[e] = (int)(keys[e] & 0xffffffffu);
         col_new[e] = (unsigned)(keys[e] >> 32);
         Ax_new[e] = Ax[pos[e]];
     }
 }
 __global__ void gather_rows_kernel(int n, const int* __restrict__ perm, const double* __restrict__ in, double* __restrict__ out) {
-    IPXK_GS(i, n) out[i] = in[perm[i]];
+    IPXK_GRID_STRIDE(i, n) out[i] = in[perm[i]];
 }
 __global__ void scatter_rows_kernel(int n, const int* __restrict__ perm, const double* __restrict__ in, double* __restrict__ out) {
-    IPXK_GS(i, n) out[perm[i]] = in[i];
+    IPXK_GRID_STRIDE(i, n) out[perm[i]] = in[i];
 }
 template <class K>
 void sort_pairs_u64(Tmp& T, const K* kin, K* kout, const unsigned* vin, unsigned* vout, size_t n, int bits, hipStream_t s) {
@@ -988,7 +985,7 @@ __global__ void bfs_level_kernel(const int* __restrict__ frontier, const int* __
         if (zero_b) *zero_b = 0;
         if (hist_slot) *hist_slot = nf;
     }
-    IPXK_GS(t, nf) {
+    IPXK_GRID_STRIDE(t, nf) {
         const int v = frontier[t];
         for (int p = ptr[v]; p < ptr[v + 1]; p++) {
             const int w = idx[p];

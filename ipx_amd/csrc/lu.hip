@@ -80,10 +80,8 @@ constexpr int kPanel = 32;           // columns per panel of the dense eliminati
 constexpr int kPanelThreads = 1024;
 constexpr u64 kNoKey = ~0ull;
 
-int grid_for(int64_t n) { return (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
 int bits_for(int64_t n) { int b = 1; while ((int64_t(1) << b) < n) b++; return b; }
 
-#define IPXK_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 struct Tmp {
     DevBuf<unsigned char> bytes;
@@ -125,8 +123,6 @@ __global__ void lu_expand_kernel(int dim, const int* __restrict__ Bp, const int*
 __global__ void lu_rows_kernel(int64_t nb, const int* __restrict__ pos_sorted, const int* __restrict__ colof, int* __restrict__ Rj) {
     IPXK_GRID_STRIDE(q, nb) Rj[q] = colof[pos_sorted[q]];
 }
-__global__ void lu_fill_int_kernel(int64_t n, int v, int* a) { IPXK_GRID_STRIDE(i, n) a[i] = v; }
-__global__ void lu_fill_u64_kernel(int64_t n, u64 v, u64* a) { IPXK_GRID_STRIDE(i, n) a[i] = v; }
 
 // ---- singleton rounds ---------------------------------------------------------------------------
 // While the rounds run, rstage / cstage hold -1 for active rows / columns and the TAG of the round that pivoted
@@ -237,8 +233,7 @@ __global__ __launch_bounds__(kBlock) void lu_count_kinds_kernel(int dim, const u
     __syncthreads();
     int n1 = 0, n2 = 0;
     IPXK_GRID_STRIDE(j, dim) { n1 += ckind[j] == 1; n2 += ckind[j] == 2; }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { n1 += __shfl_xor(n1, d, 64); n2 += __shfl_xor(n2, d, 64); }
+    wave_sum_each(n1, n2);
     if ((threadIdx.x & 63) == 0) { atomicAdd(&s1, n1); atomicAdd(&s2, n2); }
     __syncthreads();
     if (threadIdx.x == 0) { if (s1) atomicAdd(counters + 1, s1); if (s2) atomicAdd(counters + 2, s2); }
@@ -380,8 +375,7 @@ __global__ void lu_spike_count_kernel(int kb, int c0, size_t xs, int npiv, const
     const int nlanes = min(kSpikeBatch, kb - c0);
     int mine = 0;
     IPXK_GRID_STRIDE(e, (int64_t)npiv * kSpikeBatch) mine += (int)(e % kSpikeBatch) < nlanes && X[e] != 0.0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
 }
 __global__ void lu_spike_append_kernel(int kb, int c0, size_t xs, int npiv, const double* __restrict__ X, int* cursor,
@@ -454,12 +448,7 @@ __global__ __launch_bounds__(kPanelThreads) void lu_panel_kernel(Dense A, int c0
                 const double a = fabs(col[r]);
                 if (a > best) { best = a; br = r; }
             }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const double ov = __shfl_xor(best, d, 64);
-            const int orr = __shfl_xor(br, d, 64);
-            if (ov > best || (ov == best && orr < br)) { best = ov; br = orr; }
-        }
+        wave_argmax(best, br);
         if (lane == 0) { red_v[wave] = best; red_r[wave] = br; }
         __syncthreads();
         if (tid == 0) {
@@ -519,12 +508,7 @@ __device__ __forceinline__ int panel_pivot_row(const PanelShared& sh, int par, b
     double bv = sh.red_v[par][threadIdx.x & 15];
     int rr = sh.red_r[par][threadIdx.x & 15];
     if (!(bv > 0.0)) { bv = 0.0; rr = INT_MAX; }          // (no candidate, or not a number: never a pivot)
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(bv, d, 64);
-        const int orr = __shfl_xor(rr, d, 64);
-        if (ov > bv || (ov == bv && orr < rr)) { bv = ov; rr = orr; }
-    }
+    wave_argmax<16>(bv, rr);
     *dependent = col && (rr == INT_MAX || !(bv >= abstol) || bv == 0.0);
     return col && !*dependent ? rr : -1;
 }
@@ -536,12 +520,7 @@ __device__ __forceinline__ void panel_small_steps(const Dense& A, PanelShared& s
         const bool col = c0 + T < c1;                  // uniform
         double best = (col && active) ? fabs(v[T]) : 0.0;
         int br = best > 0.0 ? r : INT_MAX;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const double ov = __shfl_xor(best, d, 64);
-            const int orr = __shfl_xor(br, d, 64);
-            if (ov > best || (ov == best && orr < br)) { best = ov; br = orr; }
-        }
+        wave_argmax(best, br);
         constexpr int par = T & 1;
         if (lane == 0) { sh.red_v[par][wave] = best; sh.red_r[par][wave] = br; }
         __syncthreads();
@@ -617,12 +596,7 @@ __device__ __forceinline__ void panel_multi_steps(const Dense& A, PanelShared& s
             const double a = (col && ((active >> q) & 1u)) ? fabs(v[q][T]) : 0.0;
             if (a > best) { best = a; br = tid + q * kPanelThreads; }      // rows ascend with q: the first maximum stays
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const double ov = __shfl_xor(best, d, 64);
-            const int orr = __shfl_xor(br, d, 64);
-            if (ov > best || (ov == best && orr < br)) { best = ov; br = orr; }
-        }
+        wave_argmax(best, br);
         constexpr int par = T & 1;
         if (lane == 0) { sh.red_v[par][wave] = best; sh.red_r[par][wave] = br; }
         __syncthreads();
@@ -762,22 +736,13 @@ __device__ __forceinline__ void coop_steps(const Dense& A, CoopShared& sh, const
             const double a = ((active >> q) & 1u) ? fabs(v[q][T]) : 0.0;
             if (a > best) { best = a; br = row0 + q * kCoopThreads + tid; }       // rows ascend with q: the first maximum stays
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const double ov = __shfl_xor(best, d, 64);
-            const int orr = __shfl_xor(br, d, 64);
-            if (ov > best || (ov == best && orr < br)) { best = ov; br = orr; }
-        }
+        wave_argmax(best, br);
         if (lane == 0) { sh.red_v[wave] = best; sh.red_r[wave] = br; }
         __syncthreads();
         double bv = 0.0;
         int rr = INT_MAX;
 #pragma unroll
-        for (int w = 0; w < kCoopThreads / 64; w++) {
-            const double ov = sh.red_v[w];
-            const int orr = sh.red_r[w];
-            if (ov > bv || (ov == bv && orr < rr)) { bv = ov; rr = orr; }
-        }
+        for (int w = 0; w < kCoopThreads / 64; w++) take_larger(bv, rr, sh.red_v[w], sh.red_r[w]);
         if (!(bv > 0.0)) { bv = 0.0; rr = INT_MAX; }       // (no candidate, or not a number: never a pivot)
         if (rr != INT_MAX && (rr - row0) % kCoopThreads == tid) {
             const int qo = (rr - row0) / kCoopThreads;
@@ -1185,8 +1150,7 @@ __global__ __launch_bounds__(kBlock) void sp_cand_kernel(Sparse S) {
         const int p0 = S.Bp[j], p1 = S.Bp[j + 1];
         double colmax = 0.0;
         for (int p = p0 + lane; p < p1; p += 64) colmax = fmax(colmax, fabs(S.Bx[p]));
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) colmax = fmax(colmax, __shfl_xor(colmax, d, 64));
+        colmax = wave_reduce<FmaxOp, 64>(colmax);
         int bi = INT_MAX, brc = INT_MAX;
         double ba = 0.0;
         const double rel = S.pivottol * colmax;
@@ -1763,9 +1727,9 @@ SparseOut sparse_rounds(hipStream_t s, LuWork& W, int dim, int64_t nb, const int
                  P.cc.get(), P.candrow.get(), P.cost.get(), P.key.get(), P.rowbest.get(), P.stats.get(), abstol, pivottol};
         const int gl = grid_for(dimL);
         hipLaunchKernelGGL(sp_stats_init_kernel, dim3(1), dim3(64), 0, s, P.stats.get());
-        hipLaunchKernelGGL(lu_fill_u64_kernel, dim3(gl), dim3(kBlock), 0, s, (int64_t)dimL, kNoKey, P.rowbest.get());
-        hipLaunchKernelGGL(lu_fill_int_kernel, dim3(gl), dim3(kBlock), 0, s, (int64_t)dimL, -1, P.rstL.get());
-        hipLaunchKernelGGL(lu_fill_int_kernel, dim3(gl), dim3(kBlock), 0, s, (int64_t)dimL, -1, P.cstL.get());
+        hipLaunchKernelGGL(fill_kernel<u64>, dim3(gl), dim3(kBlock), 0, s, (int64_t)dimL, kNoKey, P.rowbest.get());
+        hipLaunchKernelGGL(fill_kernel<int>, dim3(gl), dim3(kBlock), 0, s, (int64_t)dimL, -1, P.rstL.get());
+        hipLaunchKernelGGL(fill_kernel<int>, dim3(gl), dim3(kBlock), 0, s, (int64_t)dimL, -1, P.cstL.get());
         IPXK_HIP(hipMemsetAsync(P.nupd.get(), 0, (l1 + 1) * sizeof(int), s));
         const int gw = (int)std::min<int64_t>(4096, ((int64_t)dimL + kBlock / 64 - 1) / (kBlock / 64));     // a wavefront per column
         hipLaunchKernelGGL(sp_cand_kernel, dim3(gw), dim3(kBlock), 0, s, S);
@@ -1918,9 +1882,9 @@ static void lu_factorize_device(Context* c, LuState* S, int dim, int64_t nb_in, 
     IPXK_HIP(hipMemsetAsync(pivot.get(), 0, d1 * sizeof(double), s));
     const int g = grid_for(dim);
     if (dim > 0) {
-        hipLaunchKernelGGL(lu_fill_int_kernel, dim3(g), dim3(kBlock), 0, s, (int64_t)dim, -1, rstage.get());
-        hipLaunchKernelGGL(lu_fill_int_kernel, dim3(g), dim3(kBlock), 0, s, (int64_t)dim, -1, cstage.get());
-        hipLaunchKernelGGL(lu_fill_int_kernel, dim3(g), dim3(kBlock), 0, s, (int64_t)dim, INT_MAX, claim.get());
+        hipLaunchKernelGGL(fill_kernel<int>, dim3(g), dim3(kBlock), 0, s, (int64_t)dim, -1, rstage.get());
+        hipLaunchKernelGGL(fill_kernel<int>, dim3(g), dim3(kBlock), 0, s, (int64_t)dim, -1, cstage.get());
+        hipLaunchKernelGGL(fill_kernel<int>, dim3(g), dim3(kBlock), 0, s, (int64_t)dim, INT_MAX, claim.get());
         hipLaunchKernelGGL(lu_expand_kernel, dim3(g), dim3(kBlock), 0, s, dim, Bp, Bi, colof.get(), keys.get(), pos.get(),
                            rc.get(), cc.get(), counters.get() + 7);
         if (nb > 0) {
@@ -2107,8 +2071,8 @@ static void lu_factorize_device(Context* c, LuState* S, int dim, int64_t nb_in, 
         IPXK_HIP(hipMemsetAsync(D.get(), 0, (size_t)kb * kb * sizeof(double), s));
         IPXK_HIP(hipMemsetAsync(bstep.get(), 0, 8 * sizeof(int), s));
         const int gk = grid_for(kb);
-        hipLaunchKernelGGL(lu_fill_int_kernel, dim3(gk), dim3(kBlock), 0, s, (int64_t)kb, -1, brstep.get());
-        hipLaunchKernelGGL(lu_fill_int_kernel, dim3(gk), dim3(kBlock), 0, s, (int64_t)kb, -1, bcstep.get());
+        hipLaunchKernelGGL(fill_kernel<int>, dim3(gk), dim3(kBlock), 0, s, (int64_t)kb, -1, brstep.get());
+        hipLaunchKernelGGL(fill_kernel<int>, dim3(gk), dim3(kBlock), 0, s, (int64_t)kb, -1, bcstep.get());
         if (sparse_done) {
             // the block's columns in ascending order of their number of entries (ties: index): fewer nonzeros in its factors
             LuWork::Sp& P = W.sp;
@@ -2305,7 +2269,7 @@ static void lu_factorize_device(Context* c, LuState* S, int dim, int64_t nb_in, 
                 W_.coop_slots.ensure((size_t)5 * kCoopMaxG * kCoopSlot); W_.coop_bar.ensure(2);
                 if (W_.coop_xcc.size() < (size_t)kCoopMaxG) { W_.coop_xcc.ensure((size_t)kCoopMaxG); IPXK_HIP(hipMemsetAsync(W_.coop_xcc.get(), 0, kCoopMaxG * sizeof(unsigned long long), s)); }
                 IPXK_HIP(hipMemsetAsync(W_.coop_bar.get(), 0, 2 * sizeof(unsigned), s));
-                hipLaunchKernelGGL(lu_fill_u64_kernel, dim3(8), dim3(kBlock), 0, s, (int64_t)5 * kCoopMaxG * kCoopSlot, (u64)kCoopSentinel,
+                hipLaunchKernelGGL(fill_kernel<u64>, dim3(8), dim3(kBlock), 0, s, (int64_t)5 * kCoopMaxG * kCoopSlot, (u64)kCoopSentinel,
                                    reinterpret_cast<u64*>(W_.coop_slots.get()));
             }
             int k = 0, last_late = -1;                  // outer panel index; the last outer panel with a late update in flight
@@ -2419,8 +2383,8 @@ static void lu_factorize_device(Context* c, LuState* S, int dim, int64_t nb_in, 
         for (DevBuf<u64>* b : {&ukey, &ukey2}) b->ensure((size_t)nu);
         for (DevBuf<double>* b : {&lval, &lval2}) b->ensure((size_t)std::max<int64_t>(nl, 1));
         for (DevBuf<double>* b : {&uval, &uval2}) b->ensure((size_t)nu);
-        if (nl > 0) hipLaunchKernelGGL(lu_fill_u64_kernel, dim3(grid_for(nl)), dim3(kBlock), 0, s, nl, kNoKey, lkey.get());
-        hipLaunchKernelGGL(lu_fill_u64_kernel, dim3(grid_for(nu)), dim3(kBlock), 0, s, nu, kNoKey, ukey.get());
+        if (nl > 0) hipLaunchKernelGGL(fill_kernel<u64>, dim3(grid_for(nl)), dim3(kBlock), 0, s, nl, kNoKey, lkey.get());
+        hipLaunchKernelGGL(fill_kernel<u64>, dim3(grid_for(nu)), dim3(kBlock), 0, s, nu, kNoKey, ukey.get());
         const int kshift = bits_for((int64_t)dim + 1);            // 2^kshift > dim
         Assemble A{dim, kb, Bp, asm_row, asm_col, asm_val, rstage.get(), cstage.get(), rloc.get(), cloc.get(), brow.get(), bcol.get(),
                    bcstep.get(), pivot.get(), D.get(), ckind.get(), lkey.get(), ukey.get(), lval.get(), uval.get(), tearing ? 1 : 0, kshift};

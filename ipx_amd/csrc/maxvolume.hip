@@ -43,57 +43,29 @@ constexpr int kRedGrid = 512;            // workgroups of the two-stage reductio
 constexpr int kEtaThreads = 1024;
 constexpr double kPivotZeroTol = 1e-7;   // src/maxvolume.h:34
 
-int grid_for(int64_t n) { return (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
-#define IPXK_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 using Scalars = MvScalars;     // the scalars of one step (internal.hpp)
 using Part = MvPart;
 
 // ---- FindLargest (src/maxvolume.cc:179-200): first index of the largest |w| ----------------------------------
 __global__ __launch_bounds__(kBlock) void mv_argmax_kernel(int64_t N, const double* __restrict__ w, Part* part) {
-    __shared__ double sv[kBlock / 64];
-    __shared__ int si[kBlock / 64];
     double best = 0.0;
     int bi = INT_MAX;
     IPXK_GRID_STRIDE(j, N) {
         const double a = fabs(w[j]);
         if (a > best || (a == best && a > 0.0 && (int)j < bi)) { best = a; bi = (int)j; }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(best, d, 64);
-        const int oi = __shfl_xor(bi, d, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
+    block_argmax<kBlock>(best, bi);
     if (threadIdx.x == 0) {
-        for (int k = 1; k < kBlock / 64; k++)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-        part[blockIdx.x].v = best;
-        part[blockIdx.x].i = bi;
+        part[blockIdx.x].v[0] = best;
+        part[blockIdx.x].i[0] = bi;
     }
 }
-// one workgroup of kRedGrid threads: thread k holds partial k, the tree keeps (largest value, smallest index)
-__device__ __forceinline__ void final_argmax(double& best, int& bi, double* sv, int* si) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(best, d, 64);
-        const int oi = __shfl_xor(bi, d, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int k = 1; k < kRedGrid / 64; k++)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-}
+// one workgroup of kRedGrid threads: thread k holds partial k
 __global__ __launch_bounds__(kRedGrid) void mv_argmax_final_kernel(int nparts, const Part* part, const double* __restrict__ w, Scalars* S) {
-    __shared__ double sv[kRedGrid / 64];
-    __shared__ int si[kRedGrid / 64];
-    double best = (int)threadIdx.x < nparts ? part[threadIdx.x].v : 0.0;
-    int bi = (int)threadIdx.x < nparts ? part[threadIdx.x].i : INT_MAX;
-    final_argmax(best, bi, sv, si);
+    double best = (int)threadIdx.x < nparts ? part[threadIdx.x].v[0] : 0.0;
+    int bi = (int)threadIdx.x < nparts ? part[threadIdx.x].i[0] : INT_MAX;
+    block_argmax<kRedGrid>(best, bi);
     if (threadIdx.x == 0) {
         S->jn = bi == INT_MAX ? 0 : bi;             // all weights zero: index 0, weight 0 (the loop ends)
         S->weight = w[S->jn];
@@ -128,8 +100,7 @@ __global__ __launch_bounds__(kEtaThreads) void mv_eta_btran_kernel(int K, const 
     for (int t = K - 1; t >= 0; t--) {
         double sum = 0.0;
         for (int e = ptr[t] + threadIdx.x; e < ptr[t + 1]; e += kEtaThreads) sum += val[e] * v[idx[e]];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+        sum = wave_sum(sum);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -262,8 +233,7 @@ __global__ __launch_bounds__(kBlock) void mv_eta_dense_dots_kernel(int m, const 
     const double* e = E + (size_t)blockIdx.x * m;
     double sum = 0.0;
     for (int i = threadIdx.x; i < m; i += kBlock) sum += e[i] * v[i];
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) sum += __shfl_xor(sum, k, 64);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -396,8 +366,7 @@ __global__ __launch_bounds__(kBlock) void mv_eta_forward_gemv_kernel(int K, int 
     for (int t = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); t < K; t += gridDim.x * (kBlock / 64)) {
         double sum = 0.0;
         for (int j = lane; j < Kd; j += 64) sum += F[(size_t)t * Kd + j] * v[pos[first[j]]];
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) sum += __shfl_xor(sum, k, 64);
+        sum = wave_sum(sum);
         if (lane == 0) alpha[t] = sum;
     }
 }
@@ -409,8 +378,7 @@ __global__ __launch_bounds__(kBlock) void mv_eta_backward_gemv_kernel(int K, int
     for (int t = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); t < K; t += gridDim.x * (kBlock / 64)) {
         double sum = 0.0;
         for (int u = lane; u < W; u += 64) sum += G[(size_t)t * W + u] * (u < K ? d[u] : v[pos[first[u - K]]]);
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) sum += __shfl_xor(sum, k, 64);
+        sum = wave_sum(sum);
         if (lane == 0) w[t] = sum;
     }
 }
@@ -424,8 +392,6 @@ __global__ void mv_eta_backward_scatter_kernel(int Kd, const int* __restrict__ f
 __global__ __launch_bounds__(kBlock) void mv_scale_ftran_kernel(int m, const Scalars* S, const double* __restrict__ lhs,
                                                                 const double* __restrict__ colscale, const double* __restrict__ invscale,
                                                                 const int* __restrict__ slice_of, int slice, Part* part) {
-    __shared__ double sv[kBlock / 64], ss[kBlock / 64];
-    __shared__ int si[kBlock / 64], sc[kBlock / 64];
     const double dj = colscale[S->jn];
     double best = 0.0, sum = 0.0;
     int bi = INT_MAX, cnt = 0;
@@ -437,50 +403,25 @@ __global__ __launch_bounds__(kBlock) void mv_scale_ftran_kernel(int m, const Sca
         if (slice_of[p] == slice) sum += scaled;
         cnt += pivot != 0.0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(best, d, 64);
-        const int oi = __shfl_xor(bi, d, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        sum += __shfl_xor(sum, d, 64);
-        cnt += __shfl_xor(cnt, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; sv[w] = best; si[w] = bi; ss[w] = sum; sc[w] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kBlock / 64; k++) {
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-            sum += ss[k];
-            cnt += sc[k];
-        }
-        part[blockIdx.x] = Part{best, bi, sum, cnt};
-    }
+    const Part mine = block_partial<kBlock>(Part{{best}, {bi}, sum, cnt});
+    if (threadIdx.x == 0) part[blockIdx.x] = mine;
 }
 __global__ __launch_bounds__(kRedGrid) void mv_scale_ftran_final_kernel(int nparts, const Part* part, const double* __restrict__ lhs,
                                             const double* __restrict__ colscale, const double* __restrict__ invscale,
                                             const int* __restrict__ slice_of, int slice, const ipxint* __restrict__ basis, Scalars* S) {
-    __shared__ double sv[kRedGrid / 64], ss[kRedGrid / 64];
-    __shared__ int si[kRedGrid / 64], sc[kRedGrid / 64];
-    const bool have = (int)threadIdx.x < nparts;
-    double best = have ? part[threadIdx.x].v : 0.0, sum = have ? part[threadIdx.x].s : 0.0;
-    int bi = have ? part[threadIdx.x].i : INT_MAX, cnt = have ? part[threadIdx.x].c : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { sum += __shfl_xor(sum, d, 64); cnt += __shfl_xor(cnt, d, 64); }
-    if ((threadIdx.x & 63) == 0) { ss[threadIdx.x >> 6] = sum; sc[threadIdx.x >> 6] = cnt; }
-    final_argmax(best, bi, sv, si);                  // (its barrier also publishes ss / sc)
+    const Part all = block_partial<kRedGrid>(load_partial(nparts, part));
     if (threadIdx.x != 0) return;
-    for (int k = 1; k < kRedGrid / 64; k++) { sum += ss[k]; cnt += sc[k]; }
-    const int pmax = bi == INT_MAX ? 0 : bi;        // no entry qualified: position 0 (:325, :255-256)
+    const int pmax = all.i[0] == INT_MAX ? 0 : all.i[0];        // no entry qualified: position 0 (:325, :255-256)
     const double dj = colscale[S->jn];
     S->pmax = pmax;
     S->jb = (int)basis[pmax];
     S->vmax = fabs(lhs[pmax] * dj * invscale[pmax]);
-    S->weight_recomp = sum;
+    S->weight_recomp = all.s;
     S->colscale_jn = dj;
     S->invscale_pmax = invscale[pmax];
     S->pivot_col = lhs[pmax];
     S->used_pmax = slice_of[pmax] == slice ? 1 : 0;
-    S->eta_nnz = cnt;
+    S->eta_nnz = all.c;
 }
 // skipped column (:259-266)
 __global__ void mv_skip_kernel(const Scalars* S, double* colweights, double* colscale) {
@@ -542,8 +483,6 @@ __global__ void mvs_set_candidate_kernel(int j, double dj, Scalars* S) { S->jn =
 // squares of the scaled column (tblnnz, frobnorm_squared)
 __global__ __launch_bounds__(kBlock) void mvs_search_pivot_kernel(int m, const Scalars* S, const double* __restrict__ lhs,
                                                                   const double* __restrict__ invscale, Part* part) {
-    __shared__ double sv[kBlock / 64], ss[kBlock / 64];
-    __shared__ int si[kBlock / 64], sc[kBlock / 64];
     const double dj = S->colscale_jn;
     double best = 0.0, sum = 0.0;
     int bi = INT_MAX, cnt = 0;
@@ -553,44 +492,19 @@ __global__ __launch_bounds__(kBlock) void mvs_search_pivot_kernel(int m, const S
         sum += v * v;
         cnt += v != 0.0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(best, d, 64);
-        const int oi = __shfl_xor(bi, d, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        sum += __shfl_xor(sum, d, 64);
-        cnt += __shfl_xor(cnt, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; sv[w] = best; si[w] = bi; ss[w] = sum; sc[w] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kBlock / 64; k++) {
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-            sum += ss[k];
-            cnt += sc[k];
-        }
-        part[blockIdx.x] = Part{best, bi, sum, cnt};
-    }
+    const Part mine = block_partial<kBlock>(Part{{best}, {bi}, sum, cnt});
+    if (threadIdx.x == 0) part[blockIdx.x] = mine;
 }
 __global__ __launch_bounds__(kRedGrid) void mvs_search_pivot_final_kernel(int nparts, const Part* part, const double* __restrict__ lhs,
                                                                           const double* __restrict__ invscale, const ipxint* __restrict__ basis,
                                                                           Scalars* S) {
-    __shared__ double sv[kRedGrid / 64], ss[kRedGrid / 64];
-    __shared__ int si[kRedGrid / 64], sc[kRedGrid / 64];
-    const bool have = (int)threadIdx.x < nparts;
-    double best = have ? part[threadIdx.x].v : 0.0, sum = have ? part[threadIdx.x].s : 0.0;
-    int bi = have ? part[threadIdx.x].i : INT_MAX, cnt = have ? part[threadIdx.x].c : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { sum += __shfl_xor(sum, d, 64); cnt += __shfl_xor(cnt, d, 64); }
-    if ((threadIdx.x & 63) == 0) { ss[threadIdx.x >> 6] = sum; sc[threadIdx.x >> 6] = cnt; }
-    final_argmax(best, bi, sv, si);
+    const Part all = block_partial<kRedGrid>(load_partial(nparts, part));
     if (threadIdx.x != 0) return;
-    for (int k = 1; k < kRedGrid / 64; k++) { sum += ss[k]; cnt += sc[k]; }
-    const int pmax = bi == INT_MAX ? -1 : bi;
+    const int pmax = all.i[0] == INT_MAX ? -1 : all.i[0];
     S->pmax = pmax;
-    S->vmax = best;
-    S->weight_recomp = sum;                            // sum of squares of the scaled column
-    S->eta_nnz = cnt;                                  // # nonzeros of the column (its eta has one fewer)
+    S->vmax = all.v[0];
+    S->weight_recomp = all.s;                            // sum of squares of the scaled column
+    S->eta_nnz = all.c;                                  // # nonzeros of the column (its eta has one fewer)
     S->jb = pmax >= 0 ? (int)basis[pmax] : -1;
     S->pivot_col = pmax >= 0 ? lhs[pmax] : 0.0;
     S->invscale_pmax = pmax >= 0 ? invscale[pmax] : 0.0;
@@ -605,8 +519,7 @@ __global__ __launch_bounds__(kBlock) void mvs_pivot_row_kernel(int n, const int*
     if (j >= n) { if (threadIdx.x == 0) S->pivot_row = btran[j - n]; return; }
     // (sequential order of the column's entries for few entries; a fixed tree over the threads otherwise)
     for (int q = Ap[j] + threadIdx.x; q < Ap[j + 1]; q += kBlock) sum += Ax[q] * btran[Ai[q]];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0) { double t = 0.0; for (int k = 0; k < kBlock / 64; k++) t += red[k]; S->pivot_row = t; }

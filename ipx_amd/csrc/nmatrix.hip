@@ -33,12 +33,9 @@ namespace {
 
 using u64 = unsigned long long;
 constexpr int kTileShift = 42, kRowShift = 32;      // key = tile << 42 | row in tile << 32 | storage position
-#define IPXK_GS(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-int gridn(int64_t n) { return (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
 
 __global__ void nm_keep_kernel(int n, const double* __restrict__ W, const int* __restrict__ Ap, int* __restrict__ keep, int* __restrict__ len) {
-    IPXK_GS(j, n) {
+    IPXK_GRID_STRIDE(j, n) {
         const int k = W[j] != 0.0 ? 1 : 0;
         keep[j] = k;
         len[j] = k ? Ap[j + 1] - Ap[j] : 0;
@@ -46,7 +43,7 @@ __global__ void nm_keep_kernel(int n, const double* __restrict__ W, const int* _
 }
 __global__ void nm_colof_kernel(int n, const int* __restrict__ keep, const int* __restrict__ newidx, int* __restrict__ colof,
                                 int* __restrict__ newidx_or_minus) {
-    IPXK_GS(j, n) {
+    IPXK_GRID_STRIDE(j, n) {
         if (keep[j]) colof[newidx[j]] = (int)j;
         newidx_or_minus[j] = keep[j] ? newidx[j] : -1;
     }
@@ -54,23 +51,21 @@ __global__ void nm_colof_kernel(int n, const int* __restrict__ keep, const int* 
 // # columns whose kept flag differs from the previous build's (the exact test behind the fingerprint)
 __global__ void nm_diff_kernel(int n, const int* __restrict__ keep, const int* __restrict__ keep_prev, int* out) {
     int d = 0;
-    IPXK_GS(j, n) d += keep[j] != keep_prev[j] ? 1 : 0;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) d += __shfl_xor(d, s, 64);
+    IPXK_GRID_STRIDE(j, n) d += keep[j] != keep_prev[j] ? 1 : 0;
+    d = wave_sum(d);
     if ((threadIdx.x & 63) == 0 && d) atomicAdd(out, d);
 }
 // a 64-bit fingerprint of the kept set (order-independent sum of a hash of the kept indices)
 __global__ void nm_hash_kernel(int n, const int* __restrict__ keep, u64* out) {
     u64 h = 0;
-    IPXK_GS(j, n) if (keep[j]) { u64 x = (u64)j * 0x9E3779B97F4A7C15ull; x ^= x >> 29; h += x * 0xBF58476D1CE4E5B9ull; }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) h += __shfl_xor(h, d, 64);
+    IPXK_GRID_STRIDE(j, n) if (keep[j]) { u64 x = (u64)j * 0x9E3779B97F4A7C15ull; x ^= x >> 29; h += x * 0xBF58476D1CE4E5B9ull; }
+    h = wave_sum(h);
     if ((threadIdx.x & 63) == 0 && h) atomicAdd(out, h);
 }
 // keys of P1: one per entry of a kept column, in any order
 __global__ void nm_keys_p1_kernel(int n, const int* __restrict__ Ap, const int* __restrict__ Ai, const int* __restrict__ newidx,
                                   const int* __restrict__ off, int R, int ns, int slice, u64* __restrict__ keys) {
-    IPXK_GS(j, n) {
+    IPXK_GRID_STRIDE(j, n) {
         const int c = newidx[j];
         if (c < 0) continue;
         const u64 rb = (u64)(c / R), r = (u64)(c % R);
@@ -84,7 +79,7 @@ __global__ void nm_keys_p1_kernel(int n, const int* __restrict__ Ap, const int* 
 // keys of P2: entries of the row-wise copy whose column is kept; the others get the largest key (sorted to the end)
 __global__ void nm_keys_p2_kernel(int m, const int* __restrict__ Tp, const int* __restrict__ Ti, const int* __restrict__ newidx,
                                   int R, int ns, int slice, u64* __restrict__ keys) {
-    IPXK_GS(i, m) {
+    IPXK_GRID_STRIDE(i, m) {
         const u64 rb = (u64)(i / R), r = (u64)(i % R);
         for (int q = Tp[i]; q < Tp[i + 1]; q++) {
             const int c = newidx[Ti[q]];
@@ -93,7 +88,7 @@ __global__ void nm_keys_p2_kernel(int m, const int* __restrict__ Tp, const int* 
     }
 }
 __global__ void nm_tileptr_kernel(int ntiles, int64_t nz, const u64* __restrict__ keys, unsigned* __restrict__ ptr) {
-    IPXK_GS(t, (int64_t)ntiles + 1) {
+    IPXK_GRID_STRIDE(t, (int64_t)ntiles + 1) {
         const u64 want = (u64)t << kTileShift;
         int64_t lo = 0, hi = nz;
         while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (keys[mid] < want) lo = mid + 1; else hi = mid; }
@@ -104,7 +99,7 @@ __global__ void nm_tileptr_kernel(int ntiles, int64_t nz, const u64* __restrict_
 __global__ void nm_fill_kernel(int64_t nz, const u64* __restrict__ keys, int R, const int* __restrict__ src_idx,
                                const double* __restrict__ src_val, const int* __restrict__ newidx, int* __restrict__ cnt32,
                                int* __restrict__ idx, double* __restrict__ val) {
-    IPXK_GS(e, nz) {
+    IPXK_GRID_STRIDE(e, nz) {
         const u64 k = keys[e];
         const unsigned p = (unsigned)(k & 0xffffffffull);
         const int64_t slot = (int64_t)(k >> kTileShift) * R + (int64_t)((k >> kRowShift) & 1023ull);
@@ -115,7 +110,7 @@ __global__ void nm_fill_kernel(int64_t nz, const u64* __restrict__ keys, int R, 
     }
 }
 __global__ void nm_pack_counts_kernel(int64_t nslots, const int* __restrict__ cnt32, unsigned char* __restrict__ cnt, int* overflow) {
-    IPXK_GS(x, nslots) {
+    IPXK_GRID_STRIDE(x, nslots) {
         const int v = cnt32[x];
         if (v > 255) *overflow = 1;
         cnt[x] = (unsigned char)v;
@@ -123,13 +118,12 @@ __global__ void nm_pack_counts_kernel(int64_t nslots, const int* __restrict__ cn
 }
 __global__ void nm_max_tile_kernel(int ntiles, const unsigned* __restrict__ ptr, int* out) {
     int best = 0;
-    IPXK_GS(t, ntiles) best = max(best, (int)(ptr[t + 1] - ptr[t]));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) best = max(best, __shfl_xor(best, d, 64));
+    IPXK_GRID_STRIDE(t, ntiles) best = max(best, (int)(ptr[t + 1] - ptr[t]));
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0) atomicMax(out, best);
 }
 __global__ void nm_weights_kernel(int nN, const int* __restrict__ colof, const double* __restrict__ W, double* __restrict__ wN) {
-    IPXK_GS(c, nN) wN[c] = W[colof[c]];
+    IPXK_GRID_STRIDE(c, nN) wN[c] = W[colof[c]];
 }
 
 // ---- N in plain compact form (for the accumulated-tiles layout, layout_device.hip) ----
@@ -137,7 +131,7 @@ __global__ void nm_weights_kernel(int nN, const int* __restrict__ colof, const d
 __global__ void nm_csr1_kernel(int nN, int64_t nzN, const int* __restrict__ colof, const int* __restrict__ off, const int* __restrict__ Ap,
                                const int* __restrict__ Ai, const double* __restrict__ Ax, int* __restrict__ ptr, int* __restrict__ idx,
                                double* __restrict__ val) {
-    IPXK_GS(c, nN) {
+    IPXK_GRID_STRIDE(c, nN) {
         const int j = colof[c], o = off[j];
         ptr[c] = o;
         for (int p = Ap[j], q = o; p < Ap[j + 1]; p++, q++) { idx[q] = Ai[p]; val[q] = Ax[p]; }
@@ -146,7 +140,7 @@ __global__ void nm_csr1_kernel(int nN, int64_t nzN, const int* __restrict__ colo
 }
 // N by row of A: the entries whose column is kept, compact column index
 __global__ void nm_csr2_count_kernel(int m, const int* __restrict__ Tp, const int* __restrict__ Ti, const int* __restrict__ newidx, int* __restrict__ cnt) {
-    IPXK_GS(i, m) {
+    IPXK_GRID_STRIDE(i, m) {
         int k = 0;
         for (int q = Tp[i]; q < Tp[i + 1]; q++) k += newidx[Ti[q]] >= 0 ? 1 : 0;
         cnt[i] = k;
@@ -154,7 +148,7 @@ __global__ void nm_csr2_count_kernel(int m, const int* __restrict__ Tp, const in
 }
 __global__ void nm_csr2_fill_kernel(int m, int64_t nzN, const int* __restrict__ Tp, const int* __restrict__ Ti, const double* __restrict__ Tx,
                                     const int* __restrict__ newidx, int* __restrict__ ptr, int* __restrict__ idx, double* __restrict__ val) {
-    IPXK_GS(i, m) {
+    IPXK_GRID_STRIDE(i, m) {
         int o = ptr[i];
         for (int q = Tp[i]; q < Tp[i + 1]; q++) {
             const int c = newidx[Ti[q]];
@@ -215,9 +209,9 @@ static bool finish_layout(NMatrix& N, SlicedMatrix& P, int nrows, int R, int ns,
     const int ntiles = nrb * ns;
     P.R = R; P.nslices = ns; P.nrb = nrb; P.nrows_pad = nrb * R;
     P.tile_ptr.ensure((size_t)ntiles + 1);
-    hipLaunchKernelGGL(nm_tileptr_kernel, dim3(gridn(ntiles + 1)), dim3(kBlock), 0, s, ntiles, nz, keys, P.tile_ptr.get());
+    hipLaunchKernelGGL(nm_tileptr_kernel, dim3(grid_for(ntiles + 1)), dim3(kBlock), 0, s, ntiles, nz, keys, P.tile_ptr.get());
     IPXK_HIP(hipMemsetAsync(N.counters.get(), 0, 4 * sizeof(int), s));
-    hipLaunchKernelGGL(nm_max_tile_kernel, dim3(gridn(ntiles)), dim3(kBlock), 0, s, ntiles, P.tile_ptr.get(), N.counters.get());
+    hipLaunchKernelGGL(nm_max_tile_kernel, dim3(grid_for(ntiles)), dim3(kBlock), 0, s, ntiles, P.tile_ptr.get(), N.counters.get());
     int h[4] = {0, 0, 0, 0};
     IPXK_HIP(hipMemcpyAsync(h, N.counters.get(), sizeof h, hipMemcpyDeviceToHost, s));
     IPXK_HIP(hipStreamSynchronize(s));
@@ -228,9 +222,9 @@ static bool finish_layout(NMatrix& N, SlicedMatrix& P, int nrows, int R, int ns,
     IPXK_HIP(hipMemsetAsync(N.cnt32.get(), 0, (size_t)nslots * sizeof(int), s));
     P.idx.ensure((size_t)std::max<int64_t>(nz, 1)); P.val.ensure((size_t)std::max<int64_t>(nz, 1));
     P.cnt.ensure((size_t)nslots);
-    hipLaunchKernelGGL(nm_fill_kernel, dim3(gridn(nz)), dim3(kBlock), 0, s, nz, keys, R, src_idx, src_val, newidx, N.cnt32.get(),
+    hipLaunchKernelGGL(nm_fill_kernel, dim3(grid_for(nz)), dim3(kBlock), 0, s, nz, keys, R, src_idx, src_val, newidx, N.cnt32.get(),
                        P.idx.get(), P.val.get());
-    hipLaunchKernelGGL(nm_pack_counts_kernel, dim3(gridn(nslots)), dim3(kBlock), 0, s, nslots, N.cnt32.get(), P.cnt.get(), N.counters.get() + 1);
+    hipLaunchKernelGGL(nm_pack_counts_kernel, dim3(grid_for(nslots)), dim3(kBlock), 0, s, nslots, N.cnt32.get(), P.cnt.get(), N.counters.get() + 1);
     IPXK_HIP(hipMemcpyAsync(h, N.counters.get(), sizeof h, hipMemcpyDeviceToHost, s));
     IPXK_HIP(hipStreamSynchronize(s));
     if (h[1]) return false;                  // > 255 entries of a row in one slice: the byte counts cannot hold it
@@ -254,9 +248,9 @@ bool nmatrix_prepare(Context* c, const double* W) {
     IPXK_REQUIRE(c->have_plain, "no resident copy of the matrix");
     N.keep.ensure((size_t)n); N.len.ensure((size_t)n); N.newidx.ensure((size_t)n); N.off.ensure((size_t)n);
     N.counters.ensure(4); N.hash.ensure(1);
-    hipLaunchKernelGGL(nm_keep_kernel, dim3(gridn(n)), dim3(kBlock), 0, s, n, W, c->pl_Ap.get(), N.keep.get(), N.len.get());
+    hipLaunchKernelGGL(nm_keep_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, W, c->pl_Ap.get(), N.keep.get(), N.len.get());
     IPXK_HIP(hipMemsetAsync(N.hash.get(), 0, sizeof(u64), s));
-    hipLaunchKernelGGL(nm_hash_kernel, dim3(gridn(n)), dim3(kBlock), 0, s, n, N.keep.get(), N.hash.get());
+    hipLaunchKernelGGL(nm_hash_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, N.keep.get(), N.hash.get());
     u64 hsh = 0;
     IPXK_HIP(hipMemcpyAsync(&hsh, N.hash.get(), sizeof hsh, hipMemcpyDeviceToHost, s));
     IPXK_HIP(hipStreamSynchronize(s));
@@ -265,7 +259,7 @@ bool nmatrix_prepare(Context* c, const double* W) {
     bool same = N.valid && hsh == N.kept_hash && N.keep_built.size() >= (size_t)n;
     if (same) {
         IPXK_HIP(hipMemsetAsync(N.counters.get(), 0, sizeof(int), s));
-        hipLaunchKernelGGL(nm_diff_kernel, dim3(gridn(n)), dim3(kBlock), 0, s, n, N.keep.get(), N.keep_built.get(), N.counters.get());
+        hipLaunchKernelGGL(nm_diff_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, N.keep.get(), N.keep_built.get(), N.counters.get());
         int diff = 1;
         IPXK_HIP(hipMemcpyAsync(&diff, N.counters.get(), sizeof(int), hipMemcpyDeviceToHost, s));
         IPXK_HIP(hipStreamSynchronize(s));
@@ -288,7 +282,7 @@ bool nmatrix_prepare(Context* c, const double* W) {
         N.nN = nN;
         N.colof.ensure((size_t)nN);
         // (newidx becomes -1 on the columns that are not kept)
-        hipLaunchKernelGGL(nm_colof_kernel, dim3(gridn(n)), dim3(kBlock), 0, s, n, N.keep.get(), N.newidx.get(), N.colof.get(), N.newidx.get());
+        hipLaunchKernelGGL(nm_colof_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, N.keep.get(), N.newidx.get(), N.colof.get(), N.newidx.get());
         N.keys.ensure((size_t)c->nnz); N.keys2.ensure((size_t)c->nnz);
         // P1: rows = kept columns, gathered index = row of A
         int64_t slice1 = 0, slice2 = 0;
@@ -296,7 +290,7 @@ bool nmatrix_prepare(Context* c, const double* W) {
         N.P1 = SlicedMatrix(); N.P2 = SlicedMatrix();
         bool ok = false;
         for (int R = kSlicedRows; R >= kBlock && !ok; R /= 2) {
-            hipLaunchKernelGGL(nm_keys_p1_kernel, dim3(gridn(n)), dim3(kBlock), 0, s, n, c->pl_Ap.get(), c->pl_Ai.get(), N.newidx.get(), N.off.get(), R,
+            hipLaunchKernelGGL(nm_keys_p1_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, c->pl_Ap.get(), c->pl_Ai.get(), N.newidx.get(), N.off.get(), R,
                                ns1, (int)slice1, N.keys.get());
             sort_u64(N.T, N.keys.get(), N.keys2.get(), (size_t)nzN, s);
             ok = finish_layout(N, N.P1, nN, R, ns1, nzN, N.keys2.get(), c->pl_Ai.get(), c->pl_Ax.get(), nullptr, s);
@@ -304,7 +298,7 @@ bool nmatrix_prepare(Context* c, const double* W) {
         if (!ok) return false;
         ok = false;
         for (int R = kSlicedRows; R >= kBlock && !ok; R /= 2) {
-            hipLaunchKernelGGL(nm_keys_p2_kernel, dim3(gridn(m)), dim3(kBlock), 0, s, m, c->pl_Tp.get(), c->pl_Ti.get(), N.newidx.get(), R, ns2, (int)slice2,
+            hipLaunchKernelGGL(nm_keys_p2_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, c->pl_Tp.get(), c->pl_Ti.get(), N.newidx.get(), R, ns2, (int)slice2,
                                N.keys.get());
             sort_u64(N.T, N.keys.get(), N.keys2.get(), (size_t)c->nnz, s);      // the entries of dropped columns sort to the end
             ok = finish_layout(N, N.P2, m, R, ns2, nzN, N.keys2.get(), c->pl_Ti.get(), c->pl_Tx.get(), N.newidx.get(), s);
@@ -316,14 +310,14 @@ bool nmatrix_prepare(Context* c, const double* W) {
             std::unique_ptr<LayoutScratch, void (*)(LayoutScratch*)> LS(new_layout_scratch(), free_layout_scratch);
             const size_t nzn = (size_t)nzN;
             N.cptr.ensure((size_t)std::max(nN, m) + 1); N.cidx.ensure(nzn); N.cval.ensure(nzn);
-            hipLaunchKernelGGL(nm_csr1_kernel, dim3(gridn(nN)), dim3(kBlock), 0, s, nN, nzN, N.colof.get(), N.off.get(), c->pl_Ap.get(), c->pl_Ai.get(),
+            hipLaunchKernelGGL(nm_csr1_kernel, dim3(grid_for(nN)), dim3(kBlock), 0, s, nN, nzN, N.colof.get(), N.off.get(), c->pl_Ap.get(), c->pl_Ai.get(),
                                c->pl_Ax.get(), N.cptr.get(), N.cidx.get(), N.cval.get());
             AccMatrix a1, a2;
             const bool ok1 = device_build_acc(*LS, a1, N.P1, nN, m, nzN, N.cptr.get(), N.cidx.get(), N.cval.get(), s);
             N.cnt32.ensure((size_t)m + 1);
-            hipLaunchKernelGGL(nm_csr2_count_kernel, dim3(gridn(m)), dim3(kBlock), 0, s, m, c->pl_Tp.get(), c->pl_Ti.get(), N.newidx.get(), N.cnt32.get());
+            hipLaunchKernelGGL(nm_csr2_count_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, c->pl_Tp.get(), c->pl_Ti.get(), N.newidx.get(), N.cnt32.get());
             scan_int(N.T, N.cnt32.get(), N.cptr.get(), (size_t)m, s);
-            hipLaunchKernelGGL(nm_csr2_fill_kernel, dim3(gridn(m)), dim3(kBlock), 0, s, m, nzN, c->pl_Tp.get(), c->pl_Ti.get(), c->pl_Tx.get(),
+            hipLaunchKernelGGL(nm_csr2_fill_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, nzN, c->pl_Tp.get(), c->pl_Ti.get(), c->pl_Tx.get(),
                                N.newidx.get(), N.cptr.get(), N.cidx.get(), N.cval.get());
             const bool ok2 = device_build_acc(*LS, a2, N.P2, m, nN, nzN, N.cptr.get(), N.cidx.get(), N.cval.get(), s);
             if (ok1 && ok2) { N.A1 = std::move(a1); N.A2 = std::move(a2); }
@@ -337,7 +331,7 @@ bool nmatrix_prepare(Context* c, const double* W) {
             fprintf(stderr, "ipxk: N built on the device: %d of %d structural columns, %lld entries; N'u tiles %d x %d (rows %d), N t tiles %d x %d (rows %d)\n",
                     nN, n, (long long)nzN, N.P1.nrb, N.P1.nslices, N.P1.R, N.P2.nrb, N.P2.nslices, N.P2.R);
     }
-    hipLaunchKernelGGL(nm_weights_kernel, dim3(gridn(N.nN)), dim3(kBlock), 0, s, N.nN, N.colof.get(), W, N.wN.get());
+    hipLaunchKernelGGL(nm_weights_kernel, dim3(grid_for(N.nN)), dim3(kBlock), 0, s, N.nN, N.colof.get(), W, N.wN.get());
     IPXK_HIP(hipGetLastError());
     return true;
 }

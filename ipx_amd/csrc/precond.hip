@@ -291,8 +291,7 @@ __global__ __launch_bounds__(1024) void potrs_blocked_kernel(int k, const double
             const int r = tid >> 4, q = tid & 15;
             double s = 0.0;
             if (r < nb) for (int l = q; l <= r; l += 16) s += Ib[r + 64 * l] * x[b0 + l];
-#pragma unroll
-            for (int d = 8; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+            s = wave_sum<16>(s);
             if (q == 0) xb[r] = s;
         }
         __syncthreads();
@@ -320,8 +319,7 @@ __global__ __launch_bounds__(1024) void potrs_blocked_kernel(int k, const double
             const int r = tid >> 4, q = tid & 15;
             double s = 0.0;
             if (r < nb) for (int l = r + q; l < nb; l += 16) s += Ib[l + 64 * r] * x[b0 + l];    // inverse transposed
-#pragma unroll
-            for (int d = 8; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+            s = wave_sum<16>(s);
             if (q == 0) xb[r] = s;
         }
         __syncthreads();

@@ -36,9 +36,7 @@ namespace ipxk {
 
 namespace {
 
-int grid_for(int64_t n) { return (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
 
-#define IPXK_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 // ---- step 0: the factors must be what the contract says (lu_update.h:43-60) before any kernel trusts
 //      their indices: an out-of-range row index would be an out-of-bounds access on the device
@@ -79,10 +77,6 @@ __global__ void lt_rows_kernel(int m, int64_t nz, const ipxint* __restrict__ Lp,
                                double* __restrict__ rx) {
     IPXK_GRID_STRIDE(p, nz) { ri[p] = (int)Li[p]; rx[p] = Lx[p]; }
     IPXK_GRID_STRIDE(k, (int64_t)m + 1) rp[k] = (int)Lp[k];
-}
-
-__global__ void fill_double_kernel(int64_t n, double v, double* __restrict__ out) {
-    IPXK_GRID_STRIDE(i, n) out[i] = v;
 }
 
 // sort input for the row-wise form of L: key = row, value = entry, entries in storage order
@@ -207,11 +201,7 @@ __global__ __launch_bounds__(kBlock) void level_sweep_kernel(int dim, int ascend
                     else lv = l + 1 > lv ? l + 1 : lv;
                 }
                 if (__all(ready)) {
-#pragma unroll
-                    for (int d = 32; d >= 1; d >>= 1) {
-                        const int o = __shfl_xor(lv, d, 64);
-                        lv = o > lv ? o : lv;
-                    }
+                    lv = wave_max(lv);
                     if (lane == src) {
                         __hip_atomic_store(level + i, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         finished = true;
@@ -282,11 +272,7 @@ __global__ __launch_bounds__(kRelaxLongThreads) void relax_long_rows_kernel(int 
             const int l = __hip_atomic_load(level + ri[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
             lv = l > lv ? l : lv;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const int o = __shfl_xor(lv, d, 64);
-            lv = o > lv ? o : lv;
-        }
+        lv = wave_max(lv);
         if (lane == 0) red[wave] = lv;
         __syncthreads();
         if (tid == 0) {
@@ -313,11 +299,7 @@ __global__ __launch_bounds__(kBlock) void relax_long_rows_parallel_kernel(int nl
             const int l = __hip_atomic_load(level + ri[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
             lv = l > lv ? l : lv;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const int o = __shfl_xor(lv, d, 64);
-            lv = o > lv ? o : lv;
-        }
+        lv = wave_max(lv);
         if (lane == 0 && lv > level[i]) {
             __hip_atomic_store(level + i, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             *changed = 1;
@@ -671,7 +653,7 @@ void finish_sweep(Context* c, Scratch& W, Sweep& S, bool level_launches, int dim
         S.posof.ensure((size_t)std::max(dim, 1));
         IPXK_HIP(hipMemsetAsync(S.order.get(), 0xff, sizeof(int) * np1, s));
         IPXK_HIP(hipMemsetAsync(S.len.get(), 0, sizeof(int) * np1, s));
-        if (npos > 0) hipLaunchKernelGGL(fill_double_kernel, dim3(grid_for(npos)), dim3(kBlock), 0, s, (int64_t)npos, 1.0, S.diag.get());
+        if (npos > 0) hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for(npos)), dim3(kBlock), 0, s, (int64_t)npos, 1.0, S.diag.get());
         slots = 0;
         if (dim > 0) {
             W.lpos.ensure(lpos.size()); W.lsub.ensure(lsub.size());
@@ -842,7 +824,7 @@ void analyse_sweeps_resident(Context* c, SplitOperator* S, const DeviceFactors& 
     // --- L' sweep: unknown k gathers column k of L (rows > k), descending, unit diagonal
     hipLaunchKernelGGL(lt_rows_kernel, dim3(grid_for(std::max<int64_t>(nzL, m + 1))), dim3(kBlock), 0, s, m, nzL,
                        dLp.get(), dLi.get(), dLx.get(), W.rp.get(), W.ri.get(), W.rx.get());
-    hipLaunchKernelGGL(fill_double_kernel, dim3(g), dim3(kBlock), 0, s, (int64_t)m, 1.0, W.dgn.get());
+    hipLaunchKernelGGL(fill_kernel<double>, dim3(g), dim3(kBlock), 0, s, (int64_t)m, 1.0, W.dgn.get());
     S->Lt.newest_first = true;      // a row's first entries (rows k+1, k+2, ... of column k) are the unknowns solved last
     finish_sweep(c, W, S->Lt, ll, m, nzL, false, false, 0, [&](std::vector<int>& lv) {
         H.fetch(F, m, s);

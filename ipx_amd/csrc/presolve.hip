@@ -10,15 +10,11 @@
 
 #include <cmath>
 
-#include "internal.hpp"
+#include "device_utils.hpp"
 
 namespace ipxk {
 
 namespace {
-
-int grid_for(int64_t n) { return (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
-
-#define IPXK_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 constexpr int kExpMin = 0, kExpMax = 3, kMaxRound = 10;     // src/presolver.cc:906-908
 
@@ -75,7 +71,6 @@ __global__ void rescale_kernel(int64_t n, const ipxint* __restrict__ Ap, const i
     }
 }
 
-__global__ void fill_kernel(int64_t n, double v, double* __restrict__ x) { IPXK_GRID_STRIDE(i, n) x[i] = v; }
 __global__ void narrow_index_kernel(int64_t nz, const ipxint* __restrict__ in, int* __restrict__ out, int limit, int* bad) {
     IPXK_GRID_STRIDE(p, nz) {
         const ipxint v = in[p];
@@ -150,8 +145,8 @@ void equilibrate_device(int device, int64_t m, int64_t n, const ipxint* Ap, cons
         hipLaunchKernelGGL(narrow_index_kernel, dim3(grid_for(nz)), dim3(kBlock), 0, s, nz, dAi64.get(), dAi.get(), (int)m, flags.get() + 1);
         hipLaunchKernelGGL(out_of_range_kernel, dim3(grid_for(nz)), dim3(kBlock), 0, s, nz, dAx.get(), flags.get());
     }
-    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, 1.0, cs.get());
-    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, 1.0, rs.get());
+    hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for(n)), dim3(kBlock), 0, s, n, 1.0, cs.get());
+    hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for(m)), dim3(kBlock), 0, s, m, 1.0, rs.get());
     int h[2] = {0, 0};
     flags.download(h, 2, s);
     IPXK_REQUIRE(h[1] == 0, "row index out of range");

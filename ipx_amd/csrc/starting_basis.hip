@@ -50,56 +50,14 @@ struct SbScalars {
     double delta_obj;         // objective change along the primal / dual ray
 };
 
-struct SbPart { double v1; int i1; double v2; int i2; double s; int c; };
+using SbPart = Partial<2>;       // two indexed bests, a sum, a count (device_utils.hpp)
 
-int grid_for(int64_t n) { return (int)std::min<int64_t>(kSbGrid, std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
-#define SB_GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-__device__ __forceinline__ void take_larger(double& v, int& i, double ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
-__device__ __forceinline__ void wave_argmax(double& v, int& i) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(v, d, 64);
-        const int oi = __shfl_xor(i, d, 64);
-        take_larger(v, i, ov, oi);
-    }
-}
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    return s;
-}
-// the workgroup's partial: wavefront trees, then the wavefronts in order; valid in thread 0
-template <int kThreads>
-__device__ __forceinline__ SbPart block_partial(SbPart p) {
-    __shared__ SbPart sh[kThreads / 64];
-    wave_argmax(p.v1, p.i1);
-    wave_argmax(p.v2, p.i2);
-    p.s = wave_sum(p.s);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) p.c += __shfl_xor(p.c, d, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = p;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int k = 1; k < kThreads / 64; k++) {
-            take_larger(p.v1, p.i1, sh[k].v1, sh[k].i1);
-            take_larger(p.v2, p.i2, sh[k].v2, sh[k].i2);
-            p.s += sh[k].s;
-            p.c += sh[k].c;
-        }
-    return p;
-}
-__device__ __forceinline__ SbPart load_partial(int nparts, const SbPart* part) {
-    return (int)threadIdx.x < nparts ? part[threadIdx.x] : SbPart{0.0, INT_MAX, 0.0, INT_MAX, 0.0, 0};
-}
 
 // ---- weights and the model vectors of the ray tests ---------------------------------------------------------------------
 // starting_basis.cc:138-146: the scaling factor, inf exactly for lb = -inf, ub = +inf, and 0 where lb == ub
 __global__ void sb_weights_kernel(int64_t N, const double* __restrict__ d, const double* __restrict__ lb, const double* __restrict__ ub,
                                   double* __restrict__ w, int* bad) {
-    SB_GRID_STRIDE(j, N) {
+    IPXK_GRID_STRIDE(j, N) {
         const bool free_bounds = isinf(lb[j]) && isinf(ub[j]);
         const double dj = d[j];
         if (free_bounds ? !(isinf(dj) && dj > 0.0) : !isfinite(dj)) atomicMin(bad, (int)j);
@@ -110,7 +68,7 @@ __global__ void sb_weights_kernel(int64_t N, const double* __restrict__ d, const
 __global__ void sb_b_minus_fixed_kernel(int m, int n, const int* __restrict__ Tp, const int* __restrict__ Ti, const double* __restrict__ Tx,
                                         const double* __restrict__ b, const double* __restrict__ lb, const double* __restrict__ ub,
                                         double* __restrict__ out) {
-    SB_GRID_STRIDE(i, m) {
+    IPXK_GRID_STRIDE(i, m) {
         double v = b[i];
         for (int q = Tp[i]; q < Tp[i + 1]; q++) {
             const int j = Ti[q];
@@ -121,8 +79,8 @@ __global__ void sb_b_minus_fixed_kernel(int m, int n, const int* __restrict__ Tp
     }
 }
 __global__ void sb_slack_basis_kernel(int m, int n, ipxint* __restrict__ basis, int* __restrict__ posof) {
-    SB_GRID_STRIDE(j, (int64_t)n + m) posof[j] = j >= n ? (int)(j - n) : -1;
-    SB_GRID_STRIDE(i, m) basis[i] = n + i;
+    IPXK_GRID_STRIDE(j, (int64_t)n + m) posof[j] = j >= n ? (int)(j - n) : -1;
+    IPXK_GRID_STRIDE(i, m) basis[i] = n + i;
 }
 __global__ void sb_set_kernel(int jn, int pmax, int jb, SbScalars* S) { S->mv.jn = jn; S->mv.pmax = pmax; S->mv.jb = jb; }
 
@@ -131,13 +89,13 @@ __global__ void sb_set_kernel(int jn, int pmax, int jb, SbScalars* S) { S->mv.jn
 // s: sum of c_j f_p over the free ones, c: # nonzeros of the column
 __global__ __launch_bounds__(kBlock) void sb_column_kernel(int m, const double* __restrict__ lhs, const ipxint* __restrict__ basis,
                                                            const double* __restrict__ w, const double* __restrict__ cc, SbPart* part) {
-    SbPart p{0.0, INT_MAX, 0.0, INT_MAX, 0.0, 0};
-    SB_GRID_STRIDE(q, m) {
+    SbPart p = partial_identity<2>();
+    IPXK_GRID_STRIDE(q, m) {
         const double x = lhs[q], f = fabs(x);
         const ipxint j = basis[q];
-        if (f > p.v1) { p.v1 = f; p.i1 = (int)q; }
+        if (f > p.v[0]) { p.v[0] = f; p.i[0] = (int)q; }
         if (isinf(w[j])) p.s += cc[j] * x;
-        else if (f > p.v2) { p.v2 = f; p.i2 = (int)q; }
+        else if (f > p.v[1]) { p.v[1] = f; p.i[1] = (int)q; }
         p.c += x != 0.0;
     }
     p = block_partial<kBlock>(p);
@@ -152,13 +110,13 @@ __global__ __launch_bounds__(kSbGrid) void sb_column_final_kernel(int nparts, co
     if (threadIdx.x != 0) return;
     S->mv.eta_nnz = p.c;
     if (!free_loop) { S->mv.pivot_col = lhs[S->mv.pmax]; return; }
-    const int pmax = p.i1 == INT_MAX ? -1 : p.i1, pmax_nonfree = p.i2 == INT_MAX ? -1 : p.i2;
-    S->vmax = p.v1; S->imax = pmax;
-    S->vmax_class = p.v2; S->imax_class = pmax_nonfree;
+    const int pmax = p.i[0] == INT_MAX ? -1 : p.i[0], pmax_nonfree = p.i[1] == INT_MAX ? -1 : p.i[1];
+    S->vmax = p.v[0]; S->imax = pmax;
+    S->vmax_class = p.v[1]; S->imax_class = pmax_nonfree;
     S->delta_obj = cc[S->mv.jn] - p.s;
     int decision, pos;
-    if (p.v1 > 4.0 && p.v2 < 1.0) { decision = kSbStability; pos = pmax; }
-    else if (p.v2 <= dependency_tol) { decision = kSbDependent; pos = -1; }
+    if (p.v[0] > 4.0 && p.v[1] < 1.0) { decision = kSbStability; pos = pmax; }
+    else if (p.v[1] <= dependency_tol) { decision = kSbDependent; pos = -1; }
     else { decision = kSbExchange; pos = pmax_nonfree; }
     S->decision = decision;
     S->mv.pmax = pos;                                   // (-1: the unit vector of the row pivot is zero, its result unused)
@@ -175,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void sb_row_kernel(int n, int64_t N, const 
                                                         const double* __restrict__ Ax, const double* __restrict__ btran,
                                                         const int* __restrict__ posof, const double* __restrict__ w,
                                                         double* __restrict__ row, SbPart* part) {
-    SbPart p{0.0, INT_MAX, 0.0, INT_MAX, 0.0, 0};
+    SbPart p = partial_identity<2>();
     const int lane = threadIdx.x & (kRowLanes - 1), sub = threadIdx.x / kRowLanes;
     // (the trip count is the same for every thread of the workgroup: the lane exchanges below run with all lanes active)
     for (int64_t base = (int64_t)blockIdx.x * kRowCols; base < N; base += (int64_t)gridDim.x * kRowCols) {
@@ -184,15 +142,14 @@ __global__ __launch_bounds__(kBlock) void sb_row_kernel(int n, int64_t N, const 
         double sum = 0.0;
         if (nonbasic && j < n)
             for (int q = Ap[j] + lane; q < Ap[j + 1]; q += kRowLanes) sum += Ax[q] * btran[Ai[q]];
-#pragma unroll
-        for (int d = kRowLanes / 2; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+        sum = wave_sum<kRowLanes>(sum);
         if (lane == 0 && j < N) {
             if (nonbasic && j >= n) sum = btran[j - n];
             row[j] = sum;
             const double r = fabs(sum), wj = w[j];
             if (j >= n || wj != 0.0) {
-                if (r > p.v1) { p.v1 = r; p.i1 = (int)j; }
-                if (wj != 0.0 && r > p.v2) { p.v2 = r; p.i2 = (int)j; }
+                if (r > p.v[0]) { p.v[0] = r; p.i[0] = (int)j; }
+                if (wj != 0.0 && r > p.v[1]) { p.v[1] = r; p.i[1] = (int)j; }
             }
         }
     }
@@ -203,21 +160,21 @@ __global__ __launch_bounds__(kBlock) void sb_row_kernel(int n, int64_t N, const 
 __global__ __launch_bounds__(kSbGrid) void sb_row_final_kernel(int nparts, const SbPart* part, double dependency_tol, SbScalars* S) {
     const SbPart p = block_partial<kSbGrid>(load_partial(nparts, part));
     if (threadIdx.x != 0) return;
-    S->vmax = p.v1; S->imax = p.i1 == INT_MAX ? -1 : p.i1;
-    S->vmax_class = p.v2; S->imax_class = p.i2 == INT_MAX ? -1 : p.i2;
-    S->decision = (p.v1 > 4.0 && p.v2 < 1.0) ? kSbStability : p.v2 <= dependency_tol ? kSbDependent : kSbExchange;
-    S->threshold = 0.1 * p.v2;
+    S->vmax = p.v[0]; S->imax = p.i[0] == INT_MAX ? -1 : p.i[0];
+    S->vmax_class = p.v[1]; S->imax_class = p.i[1] == INT_MAX ? -1 : p.i[1];
+    S->decision = (p.v[0] > 4.0 && p.v[1] < 1.0) ? kSbStability : p.v[1] <= dependency_tol ? kSbDependent : kSbExchange;
+    S->threshold = 0.1 * p.v[1];
 }
 // basis.cc:893-905: among the numerically stable pivots the one that maximizes the volume
 __global__ __launch_bounds__(kBlock) void sb_row_scaled_kernel(int64_t N, const double* __restrict__ row, const double* __restrict__ w,
                                                                const SbScalars* S, SbPart* part) {
-    SbPart p{0.0, INT_MAX, 0.0, INT_MAX, 0.0, 0};
+    SbPart p = partial_identity<2>();
     const double threshold = S->threshold;
-    SB_GRID_STRIDE(j, N) {
+    IPXK_GRID_STRIDE(j, N) {
         const double r = fabs(row[j]);
         if (r >= threshold) {
             const double rscaled = r * w[j];
-            if (rscaled > p.v1) { p.v1 = rscaled; p.i1 = (int)j; }
+            if (rscaled > p.v[0]) { p.v[0] = rscaled; p.i[0] = (int)j; }
         }
     }
     p = block_partial<kBlock>(p);
@@ -225,8 +182,8 @@ __global__ __launch_bounds__(kBlock) void sb_row_scaled_kernel(int64_t N, const 
 }
 // the dual ray (basis.cc:876-884): btran' (b - sum of the fixed columns)
 __global__ __launch_bounds__(kBlock) void sb_dot_kernel(int m, const double* __restrict__ u, const double* __restrict__ v, SbPart* part) {
-    SbPart p{0.0, INT_MAX, 0.0, INT_MAX, 0.0, 0};
-    SB_GRID_STRIDE(i, m) p.s += u[i] * v[i];
+    SbPart p = partial_identity<2>();
+    IPXK_GRID_STRIDE(i, m) p.s += u[i] * v[i];
     p = block_partial<kBlock>(p);
     if (threadIdx.x == 0) part[blockIdx.x] = p;
 }
@@ -237,7 +194,7 @@ __global__ __launch_bounds__(kSbGrid) void sb_row_choice_kernel(int nparts_scale
     __syncthreads();                                    // (the shared partials are written again)
     const SbPart pd = block_partial<kSbGrid>(load_partial(nparts_dot, part_dot));
     if (threadIdx.x != 0) return;
-    S->jscaled = ps.i1 == INT_MAX ? -1 : ps.i1;
+    S->jscaled = ps.i[0] == INT_MAX ? -1 : ps.i[0];
     S->delta_obj = pd.s;
     int jn = S->mv.jb;
     if (S->decision == kSbStability && S->imax >= 0) jn = S->imax;
@@ -257,7 +214,7 @@ __global__ void sb_exchange_kernel(const SbScalars* S, ipxint* basis, int* posof
 __global__ void sb_make_fixed_kernel(int64_t N, const int* __restrict__ posof, const double* __restrict__ lb, const double* __restrict__ ub,
                                      double* __restrict__ x, double* __restrict__ xl, double* __restrict__ xu, double* __restrict__ zl,
                                      double* __restrict__ zu, unsigned char* __restrict__ state) {
-    SB_GRID_STRIDE(j, N)
+    IPXK_GRID_STRIDE(j, N)
         if (lb[j] == ub[j] && posof[j] < 0) { x[j] = lb[j]; xl[j] = xu[j] = zl[j] = zu[j] = 0.0; state[j] = IPXK_STATE_FIXED; }
 }
 // dx[j] = -x[j] and rhs += x[j] a_j for the dependent free columns, one after the other in the order of the list (one workgroup)
@@ -273,25 +230,25 @@ __global__ __launch_bounds__(kBlock) void sb_dependent_columns_kernel(int ndep, 
     }
 }
 __global__ void sb_scatter_basic_kernel(int m, const ipxint* __restrict__ basis, const double* __restrict__ dxbasic, double* __restrict__ dx) {
-    SB_GRID_STRIDE(p, m) dx[basis[p]] = dxbasic[p];
+    IPXK_GRID_STRIDE(p, m) dx[basis[p]] = dxbasic[p];
 }
 // dy[p] = -y[i] at the positions of the dependent rows' slacks (list: rows i)
 __global__ void sb_dependent_rows_rhs_kernel(int ndep, const int* __restrict__ list, int n, const int* __restrict__ posof,
                                              const double* __restrict__ y, double* __restrict__ dy) {
-    SB_GRID_STRIDE(k, ndep) dy[posof[n + list[k]]] = -y[list[k]];
+    IPXK_GRID_STRIDE(k, ndep) dy[posof[n + list[k]]] = -y[list[k]];
 }
 __global__ void sb_dependent_rows_exact_kernel(int ndep, const int* __restrict__ list, const double* __restrict__ y, double* __restrict__ dy) {
-    SB_GRID_STRIDE(k, ndep) dy[list[k]] = -y[list[k]];              // "would be already in exact arithmetic"
+    IPXK_GRID_STRIDE(k, ndep) dy[list[k]] = -y[list[k]];              // "would be already in exact arithmetic"
 }
 // make_fixed(j, 0.0) for the dependent columns; make_implied_eq for the slacks of the dependent rows (device state FREE)
 __global__ void sb_make_dependent_kernel(int ncols, const int* __restrict__ cols, int nrows, const int* __restrict__ rows, int n,
                                          double* __restrict__ x, double* __restrict__ xl, double* __restrict__ xu, double* __restrict__ zl,
                                          double* __restrict__ zu, unsigned char* __restrict__ state) {
-    SB_GRID_STRIDE(k, ncols) {
+    IPXK_GRID_STRIDE(k, ncols) {
         const int j = cols[k];
         x[j] = 0.0; xl[j] = xu[j] = zl[j] = zu[j] = 0.0; state[j] = IPXK_STATE_FIXED;
     }
-    SB_GRID_STRIDE(k, nrows) {
+    IPXK_GRID_STRIDE(k, nrows) {
         const int j = n + rows[k];
         xl[j] = xu[j] = __builtin_huge_val(); zl[j] = zu[j] = 0.0; state[j] = IPXK_STATE_FREE;
     }
@@ -336,7 +293,7 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
     PinnedScalars pinned;
     SbScalars* S = scalars.get();
     IPXK_HIP(hipMemsetAsync(S, 0, sizeof(SbScalars), s));
-    const int gm = grid_for(m), gN = grid_for(N);
+    const int gm = grid_for(m, kSbGrid), gN = grid_for(N, kSbGrid);
     const int grow = (int)std::min<int64_t>(kSbGrid, (N + kRowCols - 1) / kRowCols);
 
     // ---- 1. weights (starting_basis.cc:138-146)
@@ -519,13 +476,13 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
         }
         if (nr > 0) {
             rows_dev.upload(dependent_rows, s);
-            hipLaunchKernelGGL(sb_dependent_rows_rhs_kernel, dim3(grid_for(nr)), dim3(kBlock), 0, s, nr, rows_dev.get(), n, posof.get(),
+            hipLaunchKernelGGL(sb_dependent_rows_rhs_kernel, dim3(grid_for(nr, kSbGrid)), dim3(kBlock), 0, s, nr, rows_dev.get(), n, posof.get(),
                                c->it_y.get(), dy.get());
             solve_dense_dev(c, dy.get(), dy.get(), 'T');
-            hipLaunchKernelGGL(sb_dependent_rows_exact_kernel, dim3(grid_for(nr)), dim3(kBlock), 0, s, nr, rows_dev.get(), c->it_y.get(), dy.get());
+            hipLaunchKernelGGL(sb_dependent_rows_exact_kernel, dim3(grid_for(nr, kSbGrid)), dim3(kBlock), 0, s, nr, rows_dev.get(), c->it_y.get(), dy.get());
         }
         iterate_update_dev(c, 1.0, dx.get(), nullptr, nullptr, 1.0, dy.get(), nullptr, nullptr);
-        hipLaunchKernelGGL(sb_make_dependent_kernel, dim3(grid_for(std::max(nc, nr))), dim3(kBlock), 0, s, nc, cols_dev.get(), nr, rows_dev.get(), n,
+        hipLaunchKernelGGL(sb_make_dependent_kernel, dim3(grid_for(std::max(nc, nr), kSbGrid)), dim3(kBlock), 0, s, nc, cols_dev.get(), nr, rows_dev.get(), n,
                            c->it_x.get(), c->it_xl.get(), c->it_xu.get(), c->it_zl.get(), c->it_zu.get(), c->it_state.get());
         IPXK_HIP(hipStreamSynchronize(s));      // (the index lists go out of scope)
     }

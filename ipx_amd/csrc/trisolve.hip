@@ -539,8 +539,7 @@ __global__ __launch_bounds__(kBlock) void block_gather_kernel(SweepView S, int K
         const double b = xin[zsrc[t]];
         double s2 = 0.0;
         for (int e = hptr[t] + g; e < e1; e += 32) s2 += S.val[hslot[e]] * y[hidx[e]];
-#pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) s2 += __shfl_xor(s2, d, 64);
+        s2 = wave_sum<32>(s2);
         if (g == 0) {
             const double r = b - s2;
             z[t] = pre_scale ? r / pre_scale[unk[t]] : r;
@@ -602,8 +601,7 @@ __global__ __launch_bounds__(kBlock) void block_gemv_kernel(int K, const double*
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int r = 0; r < R; r++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) acc[r] += __shfl_xor(acc[r], d, 64);
+        wave_sum_each(acc[r]);
         if (lane == 0) red[r][wave] = acc[r];
     }
     __syncthreads();
@@ -656,8 +654,7 @@ __global__ __launch_bounds__(kBlock) void block_probe_mz_kernel(int K, const dou
     for (int i = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); i < K; i += gridDim.x * (kBlock / 64)) {
         double s0 = 0.0, s1 = 0.0;
         for (int l = lane; l <= i; l += 64) { const double a = M[(size_t)i * K + l]; s0 += a * probe_z(0, l); s1 += a * probe_z(1, l); }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { s0 += __shfl_xor(s0, d, 64); s1 += __shfl_xor(s1, d, 64); }
+        wave_sum_each(s0, s1);
         if (lane == 0) { w[i] = s0; w[K + i] = s1; }
     }
 }
@@ -680,8 +677,7 @@ __global__ __launch_bounds__(kBlock) void bump_probe_mz_kernel(int kb, const dou
     for (int i = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); i < kb; i += gridDim.x * (kBlock / 64)) {
         double s0 = 0.0, s1 = 0.0;
         for (int l = lane; l < kb; l += 64) { const double a = inv[(size_t)i * kb + l]; s0 += a * probe_z(0, l); s1 += a * probe_z(1, l); }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { s0 += __shfl_xor(s0, d, 64); s1 += __shfl_xor(s1, d, 64); }
+        wave_sum_each(s0, s1);
         if (lane == 0) { w[i] = s0; w[kb + i] = s1; }
     }
 }
@@ -1327,8 +1323,7 @@ __device__ __forceinline__ void bump_solve_lds(int kb, const double* __restrict_
                 double s2 = 0.0;
                 if (r < nb)
                     for (int l = g; l < nb; l += 16) s2 += (TRANS ? Ib[l + 64 * r] : Ib[r + 64 * l]) * x[b0 + l];
-#pragma unroll
-                for (int d = 8; d >= 1; d >>= 1) s2 += __shfl_xor(s2, d, 64);
+                s2 = wave_sum<16>(s2);
                 if (g == 0 && r < 64) xb[r] = s2;
             }
             __syncthreads();
@@ -1413,8 +1408,7 @@ __global__ __launch_bounds__(kBlock) void bump_gemv_kernel(int kb, const double*
         const double* row = M + (size_t)i * kb;
         double s2 = 0.0;
         for (int l = lane; l < kb; l += 64) s2 += row[l] * x[l];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s2 += __shfl_xor(s2, d, 64);
+        s2 = wave_sum(s2);
         if (lane == 0) y[pos[i]] = s2;
     }
 }
