@@ -41,7 +41,7 @@ struct Reordered {
 struct SplitOperator;   // trisolve.hip
 struct PrepareHost;     // trisolve.hip
 struct LuState;         // lu.hip
-struct MaxvolState;     // maxvolume.hip
+struct MaxvolState;     // internal.hpp
 struct NMatrix;         // nmatrix.hip
 
 struct Context {
@@ -143,8 +143,8 @@ struct Context {
     PrepareHost* prepare_host = nullptr;   // host workspaces of split_prepare (trisolve.hip)
     LuState* lu = nullptr;                 // factors of the last ipxk_lu_factorize* (lu.hip)
     DevBuf<double> dense_work;             // workspace of the dense block inverse (dense_inverse.hip), grow-only
-    MaxvolState* maxvol = nullptr;         // workspaces of ipxk_maxvolume (maxvolume.hip)
-    bool etas_live = false;                // the operator `split` stands for a LATER basis than its factors: Maxvolume's last exchanges are applied as etas behind them (maxvolume.hip)
+    MaxvolState* maxvol = nullptr;         // workspaces of the basis exchanges (basis.hip, maxvolume.hip, starting_basis.hip)
+    bool etas_live = false;                // the operator `split` stands for a LATER basis than its factors: Maxvolume's last exchanges are applied as etas behind them (basis.hip)
     NMatrix* nmat = nullptr;               // N of the split operator as a matrix of its own (nmatrix.hip)
     // the factors, the operator and these statuses are the result of ipxk_ipm_starting_basis (starting_basis.hip): the main phase
     // (ipm_driver_dev with use_basis) goes on from them instead of the slack basis
@@ -370,6 +370,7 @@ void maxvolume_sequential_dev(Context* c, const ipxint* status, const double* co
                               ipxint max_etas, ipxint* basis_out, ipxint* status_out, ipxk_maxvolume_info* info, ipxint* log,
                               ipxint log_cap);
 void destroy_maxvol(MaxvolState*);
+// ---- basis.hip (EtaFile, DeviceBasis: internal.hpp) ----
 bool tighten_pivottol(double& pivottol);                            // Basis::TightenLuPivotTol; false at the top of the ladder
 void mv_scatter_column(Context* c, const MvScalars* S, double* rhs);       // rhs[m] = column S->jn of AI
 void mv_unit_vector(Context* c, const MvScalars* S, double* v);            // v[m] = e_(S->pmax)

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -458,7 +459,7 @@ struct CrState {
 };
 
 // ---------------------------------------------------------------------------
-// the basis exchanges of maxvolume.hip and starting_basis.hip
+// the basis exchanges of maxvolume.hip and starting_basis.hip: the eta file and the device Basis (basis.hip)
 // ---------------------------------------------------------------------------
 // the scalars of one exchange step, written by the device, read by the host
 struct MvScalars {
@@ -506,7 +507,7 @@ struct MaxvolState {
 
 struct Context;
 
-// The etas of the exchanges since the last refactorization (maxvolume.hip has the methods and what they cost)
+// The etas of the exchanges since the last refactorization (basis.hip has the methods and what they cost)
 struct EtaFile {
     Context* c;
     MaxvolState& M;
@@ -537,5 +538,44 @@ struct EtaFile {
     void apply(bool transposed, double* v);
     static void apply_etas(MaxvolState& M, int m, int K, int cap, bool dense, bool transposed, double* v, hipStream_t s, int Kd = 0);
 };
+
+// The reference's Basis (src/basis.cc) for one call of a driver that exchanges on the device -- maxvolume_dev, maxvolume_sequential_dev,
+// ipm_starting_basis_dev -- on the resident factors plus the eta file.  A candidate goes  ftran / btran_unit  (and the driver's own pivot
+// search), one read-back of its scalars, then  exchange_if_stable  ->  the driver's exchange kernel  ->  commit.
+struct DeviceBasis {
+    Context* c;
+    MaxvolState& M;
+    const int m;
+    EtaFile etas;
+    double& pivottol;                          // the context's LU pivot tolerance (Context::maxvol_pivottol), tightened by the ladder
+    std::vector<ipxint> basis_h, status_h;     // host mirrors (refactorizations, results); filled by the driver before the first exchange
+    const double* colscale;                    // host, n + m: what split_prepare_lu is given on a refactorization
+    MvScalars* S;                              // device: jn, pmax, jb and the pivots of the current candidate
+    double *rhs, *lhs, *unit, *btran;          // m-vectors of MaxvolState
+    // factorizations counts every attempt, as the reference's num_factorizations_++ does, singular those that found the basis singular
+    // (errflag 301): the starting basis reports the attempts, Maxvolume has always reported factorizations - singular.
+    int64_t refused = 0, factorizations = 0, singular = 0;
+    ipxint errflag = 0;
+
+    DeviceBasis(Context* ctx, MaxvolState& state, ipxint max_etas, bool resume, const double* colscale_in, MvScalars* scalars);
+    void ftran();                              // lhs = inverse(B) a_(S->jn), the etas applied
+    void btran_unit();                         // btran = inverse(B') e_(S->pmax), the etas applied
+    bool refactorize();                        // false: the basis is singular, errflag 301
+    // a: the host's copy of *S with both pivots.  true: the exchange is accepted and its eta appended -- the driver launches its exchange
+    // kernel and calls commit.  false: try the candidate again (the pivot tolerance is tightened where the factors were fresh, the basis
+    // refactorized) unless errflag is set (306: the ladder is at its top, 301)
+    bool exchange_if_stable(const MvScalars& a);
+    void commit(const MvScalars& a);           // the host mirrors; a refactorization when the eta file is full (errflag 301 if that fails)
+};
+
+// the one device -> host copy of a candidate's scalars, through a pinned block
+template <class T>
+T read_scalars(const T* dev, T* pinned, hipStream_t s) {
+    IPXK_HIP(hipMemcpyAsync(pinned, dev, sizeof(T), hipMemcpyDeviceToHost, s));
+    IPXK_HIP(hipStreamSynchronize(s));
+    return *pinned;
+}
+
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace ipxk

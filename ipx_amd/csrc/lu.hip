@@ -836,7 +836,6 @@ __global__ void lu_basis_fill_kernel(int m, int n, const ipxint* __restrict__ ba
     }
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // the n rows (columns) whose stage is < 0, in ascending order: list[rank] = index, loc[index] = rank or -1
 void compact_active(hipStream_t s, Tmp& T, int n, const int* stage, int* flag, int* rank, int* loc, int* list) {

@@ -3,10 +3,8 @@
 // (src/basis.cc:353-385: PivotFreeVariablesIntoBasis :676-781, PivotFixedVariablesOutOfBasis :783-930), the status changes
 // with make_fixed (:153-173) and PostprocessDependencies (:52-126).
 //
-// The machinery is Maxvolume's (maxvolume.hip): FTRAN and BTRAN are the two sweep pairs on the resident factors
-// (solve_dense_dev) plus the product-form etas of the exchanges since the last factorization (EtaFile), an exchange is accepted
-// when the pivot from the row agrees with the pivot from the column to 1e-8 relative, else the pivot tolerance is tightened and
-// the basis refactorized (Basis::ExchangeIfStable, src/basis.cc:286-321).  What is new here:
+// The basis itself is DeviceBasis (basis.hip), shared with Maxvolume: FTRAN and BTRAN on the resident factors plus the eta file,
+// Basis::Factorize and Basis::ExchangeIfStable (src/basis.cc:286-321).  What is here:
 //   * sb_column_kernel: the maxima of the tableau column over all positions and over those whose basic variable is not free,
 //     the objective change of the primal ray and the column's number of nonzeros, in one pass over m;
 //   * sb_row_kernel: the tableau row AI' btran over all n + m columns with the maxima of its two classes fused in -- one
@@ -21,7 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -254,8 +251,6 @@ __global__ void sb_make_dependent_kernel(int ncols, const int* __restrict__ cols
     }
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 struct PinnedScalars {
     SbScalars* h = nullptr;
     PinnedScalars() { IPXK_HIP(hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(SbScalars))); }
@@ -285,7 +280,7 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
     M.part.ensure(kSbGrid); M.scalars.ensure(1);
 
     DevBuf<double> w((size_t)N), row((size_t)N), dx((size_t)N);
-    DevBuf<double> rhs((size_t)m), lhs((size_t)m), unit((size_t)m), btran((size_t)m), bfix((size_t)m), dy((size_t)m);
+    DevBuf<double> bfix((size_t)m), dy((size_t)m);
     DevBuf<int> posof((size_t)N), flag(1);
     DevBuf<ipxint> basis((size_t)m);
     DevBuf<SbPart> part(kSbGrid), part_dot(kSbGrid);
@@ -318,84 +313,50 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
 
     // ---- 2. the slack basis (Basis::SetToSlackBasis), its factors and the operator the sweeps run on.  Inside the two loops every
     // basic variable is BASIC and every other one NONBASIC, as in the reference, and the operator's scaling is not used.
-    std::vector<ipxint> basis_h((size_t)m), status_h((size_t)N);
+    const std::vector<double> ones((size_t)N, 1.0);
+    DeviceBasis B(c, M, max_etas, false, ones.data(), &S->mv);
+    std::vector<ipxint> &basis_h = B.basis_h, &status_h = B.status_h;
     std::vector<int> pos_h((size_t)N, -1);
+    status_h.resize((size_t)N);
     for (int j = 0; j < n; j++) status_h[(size_t)j] = IPXK_NONBASIC;
     for (int i = 0; i < m; i++) { status_h[(size_t)n + i] = IPXK_BASIC; basis_h[(size_t)i] = n + i; pos_h[(size_t)n + i] = i; }
-    const std::vector<double> ones((size_t)N, 1.0);
-    double& pivottol = c->maxvol_pivottol;
-    EtaFile etas(c, M, m, max_etas);
-    int& K = etas.K;
-    auto refactorize = [&]() {                   // Basis::Factorize (src/basis.cc:116-156) + the operator of the sweeps
-        ipxk_lu_info li{};
-        lu_factorize_basis(c, basis_h.data(), pivottol, false, &li);
-        I.factorizations++;
-        if (li.num_dependent > 0) { I.errflag = 301; return false; }      // IPX_ERROR_basis_singular (:131-137)
-        split_prepare_lu(c, status_h.data(), ones.data());
-        etas.reset((int)li.bump);
-        return true;
-    };
     hipLaunchKernelGGL(sb_slack_basis_kernel, dim3(gN), dim3(kBlock), 0, s, m, n, basis.get(), posof.get());
-    (void)refactorize();
+    (void)B.refactorize();
 
     auto poll_interrupt = [&]() -> ipxint {
         if (interrupt) return interrupt(user);
         return c->interrupt ? c->interrupt(c->interrupt_user) : 0;
     };
-    auto read_scalars = [&]() -> SbScalars {     // the one device -> host copy of a candidate
-        IPXK_HIP(hipMemcpyAsync(pinned.h, S, sizeof(SbScalars), hipMemcpyDeviceToHost, s));
-        IPXK_HIP(hipStreamSynchronize(s));
-        return *pinned.h;
-    };
-    auto ftran = [&]() {                         // lhs = inverse(B) a_(S->mv.jn)
-        mv_scatter_column(c, &S->mv, rhs.get());
-        solve_dense_dev(c, rhs.get(), lhs.get(), 'N');
-        etas.apply(false, lhs.get());
-    };
-    auto btran_unit = [&]() {                    // btran = inverse(B') e_(S->mv.pmax)
-        mv_unit_vector(c, &S->mv, unit.get());
-        etas.apply(true, unit.get());
-        solve_dense_dev(c, unit.get(), btran.get(), 'T');
-    };
-    // Basis::ExchangeIfStable (:286-321) from the two pivots of a.  Returns false when the candidate is to be tried again (or errflag is set).
-    auto exchange_if_stable = [&](const SbScalars& a) {
-        const double pc = a.mv.pivot_col, pr = a.mv.pivot_row;
-        const bool stable = pc != 0.0 && std::abs(pc - pr) <= 1e-8 * std::abs(pc);
-        if (!stable) {
-            if (K == 0 && !tighten_pivottol(pivottol)) { I.errflag = 306; return false; }      // IPX_ERROR_basis_too_ill_conditioned
-            (void)refactorize();
-            return false;
-        }
-        etas.append(&S->mv, lhs.get(), a.mv.eta_nnz);
+    // an accepted exchange: this driver's part between DeviceBasis::exchange_if_stable and commit.  Returns false when the candidate is to
+    // be tried again (or B.errflag is set).
+    auto exchange = [&](const SbScalars& a) {
+        if (!B.exchange_if_stable(a.mv)) return false;
         hipLaunchKernelGGL(sb_exchange_kernel, dim3(1), dim3(1), 0, s, S, basis.get(), posof.get());
         if (log && I.updates_start < log_cap) { log[2 * I.updates_start] = a.mv.jb; log[2 * I.updates_start + 1] = a.mv.jn; }
         I.updates_start++;
-        basis_h[(size_t)a.mv.pmax] = a.mv.jn;
         pos_h[(size_t)a.mv.jn] = a.mv.pmax;
         pos_h[(size_t)a.mv.jb] = -1;
-        status_h[(size_t)a.mv.jn] = IPXK_BASIC;
-        status_h[(size_t)a.mv.jb] = IPXK_NONBASIC;
-        if (etas.full()) (void)refactorize();                                                   // NeedFreshFactorization (:318-319)
+        B.commit(a.mv);
         return true;
     };
 
     // ---- 3. Basis::PivotFreeVariablesIntoBasis (:676-781)
     std::vector<int> dependent_cols, dependent_rows;
     std::vector<ipxint> remaining;
-    if (!I.errflag)
+    if (!B.errflag)
         for (int64_t j = 0; j < N; j++)
             if (std::isinf(w_h[(size_t)j]) && pos_h[(size_t)j] < 0) remaining.push_back(j);
-    while (!remaining.empty() && !I.errflag) {
+    while (!remaining.empty() && !B.errflag) {
         const ipxint jn = remaining.back();
-        if ((I.errflag = poll_interrupt()) != 0) break;
+        if ((B.errflag = poll_interrupt()) != 0) break;
         hipLaunchKernelGGL(sb_set_kernel, dim3(1), dim3(1), 0, s, (int)jn, -1, -1, S);
-        ftran();
-        hipLaunchKernelGGL(sb_column_kernel, dim3(gm), dim3(kBlock), 0, s, m, lhs.get(), basis.get(), w.get(), cc, part.get());
-        hipLaunchKernelGGL(sb_column_final_kernel, dim3(1), dim3(kSbGrid), 0, s, gm, part.get(), 1, dependency_tol, cc, lhs.get(), basis.get(), S);
+        B.ftran();
+        hipLaunchKernelGGL(sb_column_kernel, dim3(gm), dim3(kBlock), 0, s, m, B.lhs, basis.get(), w.get(), cc, part.get());
+        hipLaunchKernelGGL(sb_column_final_kernel, dim3(1), dim3(kSbGrid), 0, s, gm, part.get(), 1, dependency_tol, cc, B.lhs, basis.get(), S);
         // the BTRAN of the leaving variable (ExchangeIfStable with sys = -1, :292-293): pivot from the row
-        btran_unit();
-        mv_pivot_from_row(c, btran.get(), &S->mv);
-        const SbScalars a = read_scalars();
+        B.btran_unit();
+        mv_pivot_from_row(c, B.btran, &S->mv);
+        const SbScalars a = read_scalars(S, pinned.h, s);
         if (a.decision == kSbDependent) {
             // jn cannot be pivoted into the basis; the first such column that changes the objective is an unbounded primal ray
             if (!I.cols_inconsistent && std::abs(a.delta_obj) > dependency_tol) I.cols_inconsistent = 1;
@@ -404,32 +365,32 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
             remaining.pop_back();
             continue;
         }
-        if (!exchange_if_stable(a)) continue;                   // "factorization was unstable, try again"
+        if (!exchange(a)) continue;                             // "factorization was unstable, try again"
         remaining.pop_back();
         if (a.decision == kSbStability) { remaining.push_back(a.mv.jb); I.stability_pivots++; }
     }
 
     // ---- 4. Basis::PivotFixedVariablesOutOfBasis (:783-930)
     remaining.clear();
-    if (!I.errflag)
+    if (!B.errflag)
         for (int64_t j = n; j < N; j++)
             if (w_h[(size_t)j] == 0.0 && pos_h[(size_t)j] >= 0) remaining.push_back(j);
-    while (!remaining.empty() && !I.errflag) {
+    while (!remaining.empty() && !B.errflag) {
         const ipxint jb = remaining.back();
-        if ((I.errflag = poll_interrupt()) != 0) break;
+        if ((B.errflag = poll_interrupt()) != 0) break;
         hipLaunchKernelGGL(sb_set_kernel, dim3(1), dim3(1), 0, s, (int)jb, pos_h[(size_t)jb], (int)jb, S);
-        btran_unit();
-        hipLaunchKernelGGL(sb_row_kernel, dim3(grow), dim3(kBlock), 0, s, n, N, c->pl_Ap.get(), c->pl_Ai.get(), c->pl_Ax.get(), btran.get(),
+        B.btran_unit();
+        hipLaunchKernelGGL(sb_row_kernel, dim3(grow), dim3(kBlock), 0, s, n, N, c->pl_Ap.get(), c->pl_Ai.get(), c->pl_Ax.get(), B.btran,
                            posof.get(), w.get(), row.get(), part.get());
         hipLaunchKernelGGL(sb_row_final_kernel, dim3(1), dim3(kSbGrid), 0, s, grow, part.get(), dependency_tol, S);
         hipLaunchKernelGGL(sb_row_scaled_kernel, dim3(gN), dim3(kBlock), 0, s, N, row.get(), w.get(), S, part.get());
-        hipLaunchKernelGGL(sb_dot_kernel, dim3(gm), dim3(kBlock), 0, s, m, btran.get(), bfix.get(), part_dot.get());
+        hipLaunchKernelGGL(sb_dot_kernel, dim3(gm), dim3(kBlock), 0, s, m, B.btran, bfix.get(), part_dot.get());
         hipLaunchKernelGGL(sb_row_choice_kernel, dim3(1), dim3(kSbGrid), 0, s, gN, part.get(), gm, part_dot.get(), row.get(), S);
         // the FTRAN of the entering variable (ExchangeIfStable with sys = +1, :290-291): pivot from the column, and the eta
-        ftran();
-        hipLaunchKernelGGL(sb_column_kernel, dim3(gm), dim3(kBlock), 0, s, m, lhs.get(), basis.get(), w.get(), cc, part.get());
-        hipLaunchKernelGGL(sb_column_final_kernel, dim3(1), dim3(kSbGrid), 0, s, gm, part.get(), 0, dependency_tol, cc, lhs.get(), basis.get(), S);
-        const SbScalars a = read_scalars();
+        B.ftran();
+        hipLaunchKernelGGL(sb_column_kernel, dim3(gm), dim3(kBlock), 0, s, m, B.lhs, basis.get(), w.get(), cc, part.get());
+        hipLaunchKernelGGL(sb_column_final_kernel, dim3(1), dim3(kSbGrid), 0, s, gm, part.get(), 0, dependency_tol, cc, B.lhs, basis.get(), S);
+        const SbScalars a = read_scalars(S, pinned.h, s);
         if (a.decision == kSbDependent) {
             // jb cannot be pivoted out of the basis; the first such row that changes the dual objective is an unbounded dual ray
             if (!I.rows_inconsistent && std::abs(a.delta_obj) > dependency_tol) I.rows_inconsistent = 1;
@@ -438,14 +399,16 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
             remaining.pop_back();
             continue;
         }
-        if (!exchange_if_stable(a)) continue;
+        if (!exchange(a)) continue;
         remaining.pop_back();
         if (a.decision == kSbStability) { remaining.push_back(a.mv.jn); I.stability_pivots++; }
     }
     IPXK_HIP(hipStreamSynchronize(s));
     check_sweep_abort(c);
     // fresh factors of the final basis: what the solves below and the main phase's Maxvolume start from
-    if (!I.errflag && K > 0) (void)refactorize();
+    if (!B.errflag && B.etas.K > 0) (void)B.refactorize();
+    I.errflag = B.errflag;
+    I.factorizations = B.factorizations;       // every attempt, as the reference's num_factorizations_
     if (I.errflag) {
         I.seconds = now_s() - t_start;
         if (info) *info = I;
@@ -468,11 +431,11 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
         IPXK_HIP(hipMemsetAsync(dy.get(), 0, (size_t)m * sizeof(double), s));
         if (nc > 0) {
             cols_dev.upload(dependent_cols, s);
-            IPXK_HIP(hipMemsetAsync(rhs.get(), 0, (size_t)m * sizeof(double), s));
+            IPXK_HIP(hipMemsetAsync(B.rhs, 0, (size_t)m * sizeof(double), s));
             hipLaunchKernelGGL(sb_dependent_columns_kernel, dim3(1), dim3(kBlock), 0, s, nc, cols_dev.get(), c->pl_Ap.get(), c->pl_Ai.get(),
-                               c->pl_Ax.get(), c->it_x.get(), dx.get(), rhs.get());
-            solve_dense_dev(c, rhs.get(), lhs.get(), 'N');
-            hipLaunchKernelGGL(sb_scatter_basic_kernel, dim3(gm), dim3(kBlock), 0, s, m, basis.get(), lhs.get(), dx.get());
+                               c->pl_Ax.get(), c->it_x.get(), dx.get(), B.rhs);
+            solve_dense_dev(c, B.rhs, B.lhs, 'N');
+            hipLaunchKernelGGL(sb_scatter_basic_kernel, dim3(gm), dim3(kBlock), 0, s, m, basis.get(), B.lhs, dx.get());
         }
         if (nr > 0) {
             rows_dev.upload(dependent_rows, s);

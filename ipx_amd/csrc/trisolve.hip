@@ -1801,7 +1801,7 @@ void split_rescale_host(Context* c, const ipxint* status, const double* colscale
     IPXK_HIP(hipStreamSynchronize(c->stream));
 }
 
-// ---- the operator behind an eta file (Context::etas_live, maxvolume.hip) ----
+// ---- the operator behind an eta file (Context::etas_live, basis.hip) ----
 // B_new = B_old E (E the product of Maxvolume's last exchanges, acting on vectors by basis position), hence with the column scaling S of
 // the NEW basis   inverse(B~) = inverse(S) inverse(E) inverse(U) inverse(L),   inverse(B~') = inverse(L') inverse(U') inverse(E') inverse(S):
 // the UNSCALED sweeps of the resident factors, the eta file between them and the scaling, and the scaling as a vector operation.
