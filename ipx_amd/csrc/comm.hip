@@ -438,6 +438,34 @@ void agree_on_arguments(Context* c, const std::string& err, uint64_t h, const ch
         throw Error(IPXK_E_ARGUMENT, std::string("the replicated arguments of ") + who + " (" + what + ") differ between the ranks");
 }
 
+// this rank's first structural column and the structural columns of all ranks (slabs contiguous, in rank order):
+// one all-gather of n_local, once per communicator (comm_destroy forgets them); 0 and n without one
+void learn_col_offsets(Context* c) {
+    if (c->col_offset >= 0) return;
+    if (!comm_cols(c)) {
+        c->col_offset = 0;
+        c->n_global = c->n;
+        return;
+    }
+    const int R = c->nranks;
+    hipStream_t s = c->stream;
+    DevBuf<double> mine(1), all((size_t)R);
+    const double nl = (double)c->n;
+    mine.upload(&nl, 1, s);
+    comm_allgather(c, mine.get(), all.get(), 1);
+    std::vector<double> h((size_t)R);
+    all.download(h.data(), (size_t)R, s);
+    IPXK_HIP(hipStreamSynchronize(s));
+    comm_check(c);
+    int64_t c0 = 0, total = 0;
+    for (int r = 0; r < R; r++) {
+        if (r < c->rank) c0 += (int64_t)h[(size_t)r];
+        total += (int64_t)h[(size_t)r];
+    }
+    c->col_offset = c0;
+    c->n_global = total;
+}
+
 void comm_destroy(Context* c) {
     c->col_offset = -1;
     c->n_global = 0;

@@ -38,8 +38,8 @@ struct Reordered {
     bool in_use = false;                 // set around the CR loop of kkt_diag_solve_dev: operator and preconditioner take the copy
 };
 
-struct SplitOperator;   // trisolve.hip
-struct PrepareHost;     // trisolve.hip
+struct SplitOperator;   // trisolve.hpp
+struct PrepareHost;     // prepare_device.hip
 struct LuState;         // lu.hip
 struct MaxvolState;     // internal.hpp
 struct NMatrix;         // nmatrix.hip
@@ -132,7 +132,7 @@ struct Context {
     DevBuf<double> ipm[12];            // residuals, complementarity targets and the step of ipxk_ipm_step
 
     // ---- basis path ----
-    // guard of the explicit inverses (trisolve.hip): # probes and # inverses rejected since the context was created, worst residual
+    // guard of the explicit inverses (inverse_guard.hpp): # probes and # inverses rejected since the context was created, worst residual
     struct { long inverse_probes = 0, inverse_rejected = 0, inverse_refined = 0; double worst_probe = 0.0; } split_stats;
     SplitOperator* split = nullptr;
     SplitOperator* split_spare = nullptr;  // the operator's buffers after ipxk_reset_solver_state: reused by the next Prepare, never applied
@@ -140,7 +140,7 @@ struct Context {
     // solver object, like Basis::TightenLuPivotTol changes lu_->pivottol() for good (src/basis.cc:490-503); ipxk_reset_solver_state
     // sets it again (src/basis.cc:30: every Basis starts from control.lu_pivottol())
     double maxvol_pivottol = 0.1;
-    PrepareHost* prepare_host = nullptr;   // host workspaces of split_prepare (trisolve.hip)
+    PrepareHost* prepare_host = nullptr;   // host workspaces of split_prepare (prepare_device.hip)
     LuState* lu = nullptr;                 // factors of the last ipxk_lu_factorize* (lu.hip)
     DevBuf<double> dense_work;             // workspace of the dense block inverse (dense_inverse.hip), grow-only
     MaxvolState* maxvol = nullptr;         // workspaces of the basis exchanges (basis.hip, maxvolume.hip, starting_basis.hip)
@@ -325,7 +325,7 @@ CrResult kkt_diag_solve_dev(Context* c, const double* a, const double* b, double
                             ipxint maxiter, double* x, double* y, ipxk_interrupt_fn interrupt,
                             void* user, ipxk_times* times);
 
-// ---- trisolve.hip ----
+// ---- trisolve.hip (the operator), sweep.hip (forward_ / backward_solve_dev, split_levels, check_sweep_abort), kkt_basis.hip ----
 void split_prepare_host(Context* c, const ipxint* Lp, const ipxint* Li, const double* Lx,
                         const ipxint* Up, const ipxint* Ui, const double* Ux, const ipxint* rowperm,
                         const ipxint* colperm, const ipxint* basis, const ipxint* status,
@@ -402,6 +402,14 @@ void comm_destroy(Context* c);
 void comm_check(Context* c);             // raises if a collective of the direct transport timed out
 double* comm_stage(Context* c, size_t count);
 void comm_allreduce_sum_staged(Context* c, double* dst, size_t count);
+// dst = sum over the ranks of what produce(out) writes to out: the direct exchange's buffer where it offers one
+template <class F>
+void allreduce_product(Context* c, double* dst, size_t count, F produce) {
+    double* stage = comm_stage(c, count);
+    produce(stage ? stage : dst);
+    if (stage) comm_allreduce_sum_staged(c, dst, count);
+    else comm_allreduce_sum(c, dst, count);
+}
 // all-gather of one row of k doubles per rank (device); returns the nranks x k table, rank-major, on the host
 std::vector<double> comm_gather_table(Context* c, const double* row_dev, size_t k);
 
@@ -423,7 +431,7 @@ struct Fingerprint {
 // fingerprints differ; `who` names the call, `what` the replicated arguments.
 void agree_on_arguments(Context* c, const std::string& err, uint64_t h, const char* who, const char* what);
 // column partition: this rank's first structural column and the structural columns of all ranks (Context::col_offset,
-// n_global), one all-gather at the first call that needs them (trisolve.hip); 0 and n on any other context
+// n_global), one all-gather at the first call that needs them; 0 and n on any other context
 void learn_col_offsets(Context* c);
 
 }  // namespace ipxk

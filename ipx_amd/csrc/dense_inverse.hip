@@ -2,11 +2,11 @@
 //   D22 = (L22 + I) U22   (kb x kb, column major: U22 on and above the diagonal, L22 below -- LAPACK's LU storage)
 //   inverse(D22) = inverse(U22) * inverse(L22 + I)
 // Both triangular inverses by recursive doubling from the inverted 64 x 64 diagonal blocks (bump_invert_blocks_kernel,
-// trisolve.hip):   [A 0; B C]^-1 = [A^-1 0; -C^-1 B A^-1, C^-1],   [A B; 0 C]^-1 = [A^-1, -A^-1 B C^-1; 0, C^-1]
+// dense_bump.hip):   [A 0; B C]^-1 = [A^-1 0; -C^-1 B A^-1, C^-1],   [A B; 0 C]^-1 = [A^-1, -A^-1 B C^-1; 0, C^-1]
 // -- per level two batched products over all pairs of blocks, then one product of the two triangular inverses.  Every
 // product is one launch of a tiled fp64 GEMM on v_mfma_f64_16x16x4_f64 that skips the k-tiles a triangular operand
 // makes zero.  Measured on the MI355X: see profiles/r04_dense_inverse.txt (round 3: own kernel 134 ms / rocBLAS 4.8 ms
-// at 4096 rows).  The result is probed like every explicit inverse (trisolve.hip: the guard) before it is used.
+// at 4096 rows).  The result is probed like every explicit inverse (inverse_guard.hpp: the guard) before it is used.
 #include "context.hpp"
 
 namespace ipxk {

@@ -448,7 +448,7 @@ __global__ __launch_bounds__(kCoopThreads) __attribute__((amdgpu_waves_per_eu(1,
     const int row0 = part * R * kCoopThreads;
     if (tid == 0) { sh.abort = 0; sh.part = part; sh.G = G; sh.plain = 0; }
     if (C.xcd_mode && tid < 64) {
-        // the placement is an observation, not a contract (as for the one-XCD runs of the sweeps, trisolve.hip): every participant
+        // the placement is an observation, not a contract (as for the one-XCD runs of the sweeps, sweep.hip): every participant
         // publishes the XCD it runs on and reads everybody else's; plain stores only if all agree -- all see the same ids and decide alike
         unsigned xcc = 0;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));

@@ -149,7 +149,7 @@ __global__ void u_diag_kernel(int m, const ipxint* __restrict__ Up, const double
 
 // ---- step 2 (round 3): levels in ONE launch ---------------------------------------------------------------
 // The processing order of a sweep (ascending / descending unknowns) is a topological order of its dependency graph,
-// so the levels can be computed the way the sweeps themselves run (trisolve.hip): level[] starts at -1 = "not known",
+// so the levels can be computed the way the sweeps themselves run (sweep.hip): level[] starts at -1 = "not known",
 // wavefront w of the W resident ones takes the 64-row chunks w, w + W, ... of the processing order, a row polls the
 // levels of its dependencies (L1-bypassing loads) until all are known and stores max + 1 -- the value is the flag.  The
 // lowest unfinished row depends only on finished ones, so the launch always makes progress, whatever the placement;
@@ -476,7 +476,7 @@ void finish_sweep(Context* c, Scratch& W, Sweep& S, bool level_launches, int dim
     if (!W.h_flag) IPXK_HIP(hipHostMalloc(reinterpret_cast<void**>(&W.h_flag), sizeof(int)));
     bool have_levels = false;
     if (dim > 0 && !(getenv("IPXK_LEVEL_SWEEP") && getenv("IPXK_LEVEL_SWEEP")[0] == '0')) {
-        if (W.level_grid < 0) {                                   // per context, i.e. per device (as the sweeps' grid, trisolve.hip)
+        if (W.level_grid < 0) {                                   // per context, i.e. per device (as the sweeps' grid, sweep.hip)
             int dev = 0, per_cu = 0;
             hipDeviceProp_t prop;
             W.level_grid = 0;

@@ -1,7 +1,12 @@
-// Shared declarations of the basis-preconditioned operator: level-ordered triangular factors on the
-// device (trisolve.hip: sweep kernels, solves; prepare_device.hip: device-side analysis and packing).
+// Shared declarations of the basis-preconditioned operator: level-ordered triangular factors on the device.
+//   trisolve.hip        the operator: Prepare, rescale, _Apply, SolveDense
+//   sweep.hip           the level-scheduled sweeps;  sweep_blocks.hip: their inverted head / tail blocks
+//   dense_bump.hip      the dense bump of an LU between the two sweeps of a pair
+//   kkt_basis.hip       KKTSolverBasis::_Solve
+//   prepare_device.hip  device-side analysis and packing
 #pragma once
 
+#include <initializer_list>
 #include <vector>
 
 #include "internal.hpp"
@@ -70,7 +75,7 @@ struct Sweep {
     DevBuf<ChunkDesc> chunks;
     DevBuf<int> order;             // [npos] unknown at a position (-1: padding)
     DevBuf<int> posof;             // [dim]  position of an unknown
-    DevBuf<int> src;               // [npos] right-hand-side index (composed with the producer's layout, trisolve.hip)
+    DevBuf<int> src;               // [npos] right-hand-side index (composed with the producer's layout, finish_prepare in trisolve.hip)
     DevBuf<int> idx, len;
     DevBuf<double> y;              // [npos] result of the sweep, by position
     DevBuf<double> val, diag;      // as given
@@ -81,7 +86,7 @@ struct Sweep {
     struct Launch { int c0, c1; int kind; bool merged; };   // merged: the run contains merged chunks
     std::vector<int> merged_prefix;  // host, [nchunks+1] number of merged chunks before chunk c
     std::vector<Launch> plan;
-    // INVERTED BLOCKS (large factors; build_sweep_blocks, trisolve.hip).  The first levels of the transposed sweeps
+    // INVERTED BLOCKS (large factors; build_sweep_blocks, sweep_blocks.hip).  The first levels of the transposed sweeps
     // and the last levels of every sweep hold few unknowns each -- the planted C3 factors: 36 levels for the first
     // 6384 unknowns of U', 37 levels for the last 1059 of L, whose rows are the longest of the matrix -- and cost one
     // hand-off each however little work they carry.  With the unknowns of such a run of levels as block 2 of
@@ -141,37 +146,58 @@ struct SplitOperator {
     // Dense bump of the factorization (factors that came from the device LU): with the bump's block D22 =
     // (L22+I) U22 cut out of L and U,  (L+I) U = (L~+I) blockdiag(I, D22) U~,  L~ = L without L22, U~ = U with U22
     // replaced by I.  The level-scheduled sweeps run on L~ and U~ (no chain as long as the bump), and BETWEEN the
-    // two sweeps of a pair one workgroup solves with the dense block in place (bump_solve_kernel, trisolve.hip).
-    int bump_start = 0, bump_size = 0;     // 0: no dense block
-    DevBuf<double> bumpD;                  // bump_size^2, column major: U22 on and above the diagonal, L22 below
-    DevBuf<double> bump_invL, bump_invU;   // inverted 64 x 64 diagonal blocks of L22+I and of U22
-    // large blocks: inverse(D22) itself, row major, and its transpose (bump_size^2 each; empty for small blocks) --
-    // the solve between the sweeps of a pair is then ONE matrix-vector product spread over the chip
-    DevBuf<double> bump_inv, bump_invT, bump_x;
-    DevBuf<double> bump_gx;                // blocks too large for LDS: the unknowns of the one-workgroup blocked solve (2 x bump_size)
-    bool bump_explicit = false;
-    DevBuf<double> bump_probe;             // workspace of the guard of the explicit inverse
-    DevBuf<int> bump_pos_fwd, bump_pos_bwd;   // position of bump unknown t in the result of the L sweep / of the U' sweep
-    // workspaces of Prepare kept from one call to the next (grow-only): the factors as uploaded, the factors with the
-    // dense block cut out
-    DevBuf<ipxint> in_Lp, in_Li, in_Up, in_Ui, cut_Lp, cut_Up, cut_Ui;
-    DevBuf<double> in_Lx, in_Ux, cut_Ux;
-    DevBuf<int> cut_cnt, cut_start;
+    // two sweeps of a pair one workgroup solves with the dense block in place (bump_solve_kernel, dense_bump.hip).
+    struct DenseBump {
+        int start = 0, size = 0;           // 0: no dense block
+        DevBuf<double> D;                  // size^2, column major: U22 on and above the diagonal, L22 below
+        DevBuf<double> invL, invU;         // inverted 64 x 64 diagonal blocks of L22+I and of U22
+        // large blocks: inverse(D22) itself, row major, and its transpose (size^2 each; empty for small blocks) --
+        // the solve between the sweeps of a pair is then ONE matrix-vector product spread over the chip
+        DevBuf<double> inv, invT, x;
+        DevBuf<double> gx;                 // blocks too large for LDS: the unknowns of the one-workgroup blocked solve (2 x size)
+        bool explicit_inverse = false;
+        DevBuf<double> probe;              // workspace of the guard of the explicit inverse
+        DevBuf<int> pos_fwd, pos_bwd;      // position of bump unknown t in the result of the L sweep / of the U' sweep
+        // workspaces of the cut kept from one Prepare to the next (grow-only): the factors with the dense block cut out
+        DevBuf<ipxint> cut_Lp, cut_Up, cut_Ui;
+        DevBuf<double> cut_Ux;
+        DevBuf<int> cut_cnt, cut_start;
+    } bump;
+    // workspaces of Prepare kept from one call to the next (grow-only): the factors as uploaded
+    DevBuf<ipxint> in_Lp, in_Li, in_Up, in_Ui;
+    DevBuf<double> in_Lx, in_Ux;
     // where basis position p lives in this rank's local (n+m)-vectors (loc_map()): 0..n-1 a structural column of this
     // rank, n..n+m-1 a slack column (every rank), -1 a structural column of another rank.  Unpartitioned, that is basis[p]
     // itself; on a column-partitioned context (comm_cols, part) basis[] holds GLOBAL column numbers, replicated on every
     // rank, and loc is its own array.  pos_status / pos_scale: status and colscale of every basis position, formed from
-    // the owners' contributions (trisolve.hip).
+    // the owners' contributions (scaling_positions, trisolve.hip).
     bool part = false;
     DevBuf<int> loc, pos_status;
     DevBuf<double> pos_sum, pos_scale, aB, zeros;
     const int* loc_map() const { return part ? loc.get() : basis.get(); }
 };
 
+inline bool sweep_verbose() { return getenv("IPXK_VERBOSE") || getenv("IPXK_SWEEP_STATS"); }
+
+// ---- sweep.hip ----
 // Launch plan of a sweep from its level structure (host arithmetic, O(#levels)).
 void plan_sweep(Sweep& S, bool level_launches);
+// sentinel into the result vectors of the given sweeps (one launch): every sweep needs it before it runs
+void fill_results(Context* c, std::initializer_list<const Sweep*> sweeps, const int* done);
+// A pair of sweeps with the dense bump between them (trans: U' then L'; else L then U): `first` runs on xin (addressed
+// through first.src), `second` on first.y; dst2 / out2: second copy of the second sweep's result (SweepView::dst2)
+void run_pair(Context* c, const Sweep& first, const Sweep& second, bool trans, bool scaled, const double* xin, const int* done,
+              const int* dst2 = nullptr, double* out2 = nullptr);
+// a sweep's result (by position) into index order: out[perm ? perm[k] : k] = value of unknown k
+void unpack_result(Context* c, const Sweep& S, const int* perm, double* out);
+// m-vectors: out[i] = in[perm[i]]  /  out[perm[i]] = in[i]
+void gather_perm(Context* c, const double* in, const int* perm, double* out, const int* done);
+void scatter_perm(Context* c, const double* in, const int* perm, double* out, const int* done);
+// ---- sweep_blocks.hip ----
 // decides whether the sweep gets an inverted head / tail and builds them from the packed rows (before plan_sweep)
 void build_sweep_blocks(Context* c, Sweep& S, bool level_launches);
+void run_block(Context* c, const Sweep& S, const Sweep::Block& T, const SweepView& V, bool scaled, const double* xin, const int* done);
+void locate_block_rhs(Context* c, Sweep& W);
 
 // Device-side analysis of the four sweeps (prepare_device.hip): uploads L and U as given, builds
 // the row lists, computes dependency levels, orders the unknowns and packs the rows on the GPU.
@@ -198,5 +224,16 @@ void analyse_sweeps_device(Context* c, SplitOperator* S, const ipxint* Lp, const
                            const ipxint* Up, const ipxint* Ui, const double* Ux);
 // (re)computes the column-scaled value sets of the U sweeps from S->uscale
 void rescale_sweeps_device(Context* c, SplitOperator* S);
+
+// ---- dense_bump.hip ----
+// between the two sweeps of a pair: `y` is the result of the first one
+void bump_between(Context* c, bool trans, double* y, const int* done);
+// first column of the dense trailing block of factors from the host (m: none)
+int trailing_dense_block(int m, const ipxint* Lp);
+// The analysis of the sweeps (analyse_sweeps_resident) with the trailing block [s0, s0 + kb) = [s0, m) cut out of the factors
+// where the caller found one (cuttable) and the policy allows (IPXK_BUMP_DENSE, IPXK_BUMP_MIN); hL*/hU*: as above, for the
+// factors as given
+void analyse_sweeps_cutting_bump(Context* c, SplitOperator* S, const DeviceFactors& F, bool cuttable, int s0, int kb,
+                                 const ipxint* hLp, const ipxint* hLi, const ipxint* hUp, const ipxint* hUi);
 
 }  // namespace ipxk

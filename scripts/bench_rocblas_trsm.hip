@@ -1,5 +1,5 @@
 // Microbenchmark: the inverse of a dense LU-factored block D22 = (L+I) U (kb x kb, column major, L below / U on and above the
-// diagonal) as two rocblas_dtrsm on the identity -- what bump_inverse_kernel (trisolve.hip) computes with one blocked solve
+// diagonal) as two rocblas_dtrsm on the identity -- what bump_inverse_kernel (dense_bump.hip) computes with one blocked solve
 // per column.  usage: bench_rocblas_trsm [kb ...]
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>

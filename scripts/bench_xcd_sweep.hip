@@ -1,4 +1,4 @@
-// Microbenchmark for the level-scheduled triangular sweeps (prototype of trisolve.hip's kernels): cost of a
+// Microbenchmark for the level-scheduled triangular sweeps (prototype of sweep.hip's kernels): cost of a
 // whole sweep over a given level-width profile when levels are executed as
 //   L  one launch per level (packed ELL records: record + entries in ONE round trip, gathers in a second)
 //   S  sync-free runs: ONE launch for a run of levels, value-as-flag hand-off (the result vector is pre-filled

@@ -364,7 +364,7 @@ def test_lu_and_maxvolume_at_baseline_size(kkt, ref):
 
 
 def test_dense_block_inverse_on_the_matrix_cores_against_the_blocked_solves(kkt, monkeypatch, capfd):
-    """the explicit inverse of a dense block of the factors (trisolve.hip: cut_dense_block): triangular inverses by recursive
+    """the explicit inverse of a dense block of the factors (dense_bump.hip: cut_dense_block): triangular inverses by recursive
     doubling + one product on v_mfma_f64_16x16x4_f64 (dense_inverse.hip) against the older kernel -- one blocked solve per
     column of the identity -- on the same factors: operator applications and dense solves agree to 1e-9 (both inverses carry
     cond * eps).  Block sizes that

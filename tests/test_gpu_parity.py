@@ -386,7 +386,7 @@ def test_inverted_head_and_tail_of_the_sweeps(kkt, po, oracle, monkeypatch, capf
 
 
 def test_ill_conditioned_block_is_not_inverted(kkt, monkeypatch, capfd):
-    """The guard of the explicit inverses (trisolve.hip; IPX's bases get ill conditioned late in a solve: that is what
+    """The guard of the explicit inverses (inverse_guard.hpp; IPX's bases get ill conditioned late in a solve: that is what
     the stability loop of src/basis.cc:130-152 and the residual test of src/lu_factorization.cc:87-127 are for).  A
     planted basis whose L has entries of magnitude 3 in its last rows: along the dependency chains of those rows the
     inverse of the tail block grows like 3^depth (probe residual |T M z - z| ~ 1e2, i.e. cond * eps with cond ~ 1e18).
