@@ -329,10 +329,10 @@ int ipxk_get_rowwise(const ipxk_context* c, ipxint* ATp, ipxint* ATi, double* AT
     return guarded([&] {
         IPXK_REQUIRE(c != nullptr, "ctx is NULL");
         IPXK_HIP(hipSetDevice(c->device));
-        // the row-wise copy is produced by the library's own Transpose arithmetic (spmv.hip)
+        // the row-wise copy is produced by the library's own Transpose arithmetic (model.hip)
         const size_t m = (size_t)c->m, nz = (size_t)c->nnz;
         Context* cc = const_cast<Context*>(static_cast<const Context*>(c));
-        ensure_host_model(cc, true);      // a download of the device's row-wise copy (layout_device.hip)
+        ensure_host_model(cc, true);      // a download of the device's row-wise copy (model.hip)
         if (ATp) for (size_t r = 0; r <= m; r++) ATp[r] = c->h_ATp[r];
         if (ATi) for (size_t q = 0; q < nz; q++) ATi[q] = c->h_ATi[q];
         if (ATx) for (size_t q = 0; q < nz; q++) ATx[q] = c->h_ATx[q];

@@ -22,7 +22,7 @@ enum PartialSlot {
     kNumPartialSlots
 };
 
-// A second copy of the model with rows and columns renumbered for locality (layout_device.hip, reorder_model): the loop of the
+// A second copy of the model with rows and columns renumbered for locality (reorder.hip, reorder_model): the loop of the
 // preconditioned CR method of the diag path runs on it, in permuted numbering; everything else keeps the original numbering.
 struct Reordered {
     bool active = false;                 // the copy exists and is the faster one
@@ -63,7 +63,7 @@ struct Context {
     int64_t m = 0, n = 0, nnz = 0;
     std::vector<ipxint> h_Ap;           // column pointers (host)
     // host copies of the entries and of the row-wise copy: filled on demand only (ensure_host_model) -- the model
-    // lives on the device, the layouts are built there (layout_device.hip)
+    // lives on the device, the layouts are built there (model.hip, layout_device.hip)
     std::vector<ipxint> h_Ai;
     std::vector<double> h_Ax;
     std::vector<ipxint> h_ATp, h_ATi;
@@ -76,7 +76,7 @@ struct Context {
     double create_ms[4] = {0, 0, 0, 0};   // ipxk_create: upload + transpose, Acols layouts, Arows layouts, the rest
     GatherMatrix Acols;                 // rows = columns of A  (computes A'y)
     GatherMatrix Arows;                 // rows = rows of A     (computes A t)
-    Reordered reord;                    // the same matrix renumbered for locality, if that pays (layout_device.hip)
+    Reordered reord;                    // the same matrix renumbered for locality, if that pays (reorder.hip)
     int64_t num_dense = 0, nz_dense = 0;
     std::vector<ipxint> dense_cols;
 
@@ -176,14 +176,23 @@ struct Context {
     double* part(int slot) const { return partials.get() + (size_t)slot * kPartialStride; }
 };
 
-// layout_device.hip
-struct LayoutScratch;
-LayoutScratch* new_layout_scratch();
-void free_layout_scratch(LayoutScratch* S);
+// ---- model.hip: the model on the device, its gather matrices, the dense-column classification ----
+void build_model(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax);
 void upload_plain_model(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax);
 void ensure_host_model(Context* c, bool rowwise);
 void fetch_columns(Context* c, const std::vector<ipxint>& cols, std::vector<ipxint>& Cp, std::vector<ipxint>& Ci, std::vector<double>& Cx);
+// partitioned contexts: dense-column classification of the whole matrix (comm_init); true if it changed
+bool classify_dense_columns_global(Context* c);
+struct LayoutScratch;                 // layout_scratch.hpp
+struct Tmp;
 int device_max_row_length(LayoutScratch& S, int nrows, const int* dptr, hipStream_t s);
+// row of every entry of a row-wise matrix, and (pos != nullptr) the entry's own position; row pointers from the sorted rows of the entries
+void device_row_of_entries(int nrows, const int* ptr, int* rowof, unsigned* pos, hipStream_t s);
+void device_row_pointers(int64_t nrows, int64_t nz, const unsigned* sorted_rows, int* ptr, hipStream_t s);
+void device_transpose(Tmp& T, DevBuf<int>& colof, int64_t n, int64_t m, int64_t nz, const int* Ap, const int* Ai, const double* Ax, int* Tp,
+                      int* Ti, double* Tx, hipStream_t s);
+
+// ---- layout_device.hip: the device builders (the host builders are members of GatherMatrix: layout_host.hip) ----
 // rows of more than kMaxRowLen entries out of a row-wise matrix: fills G's long-row arrays, returns the matrix without them
 bool device_strip_long_rows(LayoutScratch& S, GatherMatrix& G, int nrows, const int* dptr, const int* didx, const double* dval,
                             DevBuf<int>& sptr, DevBuf<int>& sidx, DevBuf<double>& sval, int64_t* nnz_short, hipStream_t s);
@@ -195,14 +204,11 @@ bool device_build_acc_fused(LayoutScratch& S, AccMatrix& out, int nrows, int nco
                             const double* dval, hipStream_t s);
 bool device_build_sorted(LayoutScratch& S, SortedMatrix& out, const SlicedMatrix& sliced, int nrows, int ncols, int64_t nnz, const int* dptr,
                          const int* didx, const double* dval, hipStream_t s);
-
-int acc_rows_per_block(int nrows, int ns);
 bool device_build_acc(LayoutScratch& S, AccMatrix& out, const SlicedMatrix& sliced, int nrows, int ncols, int64_t nnz, const int* dptr,
                       const int* didx, const double* dval, hipStream_t s);
 
-// layout_device.hip: the locality-recovering renumbering (SURVEY section 7 / 8d "row/column reordering ... a pure permutation")
+// ---- reorder.hip: the locality-recovering renumbering (SURVEY section 7 / 8d "row/column reordering ... a pure permutation") ----
 void reorder_model(Context* c);
-float time_normal_pair(Context* c, GatherMatrix& Ac, GatherMatrix& Ar);     // spmv.hip: microseconds of the two products
 void reorder_permute_rows(Context* c, const double* in_old, double* out_new);      // out_new[i'] = in_old[rowperm[i']]
 void reorder_unpermute_rows(Context* c, const double* in_new, double* out_old);    // out_old[rowperm[i']] = in_new[i']
 void reorder_permute_weights(Context* c, const double* W_old, double* W_new);      // n structural by colperm, m slack by rowperm
@@ -223,9 +229,7 @@ void finish_out(Context* c, double* user, const double* dev, size_t len);
 // ---- spmv.hip ----
 void normal_apply_dev(Context* c, const double* W, const double* rhs, double* lhs, int* ndot,
                       const int* done);
-void build_model(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax);
-// partitioned contexts: dense-column classification of the whole matrix (comm_init); true if it changed
-bool classify_dense_columns_global(Context* c);
+float time_normal_pair(Context* c, GatherMatrix& Ac, GatherMatrix& Ar);     // microseconds of the two products
 void debug_single_pass(Context* c, int which, const double* x, double* out);
 
 // ---- precond.hip ----

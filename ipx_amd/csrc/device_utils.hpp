@@ -16,6 +16,37 @@ namespace ipxk {
 template <class T>
 __global__ void fill_kernel(int64_t n, T v, T* __restrict__ a) { IPXK_GRID_STRIDE(i, n) a[i] = v; }
 
+// exclusive prefix sum of n counts by ONE workgroup of kThreads threads (n = # tiles, a few thousand); out[n] = their sum
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void scan_u32_kernel(int n, const unsigned* __restrict__ in, unsigned* __restrict__ out) {
+    __shared__ unsigned wsum[kThreads / 64];
+    __shared__ unsigned carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) carry = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += kThreads) {
+        const int i = base + tid;
+        const unsigned v = i < n ? in[i] : 0u;
+        unsigned incl = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        unsigned before = carry;
+        for (int w = 0; w < wave; w++) before += wsum[w];
+        if (i < n) out[i] = before + incl - v;
+        __syncthreads();
+        if (tid == kThreads - 1) carry = before + incl;
+        __syncthreads();
+    }
+    if (tid == 0) out[n] = carry;
+}
+// (a template so that only the files that call it instantiate the kernel)
+template <int kThreads = 1024>
+void scan_u32(int n, const unsigned* in, unsigned* out, hipStream_t s) {
+    hipLaunchKernelGGL(scan_u32_kernel<kThreads>, dim3(1), dim3(kThreads), 0, s, n, in, out);
+}
+
 struct SumOp {
     static __device__ __forceinline__ double identity() { return 0.0; }
     static __device__ __forceinline__ double apply(double a, double b) { return a + b; }

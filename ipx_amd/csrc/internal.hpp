@@ -285,10 +285,6 @@ constexpr int kAccThreads = 512;
 constexpr int kAccPerThread = 4;
 constexpr int kAccBatch = kAccThreads * kAccPerThread;     // 2048 entries between two barriers
 constexpr int kAccMaxRows = 16384;                         // 128 KB of row sums; 14 bits of row in the entry word
-// workgroups of the persistent tile kernel on the current device: its CU count rounded down to a multiple of 8 (XCDs) and of
-// ns, so that a workgroup's tiles are all of one slice and stay on one XCD; 0 with IPXK_ACC_PERSIST=0 (one workgroup per tile);
-// IPXK_ACC_PERSIST=<g> caps it at g
-int acc_persist_grid(int ns);
 //   * FUSED form (one slice = all of x, for matrices whose gathers have locality; round 4): a tile is a row block of RB rows
 //     (as many as give every CU two tiles), the gathered index is stored relative to the tile's smallest one (`xmin`; the
 //     tile's window of x must span less than 2^18 entries), the row sums start from the epilogue's initial value and the
@@ -314,7 +310,7 @@ struct AccMatrix {
     DevBuf<int> xmin;
 };
 
-struct LayoutScratch;                 // layout_device.hip
+struct LayoutScratch;                 // layout_scratch.hpp
 
 // The layout of a gather matrix's unmasked products; the values are the codes ipxk_spmv_layout reports.
 enum class SpmvLayout { phased, sliced, fused, sorted, sortedfused, acc, plain, accfused };
@@ -347,10 +343,13 @@ struct GatherMatrix {
     // Builds from host arrays with 64-bit indices (ptr has nrows+1 entries).
     void build(int64_t nrows_, int64_t ncols_, const ipxint* hptr, const ipxint* hidx,
                const double* hval, hipStream_t s);
-    // Builds from the plain device copy (ptr / idx 32 bits) with radix sorts on the device (layout_device.hip): the sliced
-    // and the sorted layout, every array equal to build()'s.  Returns false -- nothing built -- when the matrix is not
-    // one of those the device path covers (long rows, a gathered vector that fits an XCD's L2, gathers that do not
-    // spread over the slices): the caller then runs build() on host arrays.
+    // Builds from the plain device copy (ptr / idx 32 bits) with radix sorts on the device (layout_device.hip), every array equal
+    // to the host builders'.  Long rows are taken out first (device_strip_long_rows) and the tiles built from the rest; a matrix
+    // whose x needs slicing and whose gathers spread over the slices gets the sliced, accumulated and sorted tiles, every other
+    // one -- x fits an XCD's L2, or the gathers have locality -- the fused, sorted fused and fused accumulated tiles and the plain
+    // rows (build_device_local).  Returns false -- the caller then runs build() on host arrays -- for small matrices
+    // (nnz < 2^16, also after the long rows are out), tune_level < 2, keep_plain, a forced layout, IPXK_LAYOUT_BUILD=host and
+    // when the fused tiles cannot be built (more than 255 entries of a row in a tile, a tile beyond the staging buffer).
     bool build_device(LayoutScratch& S, int64_t nrows_, int64_t ncols_, int64_t nnz_, const int* dptr, const int* didx,
                       const double* dval, hipStream_t s);
     bool build_device_local(LayoutScratch& S, int64_t nrows_, int64_t ncols_, int64_t nnz_, const int* dptr, const int* didx,
@@ -374,7 +373,7 @@ struct GatherMatrix {
     void build_sorted_fused(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
     // accumulated tiles (the sliced layout's slices, row sums in LDS), and their FUSED form
     AccMatrix acc;
-    void build_acc(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);     // host builder (test reference)
+    void build_acc(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);     // host builders: layout_host.hip
     void build_acc_fused(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
     AccMatrix accf;
     AccView acc_fused_view() const;
@@ -436,8 +435,9 @@ struct GatherMatrix {
     std::vector<unsigned char> h_row_long;   // host copy of row_long (empty: no long rows)
 };
 
-// elements of the gathered vector per phase (IPXK_SLICE_KB overrides, default 1 MiB)
+// elements of the gathered vector per phase (IPXK_SLICE_KB overrides, default 1 MiB); phase_slice: of a vector of ncols entries
 int slice_elems();
+int64_t phase_slice(int64_t ncols);
 
 // ---------------------------------------------------------------------------
 // CR loop state kept on the device (see cr.hip)
@@ -579,3 +579,5 @@ T read_scalars(const T* dev, T* pinned, hipStream_t s) {
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace ipxk
+
+#include "layout_geometry.hpp"     // (needs the constants above; spmv_kernels.hpp needs acc_persist_grid)

@@ -19,11 +19,8 @@
 //   * the scaling (the weights W_N) is refreshed with every rescale; the structure is rebuilt only when the set of
 //     columns changes.
 // Only for models whose gathered vectors need slicing (x beyond an XCD's L2) and without long rows; otherwise the
-// masked / compacted model matrix of spmv.hip serves.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "context.hpp"
+// masked / compacted model matrix of spmv_mask.hip serves.
+#include "layout_scratch.hpp"
 #include "spmv_kernels.hpp"
 #include "trisolve.hpp"
 
@@ -31,7 +28,6 @@ namespace ipxk {
 
 namespace {
 
-using u64 = unsigned long long;
 constexpr int kTileShift = 42, kRowShift = 32;      // key = tile << 42 | row in tile << 32 | storage position
 
 __global__ void nm_keep_kernel(int n, const double* __restrict__ W, const int* __restrict__ Ap, int* __restrict__ keep, int* __restrict__ len) {
@@ -158,22 +154,6 @@ __global__ void nm_csr2_fill_kernel(int m, int64_t nzN, const int* __restrict__ 
     }
 }
 
-struct Tmp {
-    DevBuf<unsigned char> bytes;
-    void* need(size_t n) { if (bytes.size() < n) bytes.resize(n); return bytes.get(); }
-};
-
-int slices_for(int64_t ncols, int64_t* slice_out) {
-    int64_t slice_bytes = int64_t(2) << 20;
-    if (const char* e = getenv("IPXK_SLICE_TEST_KB"))        // tests: slices for small matrices (as in spmv.hip)
-        if (atoi(e) > 0) slice_bytes = (int64_t)atoi(e) << 10;
-    const int64_t x_bytes = ncols * 8;
-    int ns = 1;
-    if (x_bytes > 2 * slice_bytes) { ns = 2; while (ns < 8 && x_bytes > (int64_t)ns * slice_bytes) ns *= 2; }
-    *slice_out = ((ncols + ns - 1) / ns + 15) / 16 * 16;
-    return ns;
-}
-
 }  // namespace
 
 struct NMatrix {
@@ -191,20 +171,10 @@ struct NMatrix {
 };
 void destroy_nmatrix(NMatrix* N) { delete N; }
 
-static void scan_int(Tmp& T, const int* in, int* out, size_t n, hipStream_t s) {
-    size_t bytes = 0;
-    IPXK_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, n, rocprim::plus<int>(), s));
-    IPXK_HIP(rocprim::exclusive_scan(T.need(bytes), bytes, in, out, 0, n, rocprim::plus<int>(), s));
-}
-static void sort_u64(Tmp& T, u64* a, u64* b, size_t n, hipStream_t s) {
-    size_t bytes = 0;
-    IPXK_HIP(rocprim::radix_sort_keys(nullptr, bytes, a, b, n, 0u, 64u, s));
-    IPXK_HIP(rocprim::radix_sort_keys(T.need(bytes), bytes, a, b, n, 0u, 64u, s));
-}
-
 // one gather matrix from its sorted keys; false if a tile does not fit (the caller retries with fewer rows per tile)
-static bool finish_layout(NMatrix& N, SlicedMatrix& P, int nrows, int R, int ns, int64_t nz, const u64* keys, const int* src_idx,
-                          const double* src_val, const int* newidx, hipStream_t s) {
+static bool finish_layout(NMatrix& N, SlicedMatrix& P, int nrows, const RowBlockSearch& search, int ns, int64_t nz, const u64* keys,
+                          const int* src_idx, const double* src_val, const int* newidx, hipStream_t s) {
+    const int R = search.rows;
     const int nrb = (nrows + R - 1) / R;
     const int ntiles = nrb * ns;
     P.R = R; P.nslices = ns; P.nrb = nrb; P.nrows_pad = nrb * R;
@@ -216,7 +186,7 @@ static bool finish_layout(NMatrix& N, SlicedMatrix& P, int nrows, int R, int ns,
     IPXK_HIP(hipMemcpyAsync(h, N.counters.get(), sizeof h, hipMemcpyDeviceToHost, s));
     IPXK_HIP(hipStreamSynchronize(s));
     P.max_tile = h[0];
-    if (P.max_tile > kSlicedMaxTile) return false;
+    if (!search.fits(P.max_tile)) return false;
     const int64_t nslots = (int64_t)ntiles * R;
     N.cnt32.ensure((size_t)nslots);
     IPXK_HIP(hipMemsetAsync(N.cnt32.get(), 0, (size_t)nslots * sizeof(int), s));
@@ -285,41 +255,42 @@ bool nmatrix_prepare(Context* c, const double* W) {
         hipLaunchKernelGGL(nm_colof_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, N.keep.get(), N.newidx.get(), N.colof.get(), N.newidx.get());
         N.keys.ensure((size_t)c->nnz); N.keys2.ensure((size_t)c->nnz);
         // P1: rows = kept columns, gathered index = row of A
-        int64_t slice1 = 0, slice2 = 0;
-        const int ns1 = slices_for(m, &slice1), ns2 = slices_for(nN, &slice2);
+        // (a gathered vector that fits an XCD's L2 takes one slice)
+        const Slices sl1 = slices_of(m, false), sl2 = slices_of(nN, false);
+        const int ns1 = sl1.ns, ns2 = sl2.ns;
         N.P1 = SlicedMatrix(); N.P2 = SlicedMatrix();
         bool ok = false;
-        for (int R = kSlicedRows; R >= kBlock && !ok; R /= 2) {
-            hipLaunchKernelGGL(nm_keys_p1_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, c->pl_Ap.get(), c->pl_Ai.get(), N.newidx.get(), N.off.get(), R,
-                               ns1, (int)slice1, N.keys.get());
-            sort_u64(N.T, N.keys.get(), N.keys2.get(), (size_t)nzN, s);
+        for (RowBlockSearch R = sliced_rows(nN, ns1, false); !R.gave_up() && !ok; R.next()) {
+            hipLaunchKernelGGL(nm_keys_p1_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, n, c->pl_Ap.get(), c->pl_Ai.get(), N.newidx.get(), N.off.get(), R.rows,
+                               ns1, (int)sl1.width, N.keys.get());
+            sort_keys(N.T, N.keys.get(), N.keys2.get(), (size_t)nzN, s);
             ok = finish_layout(N, N.P1, nN, R, ns1, nzN, N.keys2.get(), c->pl_Ai.get(), c->pl_Ax.get(), nullptr, s);
         }
         if (!ok) return false;
         ok = false;
-        for (int R = kSlicedRows; R >= kBlock && !ok; R /= 2) {
-            hipLaunchKernelGGL(nm_keys_p2_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, c->pl_Tp.get(), c->pl_Ti.get(), N.newidx.get(), R, ns2, (int)slice2,
-                               N.keys.get());
-            sort_u64(N.T, N.keys.get(), N.keys2.get(), (size_t)c->nnz, s);      // the entries of dropped columns sort to the end
+        for (RowBlockSearch R = sliced_rows(m, ns2, false); !R.gave_up() && !ok; R.next()) {
+            hipLaunchKernelGGL(nm_keys_p2_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, c->pl_Tp.get(), c->pl_Ti.get(), N.newidx.get(), R.rows, ns2,
+                               (int)sl2.width, N.keys.get());
+            sort_keys(N.T, N.keys.get(), N.keys2.get(), (size_t)c->nnz, s);      // the entries of dropped columns sort to the end
             ok = finish_layout(N, N.P2, m, R, ns2, nzN, N.keys2.get(), c->pl_Ti.get(), c->pl_Tx.get(), N.newidx.get(), s);
         }
         if (!ok) return false;
         // the accumulated-tiles form of both (IPXK_SPMV_ACC=0: the sliced tiles stay)
         N.A1 = AccMatrix(); N.A2 = AccMatrix();
         if (!(getenv("IPXK_SPMV_ACC") && getenv("IPXK_SPMV_ACC")[0] == '0') && ns1 > 1 && ns2 > 1) {
-            std::unique_ptr<LayoutScratch, void (*)(LayoutScratch*)> LS(new_layout_scratch(), free_layout_scratch);
+            LayoutScratch LS;
             const size_t nzn = (size_t)nzN;
             N.cptr.ensure((size_t)std::max(nN, m) + 1); N.cidx.ensure(nzn); N.cval.ensure(nzn);
             hipLaunchKernelGGL(nm_csr1_kernel, dim3(grid_for(nN)), dim3(kBlock), 0, s, nN, nzN, N.colof.get(), N.off.get(), c->pl_Ap.get(), c->pl_Ai.get(),
                                c->pl_Ax.get(), N.cptr.get(), N.cidx.get(), N.cval.get());
             AccMatrix a1, a2;
-            const bool ok1 = device_build_acc(*LS, a1, N.P1, nN, m, nzN, N.cptr.get(), N.cidx.get(), N.cval.get(), s);
+            const bool ok1 = device_build_acc(LS, a1, N.P1, nN, m, nzN, N.cptr.get(), N.cidx.get(), N.cval.get(), s);
             N.cnt32.ensure((size_t)m + 1);
             hipLaunchKernelGGL(nm_csr2_count_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, c->pl_Tp.get(), c->pl_Ti.get(), N.newidx.get(), N.cnt32.get());
             scan_int(N.T, N.cnt32.get(), N.cptr.get(), (size_t)m, s);
             hipLaunchKernelGGL(nm_csr2_fill_kernel, dim3(grid_for(m)), dim3(kBlock), 0, s, m, nzN, c->pl_Tp.get(), c->pl_Ti.get(), c->pl_Tx.get(),
                                N.newidx.get(), N.cptr.get(), N.cidx.get(), N.cval.get());
-            const bool ok2 = device_build_acc(*LS, a2, N.P2, m, nN, nzN, N.cptr.get(), N.cidx.get(), N.cval.get(), s);
+            const bool ok2 = device_build_acc(LS, a2, N.P2, m, nN, nzN, N.cptr.get(), N.cidx.get(), N.cval.get(), s);
             if (ok1 && ok2) { N.A1 = std::move(a1); N.A2 = std::move(a2); }
         }
         N.wN.ensure((size_t)nN); N.tN.ensure((size_t)nN);

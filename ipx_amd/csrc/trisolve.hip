@@ -160,7 +160,7 @@ static void upload_scaling(Context* c, SplitOperator* S, const ipxint* status, c
     S->num_free = h[1];
     rescale_sweeps_device(c, S);
     // N N' runs on the model matrix with weights that are zero on the BASIC and fixed columns: value arrays in
-    // which those columns' entries are zero let both passes skip the gathers of those entries (spmv.hip)
+    // which those columns' entries are zero let both passes skip the gathers of those entries (spmv_mask.hip)
     S->masked_values = !(getenv("IPXK_MASKED_VALUES") && getenv("IPXK_MASKED_VALUES")[0] == '0');
     // IPXK_COMPACT_N=0: keep streaming the whole model matrix with masked values (round-2 form)
     const bool compact = !(getenv("IPXK_COMPACT_N") && getenv("IPXK_COMPACT_N")[0] == '0');

@@ -1,5 +1,5 @@
-"""GPU: the model upload and the gather-matrix layouts built on the device (ipx_amd/csrc/layout_device.hip)
-against the host builders (ipx_amd/csrc/spmv.hip), array by array, and one device context per Model.
+"""GPU: the model upload and the gather-matrix layouts built on the device (ipx_amd/csrc/model.hip, layout_device.hip)
+against the host builders (ipx_amd/csrc/layout_host.hip), array by array, and one device context per Model.
 
 The reference constructs its KKT solvers for free (NormalMatrix stores a reference to the model,
 src/normal_matrix.h:20-27; three solver objects per LpSolver::Solve, src/lp_solver.cc:375,386,457).  What

@@ -1,4 +1,4 @@
-"""GPU: the locality-recovering renumbering of the model (ipx_amd/csrc/layout_device.hip, reorder_model; SURVEY.md section 7
+"""GPU: the locality-recovering renumbering of the model (ipx_amd/csrc/reorder.hip, reorder_model; SURVEY.md section 7
 "row/column reordering ... must stay a pure permutation").  Index arithmetic bit-exact, solves equal to the unpermuted ones."""
 import numpy as np
 import pytest
