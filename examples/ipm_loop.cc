@@ -10,6 +10,9 @@
 // With a fifth argument p > 0, p percent of the rows are equality rows (slack lb = ub = 0): the run then starts from
 // ipxk_ipm_starting_point, and between the two phases ipxk_ipm_starting_basis (StartingBasis, src/starting_basis.cc) pivots
 // the fixed slacks out of the slack basis, which is where the main phase goes on.
+// With 2 as the fourth argument the program makes ONE call instead, ipxk_ipm_solve (LpSolver::InteriorPointSolve: starting
+// point, initial iterations, starting basis, main phase, postprocessing), and prints the evaluation of the postprocessed
+// iterate -- the reference's interior solution -- and the dropping residuals crossover would start from.
 //
 //   g++ -std=c++14 -O2 -Iinclude examples/ipm_loop.cc -Lipx_amd/lib -lipx_kkt_hip -Wl,-rpath,$PWD/ipx_amd/lib -o ipm_loop
 #include <algorithm>
@@ -63,6 +66,22 @@ int main(int argc, char** argv) {
 
     ipxk_context* ctx = nullptr;
     CHECK(ipxk_create(m, n, Ap.data(), Ai.data(), Ax.data(), 0, &ctx));
+    if (argc > 4 && std::atoi(argv[4]) == 2) {           // the whole interior point solve in one call
+        ipxk_solve_params prm{};
+        prm.kkt_tol = 0.3; prm.feasibility_tol = 1e-6; prm.optimality_tol = 1e-8; prm.crossover_start = 0.0;
+        prm.dependency_tol = 1e-6; prm.ipm_maxiter = 300; prm.switchiter = -1; prm.max_etas = 100; prm.precond_dense_cols = 1;
+        ipxk_solve_info info;
+        CHECK(ipxk_ipm_solve(ctx, b.data(), c.data(), lb.data(), ub.data(), &prm, &info, nullptr, nullptr, nullptr, nullptr));
+        std::printf("solve: status %ld after %ld iterations (%ld initial, ended by status %ld), %ld CR iterations, %ld exchanges for the "
+                    "starting basis, %ld basis updates, %ld dependent rows, %ld dependent columns\n", (long)info.status_ipm, (long)info.iter,
+                    (long)info.iter_initial, (long)info.status_initial, (long)info.kktiter, (long)info.updates_start, (long)info.basis_updates,
+                    (long)info.dependent_rows, (long)info.dependent_cols);
+        std::printf("interior solution: pobjective %.10e dobjective %.10e rel_objgap %.2e rel_presidual %.2e rel_dresidual %.2e; "
+                    "dropping residuals %.2e %.2e\n", info.pobjective, info.dobjective, info.rel_objgap, info.rel_presidual,
+                    info.rel_dresidual, info.pres_dropping, info.dres_dropping);
+        ipxk_destroy(ctx);
+        return info.status_ipm == 1 ? 0 : 1;
+    }
     // interior start away from the solution: x = xl = 1, y = 0, zl = 1 (all variables have a lower bound only)
     std::vector<double> x(N, 1.0), xl(N, 1.0), xu(N, INFINITY), y(m, 0.0), zl(N, 1.0), zu(N, 0.0);
     std::vector<unsigned char> state(N, IPXK_STATE_BARRIER_LB);

@@ -557,7 +557,10 @@ int ipxk_iterate_factorize_diag(ipxk_context* ctx, int precond_dense_cols,
  * the model vectors: out3 = {pobjective, dobjective, offset}; pobjective + offset
  * and dobjective + offset are the objectives after postprocessing (:203-211).
  * Variable states as in ipxk_iterate_set (the implied states of the basis solver's
- * drop procedures do not exist on the device).  Column partition: global, one
+ * drop procedures do not exist on the device).  On a postprocessed iterate
+ * (ipxk_iterate_postprocess) it is the other branch (:599-609): pobjective = c'x,
+ * dobjective = b'y + sum lb zl - sum ub zu over the finite bounds, offset = 0.
+ * Column partition: global, one
  * all-gather of 4 per rank (offset and the fixed structural x_j A_j'y included).
  * Row partition: refused. */
 int ipxk_iterate_objectives(ipxk_context* ctx, const double* b, const double* c,
@@ -565,7 +568,10 @@ int ipxk_iterate_objectives(ipxk_context* ctx, const double* b, const double* c,
 
 /* IPM::Driver (src/ipm.cc:56-123) on the resident iterate with the diag solver:
  * loop of {termination test (Iterate::term_crit_reached, src/iterate.cc:221-249,
- * with crossover_start = 0), divergence / bad-iteration test (:71-93), iteration
+ * with the crossover_start of ipxk_ipm_set_crossover_start, 0 unless set: a positive
+ * value adds the dropping residuals to the test, on a column partition with one more
+ * all-gather of 2 at a feasible and optimal iterate), divergence / bad-iteration
+ * test (:71-93), iteration
  * limit, InterruptCheck, KKTSolverDiag::Factorize, Predictor + AddCorrector +
  * MakeStep}.  status_ipm uses the values of include/ipx_status.h
  * (IPX_STATUS_optimal 1, primal_infeas 3, dual_infeas 4, time_limit 5,
@@ -660,7 +666,8 @@ int ipxk_ipm_load_starting_point(ipxk_context* ctx, const double* x,
  * statuses instead, BASIC_FREE and NONBASIC_FIXED persist through Maxvolume and Prepare, and the scaling
  * factors 0 / inf of fixed / free variables are taken as they are.  basis_out[m] / status_out[n+m]
  * (either may be NULL) return the final basis.  params->kkt_maxiter is ignored (KKTSolverBasis runs CR with
- * maxiter = -1).  Limits of the refactorizations: see ipxk_lu_factorize (dense bump).  Refused on any partitioned
+ * maxiter = -1).  The termination test is ipxk_ipm_driver's, crossover_start included; a postprocessed iterate is
+ * refused by both drivers.  Limits of the refactorizations: see ipxk_lu_factorize (dense bump).  Refused on any partitioned
  * context (it needs the device LU and Maxvolume). */
 int ipxk_ipm_driver_basis(ipxk_context* ctx, const double* b, const double* c,
                           const double* lb, const double* ub,
@@ -719,6 +726,90 @@ int ipxk_ipm_starting_basis(ipxk_context* ctx, const double* b, const double* c,
                             ipxk_starting_basis_info* info, ipxint* basis_out,
                             ipxint* status_out, ipxint* exchange_log, ipxint log_cap,
                             ipxk_interrupt_fn interrupt, void* interrupt_user);
+
+/* ---- the end of the solve (src/lp_solver.cc:305-332, src/iterate.cc:237-448) -------------------------------
+ * Iterate::Postprocess (src/iterate.cc:250-313) on the resident iterate for the model vectors c, lb, ub [n+m].
+ * The reference's StateDetail is derived from the five device states and the bounds: IPXK_STATE_FIXED is FIXED;
+ * IPXK_STATE_FREE with finite lb == ub is IMPLIED_EQ (the slacks of dependent equality rows after
+ * ipxk_ipm_starting_basis); IPXK_STATE_FREE otherwise is FREE.  IMPLIED_LB / IMPLIED_UB do not occur.
+ *   fixed:      xl = x - lb, xu = ub - x (inf at an infinite bound); if lb == ub, z = c_j - a_j'y goes to zl
+ *               (z >= 0) or to zu as -z.
+ *   implied eq: z goes to zl or zu by sign, the other one is 0; x = lb, xl = xu = 0.
+ * Only those variables are written; when a count on the device finds none, nothing else is launched and the
+ * iterate keeps its bits.  The products a_j'y come from one pass over the column gather matrix.
+ * Afterwards the iterate is "postprocessed" until ipxk_iterate_set, ipxk_ipm_starting_point,
+ * ipxk_ipm_load_starting_point or ipxk_reset_solver_state: ipxk_iterate_residuals keeps rc on fixed variables
+ * (:552-556), ipxk_iterate_objectives takes the postprocessed branch (:599-609), and every call that advances
+ * the iterate (ipxk_iterate_update, ipxk_ipm_step, ipxk_ipm_driver, ipxk_ipm_driver_basis,
+ * ipxk_ipm_starting_basis) is refused with IPXK_E_ARGUMENT.
+ * Column partition: c, lb, ub local; no collective (every rule is column-local, y is replicated).  Row
+ * partition: refused. */
+int ipxk_iterate_postprocess(ipxk_context* ctx, const double* c, const double* lb,
+                             const double* ub);
+/* Iterate::ResidualsFromDropping (src/iterate.cc:393-448): out2 = {pres, dres} (host memory), the primal and
+ * dual residuals that dropping every barrier variable to its bound or its dual to zero would introduce.  The
+ * per-column max |a_ij| (1 for slack columns) is computed on the device at the first call and kept with the
+ * context.  Fixed-order max over block partials.  Column partition: lb, ub local; one all-gather of 2 per rank
+ * (max; slack terms on rank 0).  Row partition: refused. */
+int ipxk_iterate_dropping_residuals(ipxk_context* ctx, const double* lb, const double* ub,
+                                    double out2[2]);
+/* Iterate::crossover_start_ for both drivers (ipx_parameters::crossover_start, 1e-8 in the reference when
+ * crossover is on).  0 (the default, restored by ipxk_reset_solver_state): a feasible and optimal iterate ends
+ * the loop.  Positive: it does so only if the dropping residuals are within value*(1 + norm_bounds) and
+ * value*(1 + norm_c) (src/iterate.cc:237-248); they are evaluated only at such an iterate. */
+int ipxk_ipm_set_crossover_start(ipxk_context* ctx, double value);
+/* Iterate::DropToComplementarity (src/iterate.cc:315-391) of a postprocessed iterate (IPXK_E_ARGUMENT on any
+ * other): x_out, z_out [n+m], y_out [m], the complementary point crossover starts from.  The outputs follow the
+ * pointer mode.  Column partition: local forms, no collective. */
+int ipxk_iterate_drop_to_complementarity(ipxk_context* ctx, const double* lb, const double* ub,
+                                         double* x_out, double* y_out, double* z_out);
+
+/* LpSolver::InteriorPointSolve (src/lp_solver.cc:305-462) without presolve, postsolve and crossover, in one call:
+ *   1. ipxk_ipm_starting_point (skipped with use_resident_point: the caller has called
+ *      ipxk_ipm_load_starting_point, :337-343); a status other than not_run ends the run.
+ *   2. RunInitialIPM (:384-420): ipxk_ipm_driver; switchiter < 0: CR cap min(500, 10 + m/20) and limit
+ *      ipm_maxiter, otherwise limit min(switchiter, ipm_maxiter) and no CR cap.  optimal, no_progress, failed and
+ *      "stopped at switchiter" go on; any other status ends the run.
+ *   3. ipxk_ipm_starting_basis with BuildStartingBasis' mapping (:430-453): errflag 999 -> time_limit (errflag 0),
+ *      any other errflag -> failed, rows_inconsistent -> primal_infeas, cols_inconsistent -> dual_infeas.
+ *   4. ipxk_ipm_driver_basis with what is left of ipm_maxiter; iter, kktiter and basis_updates are sums over both
+ *      phases.
+ *   5. ipxk_iterate_postprocess, whatever the status.
+ *   6. The postprocessed iterate's residuals, objectives, complementarity and dropping residuals.
+ *   7. optimal becomes IPX_STATUS_imprecise (2) when |rel_objgap| > optimality_tol or a relative residual exceeds
+ *      feasibility_tol (:326-330).
+ * crossover_start holds for this call only (the context's own value is restored).  basis_out[m], status_out[n+m]
+ * (either may be NULL) return the last basis if one was built.  Refused on any partitioned context, before any
+ * work. */
+typedef struct ipxk_solve_params {
+    double kkt_tol;            /* 0.3 */
+    double feasibility_tol;    /* ipm_feasibility_tol, 1e-6 */
+    double optimality_tol;     /* ipm_optimality_tol, 1e-8 */
+    double crossover_start;    /* 0: off (the reference with crossover = 0); its default with crossover: 1e-8 */
+    double dependency_tol;     /* 1e-6 */
+    ipxint ipm_maxiter;        /* 300 */
+    ipxint switchiter;         /* -1: the reference's default */
+    ipxint max_etas;           /* as ipxk_ipm_starting_basis */
+    int precond_dense_cols;
+    int use_resident_point;
+} ipxk_solve_params;
+typedef struct ipxk_solve_info {
+    ipxint status_ipm, iter, errflag, kktiter;
+    double pobjective, dobjective;       /* of the postprocessed iterate */
+    double presidual, dresidual, complementarity, mu;
+    double step_primal, step_dual;
+    ipxint basis_updates;
+    ipxint iter_initial, status_initial; /* the initial iterations and what ended them */
+    ipxint dependent_rows, dependent_cols, rows_inconsistent, cols_inconsistent, updates_start;
+    double abs_presidual, abs_dresidual; /* of the postprocessed iterate */
+    double rel_presidual, rel_dresidual; /* over 1 + norm_bounds, 1 + norm_c */
+    double rel_objgap;                   /* (pobj - dobj) / (1 + 0.5 |pobj + dobj|) */
+    double pres_dropping, dres_dropping;
+} ipxk_solve_info;
+int ipxk_ipm_solve(ipxk_context* ctx, const double* b, const double* c, const double* lb,
+                   const double* ub, const ipxk_solve_params* params, ipxk_solve_info* info,
+                   ipxint* basis_out, ipxint* status_out, ipxk_interrupt_fn interrupt,
+                   void* interrupt_user);
 
 /* ---- multi-GPU: rows of AI partitioned over ranks, one RCCL all-reduce per
  *      NormalMatrix apply ---------------------------- */

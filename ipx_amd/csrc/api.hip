@@ -270,6 +270,8 @@ int ipxk_reset_solver_state(ipxk_context* c, double lu_pivottol) {
         c->W = nullptr;
         c->normal_prepared = c->diag_factorized = c->kkt_diag_factorized = c->it_set = false;
         c->sb_live = false;
+        c->postprocessed = false;
+        c->crossover_start = 0.0;
         c->kdense = 0;
         if (c->split) {
             if (c->split_spare) destroy_split(c->split_spare);
@@ -593,6 +595,7 @@ int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const d
         if (!comm_cols(c)) IPXK_REQUIRE(args, "NULL argument");
         bind_device(c);
         c->it_set = false;
+        c->postprocessed = false;
         c->sb_live = false;                 // a starting basis belongs to the iterate it was built from
         const size_t m = (size_t)c->m, n = (size_t)c->n, N = (size_t)(c->n + c->m);
         DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
@@ -774,6 +777,7 @@ int ipxk_ipm_starting_point(ipxk_context* c, const double* b, const double* cc, 
         const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
         const double* dub = stage_in(c, ub, N, c->nw_in[3]);
         c->sb_live = false;
+        c->postprocessed = false;
         ipm_starting_point_dev(c, db, dc, dlb, dub, params, info, interrupt, interrupt_user);
         IPXK_HIP(hipStreamSynchronize(c->stream));
     });
@@ -786,6 +790,7 @@ int ipxk_ipm_starting_basis(ipxk_context* c, const double* b, const double* cc, 
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && info, "NULL argument");
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // it runs the device LU
+        IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
         IPXK_REQUIRE(log_cap >= 0 && (exchange_log || log_cap == 0), "exchange_log is NULL");
         bind_device(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
@@ -807,6 +812,7 @@ int ipxk_ipm_load_starting_point(ipxk_context* c, const double* x, const double*
         IPXK_REQUIRE(args || comm_cols(c), "NULL argument");
         bind_device(c);
         c->it_set = false;
+        c->postprocessed = false;
         c->sb_live = false;                 // a starting basis belongs to the iterate it was built from
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         std::string err = args ? std::string() : std::string("NULL argument");
@@ -825,6 +831,75 @@ int ipxk_ipm_load_starting_point(ipxk_context* c, const double* x, const double*
         const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
         const double* dub = stage_in(c, ub, N, c->nw_in[3]);
         ipm_load_starting_point_dev(c, dlb, dub);
+    });
+}
+
+// ---- the end of the solve (finish.hip) -------------------------------------------------------------------------
+int ipxk_iterate_postprocess(ipxk_context* c, const double* cc, const double* lb, const double* ub) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && cc && lb && ub, "NULL argument");
+        bind_device(c);
+        const size_t N = (size_t)(c->n + c->m);
+        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        iterate_postprocess_dev(c, dc, dlb, dub);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_iterate_dropping_residuals(ipxk_context* c, const double* lb, const double* ub, double out2[2]) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && lb && ub && out2, "NULL argument");
+        bind_device(c);
+        const size_t N = (size_t)(c->n + c->m);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        iterate_dropping_residuals_dev(c, dlb, dub, out2);
+    });
+}
+
+int ipxk_ipm_set_crossover_start(ipxk_context* c, double value) {
+    return guarded([&] {
+        IPXK_REQUIRE(c != nullptr, "ctx is NULL");
+        IPXK_REQUIRE(value >= 0.0, "crossover_start must not be negative (0: off)");    // false for a NaN
+        c->crossover_start = value;
+    });
+}
+
+int ipxk_iterate_drop_to_complementarity(ipxk_context* c, const double* lb, const double* ub, double* x_out, double* y_out,
+                                         double* z_out) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && lb && ub && x_out && y_out && z_out, "NULL argument");
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        double* dx = stage_out(c, x_out, N, c->nw_out[0]);
+        double* dy = stage_out(c, y_out, m, c->nw_out[3]);
+        double* dz = stage_out(c, z_out, N, c->nw_out[1]);
+        iterate_drop_to_complementarity_dev(c, dlb, dub, dx, dy, dz);
+        finish_out(c, x_out, dx, N);
+        finish_out(c, y_out, dy, m);
+        finish_out(c, z_out, dz, N);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_ipm_solve(ipxk_context* c, const double* b, const double* cc, const double* lb, const double* ub,
+                   const ipxk_solve_params* params, ipxk_solve_info* info, ipxint* basis_out, ipxint* status_out,
+                   ipxk_interrupt_fn interrupt, void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && b && cc && lb && ub && params && info, "NULL argument");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // its basis phase runs the device LU and Maxvolume
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* db = stage_in(c, b, m, c->nw_in[0]);
+        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        ipm_solve_dev(c, db, dc, dlb, dub, params, info, basis_out, status_out, interrupt, interrupt_user);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
     });
 }
 

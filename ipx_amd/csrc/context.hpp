@@ -130,6 +130,13 @@ struct Context {
     DevBuf<unsigned char> it_state;
     bool it_set = false;
     DevBuf<double> ipm[12];            // residuals, complementarity targets and the step of ipxk_ipm_step
+    // the end of the solve (finish.hip): Iterate::postprocessed_ (residuals and objectives take the postprocessed branches, the
+    // iterate no longer advances), Iterate::crossover_start_ (0: the drivers stop at feasible and optimal), and max |a_ij| of every
+    // structural column for ResidualsFromDropping (computed at the first use, kept: the model never changes)
+    bool postprocessed = false;
+    double crossover_start = 0.0;
+    DevBuf<double> colmax;
+    bool have_colmax = false;
 
     // ---- basis path ----
     // guard of the explicit inverses (inverse_guard.hpp): # probes and # inverses rejected since the context was created, worst residual
@@ -307,6 +314,18 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
 
 // column partition: fingerprint of b and the slack parts of c, lb, ub (device), what the ranks of the device IPM agree on
 uint64_t model_fingerprint(Context* c, const double* b, const double* cc, const double* lb, const double* ub);
+
+// ---- finish.hip ----
+// every call that advances the iterate refuses a postprocessed one with this
+constexpr const char* kPostprocessedRefusal =
+    "the resident iterate has been postprocessed (ipxk_iterate_postprocess) and no longer advances: load an iterate again "
+    "(ipxk_iterate_set, ipxk_ipm_starting_point or ipxk_ipm_load_starting_point)";
+void iterate_postprocess_dev(Context* c, const double* cc, const double* lb, const double* ub);
+// out2 = pres, dres of Iterate::ResidualsFromDropping, over all ranks of a column partition
+void iterate_dropping_residuals_dev(Context* c, const double* lb, const double* ub, double out2[2]);
+void iterate_drop_to_complementarity_dev(Context* c, const double* lb, const double* ub, double* x, double* y, double* z);
+void ipm_solve_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, const ipxk_solve_params* prm,
+                   ipxk_solve_info* info, ipxint* basis_out, ipxint* status_out, ipxk_interrupt_fn interrupt, void* user);
 
 // ---- starting_basis.hip ----
 void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub,

@@ -81,6 +81,7 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
                   double kkt_tol, ipxint maxiter, ipxk_ipm_step_info* info, ipxk_interrupt_fn interrupt, void* user,
                   const IterScalars* pre, double* comp_after) {
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
+    IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
     const int n = (int)c->n, m = (int)c->m, N = n + m;
     hipStream_t s = c->stream;
     *info = ipxk_ipm_step_info{};
@@ -166,7 +167,7 @@ void ipm_step_dev(Context* c, bool use_basis, const double* b, const double* cc,
 }
 
 // IPM::Driver (src/ipm.cc:56-123) on the resident iterate, around the diag solver: termination test
-// (Iterate::term_crit_reached with crossover_start = 0, src/iterate.cc:221-249), the divergence / bad-iteration
+// (Iterate::term_crit_reached, src/iterate.cc:221-249, with Context::crossover_start), the divergence / bad-iteration
 // test with its infeasibility classification (:71-93, for a model that was not dualized), the iteration limit,
 // InterruptCheck, Factorize (kkt_solver_diag.cc:18-65 from the resident iterate), the predictor-corrector step,
 // and MakeStep's bad-iteration count and best complementarity (:520-530).  What ends the loop is reported as
@@ -252,6 +253,7 @@ static void driver_agree(Context* c, const double* b, const double* cc, const do
     std::string err;
     uint64_t fp = 0;
     if (!c->it_set) err = "no iterate on the device (ipxk_iterate_set)";
+    else if (c->postprocessed) err = kPostprocessedRefusal;
     else fp = model_fingerprint(c, b, cc, lb, ub);
     agree_on_arguments(c, err, fp, "ipxk_ipm_driver", "b and the slack parts of c, lb and ub");
 }
@@ -275,6 +277,7 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     IPXK_REQUIRE(!(use_basis && comm_active(c)), kDeviceLuRefusal);
     if (comm_cols(c)) driver_agree(c, b, cc, lb, ub);
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
+    IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
     std::vector<ipxint> basis, status;
     std::vector<double> colscale;
     if (use_basis) { basis.resize((size_t)c->m); status.resize((size_t)(c->n + c->m)); colscale.resize((size_t)(c->n + c->m)); }
@@ -308,7 +311,16 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
                               info->dresidual <= prm->feasibility_tol * (1.0 + norms[1]);
         const double mid = 0.5 * (info->pobjective + info->dobjective), gap = info->pobjective - info->dobjective;
         const bool optimal = std::abs(gap) <= prm->optimality_tol * (1.0 + std::abs(mid));
-        if (feasible && optimal) { info->status_ipm = 1; break; }                  // IPX_STATUS_optimal
+        if (feasible && optimal) {
+            // :239-245; feasible and optimal are replicated, so the ranks of a column partition enter the combine together
+            bool reached = c->crossover_start <= 0.0;
+            if (!reached) {
+                double drop[2];
+                iterate_dropping_residuals_dev(c, lb, ub, drop);
+                reached = drop[0] <= c->crossover_start * (1.0 + norms[0]) && drop[1] <= c->crossover_start * (1.0 + norms[1]);
+            }
+            if (reached) { info->status_ipm = 1; break; }                          // IPX_STATUS_optimal
+        }
         if (num_bad_iter >= 5 || comp[0] > kDivergeTol * best_complementarity) {
             if (info->dobjective > std::max(10.0 * std::abs(info->pobjective), 1.0)) info->status_ipm = 3;        // primal_infeas
             else if (info->pobjective < -std::max(10.0 * std::abs(info->dobjective), 1.0)) info->status_ipm = 4;  // dual_infeas

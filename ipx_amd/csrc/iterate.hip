@@ -46,13 +46,13 @@ struct EpiIterRb : ProdMul {
     __device__ __forceinline__ void finish(int r, double acc, double&) const { out[r] = acc - xI[r]; }
 };
 
-// rc[j] = ((c[j] - zl[j]) + zu[j]) - A_j'y, 0 on fixed variables
+// rc[j] = ((c[j] - zl[j]) + zu[j]) - A_j'y, 0 on fixed variables unless the iterate is postprocessed (iterate.cc:552-556)
 struct EpiIterRc : ProdMul {
-    const double* c; const double* zl; const double* zu; const unsigned char* state; double* out;
+    const double* c; const double* zl; const double* zu; const unsigned char* state; double* out; bool postprocessed;
     static constexpr bool kNeg = false;
     __device__ __forceinline__ double init(int) const { return 0.0; }
     __device__ __forceinline__ void finish(int j, double acc, double&) const {
-        out[j] = state[j] == IPXK_STATE_FIXED ? 0.0 : ((c[j] - zl[j]) + zu[j]) - acc;
+        out[j] = state[j] == IPXK_STATE_FIXED && !postprocessed ? 0.0 : ((c[j] - zl[j]) + zu[j]) - acc;
     }
 };
 
@@ -62,12 +62,13 @@ __global__ void iterate_bound_residuals_kernel(int n, int m, const unsigned char
                                                const double* __restrict__ ub, const double* __restrict__ x,
                                                const double* __restrict__ xl, const double* __restrict__ xu,
                                                const double* __restrict__ y, const double* __restrict__ zl,
-                                               const double* __restrict__ zu, double* __restrict__ rc,
-                                               double* __restrict__ rl, double* __restrict__ ru) {
+                                               const double* __restrict__ zu, bool postprocessed,
+                                               double* __restrict__ rc, double* __restrict__ rl,
+                                               double* __restrict__ ru) {
     const int N = n + m;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < N; j += gridDim.x * blockDim.x) {
         const unsigned char st = state[j];
-        if (j >= n) rc[j] = st == IPXK_STATE_FIXED ? 0.0 : ((c[j] - zl[j]) + zu[j]) - y[j - n];
+        if (j >= n) rc[j] = st == IPXK_STATE_FIXED && !postprocessed ? 0.0 : ((c[j] - zl[j]) + zu[j]) - y[j - n];
         rl[j] = has_lb(st) ? lb[j] - x[j] + xl[j] : 0.0;
         ru[j] = has_ub(st) ? ub[j] - x[j] - xu[j] : 0.0;
     }
@@ -158,6 +159,26 @@ __global__ __launch_bounds__(kBlock) void iterate_objectives_kernel(int n, int m
     dobj = block_reduce<SumOp>(dobj, red);
     if (threadIdx.x == 0) { out[blockIdx.x] = pobj; out[gridDim.x + blockIdx.x] = offset; out[2 * gridDim.x + blockIdx.x] = dobj; }
 }
+// the branch of a postprocessed iterate (iterate.cc:599-609): [0] sum c_j x_j, [1] b'y + sum lb_j zl_j - sum ub_j zu_j over the
+// finite bounds
+__global__ __launch_bounds__(kBlock) void iterate_objectives_post_kernel(int n, int m, const double* __restrict__ b,
+                                                                         const double* __restrict__ c, const double* __restrict__ lb,
+                                                                         const double* __restrict__ ub, const double* __restrict__ x,
+                                                                         const double* __restrict__ y, const double* __restrict__ zl,
+                                                                         const double* __restrict__ zu, double* out) {
+    __shared__ double red[kBlock / 64 + 1];
+    const int N = n + m;
+    double pobj = 0.0, dobj = 0.0;
+    for (int j = blockIdx.x * kBlock + threadIdx.x; j < N; j += gridDim.x * kBlock) {
+        pobj += c[j] * x[j];
+        if (j < m) dobj += b[j] * y[j];
+        if (isfinite(lb[j])) dobj += lb[j] * zl[j];
+        if (isfinite(ub[j])) dobj -= ub[j] * zu[j];
+    }
+    pobj = block_reduce<SumOp>(pobj, red);
+    dobj = block_reduce<SumOp>(dobj, red);
+    if (threadIdx.x == 0) { out[blockIdx.x] = pobj; out[gridDim.x + blockIdx.x] = dobj; }
+}
 // fixed structural variables: dot partial += x_j * (A_j'y)
 struct EpiObjFixed : ProdMul {
     const unsigned char* state; const double* x;
@@ -243,11 +264,11 @@ void residual_vectors(Context* c, const double* b, const double* cc, const doubl
     const int n = (int)c->n, m = (int)c->m, N = n + m;
     hipStream_t s = c->stream;
     residual_rb(c, b, c->it_x.get(), rb);
-    EpiIterRc ec{{}, cc, c->it_zl.get(), c->it_zu.get(), c->it_state.get(), rc};
+    EpiIterRc ec{{}, cc, c->it_zl.get(), c->it_zu.get(), c->it_state.get(), rc, c->postprocessed};
     launch_spmv(c->Acols, c->it_y.get(), ec, nullptr, nullptr, s);
     hipLaunchKernelGGL(iterate_bound_residuals_kernel, dim3(vec_grid(N)), dim3(kBlock), 0, s, n, m, c->it_state.get(),
                        cc, lb, ub, c->it_x.get(), c->it_xl.get(), c->it_xu.get(), c->it_y.get(), c->it_zl.get(),
-                       c->it_zu.get(), rc, rl, ru);
+                       c->it_zu.get(), c->postprocessed, rc, rl, ru);
 }
 
 // this rank's presidual, dresidual (max over its entries; rb is replicated)
@@ -288,6 +309,17 @@ void objectives_local(Context* c, const double* b, const double* cc, const doubl
     hipStream_t s = c->stream;
     const int g = vec_grid(N);
     c->it_partials.resize((size_t)4 * 1024);
+    if (c->postprocessed) {
+        hipLaunchKernelGGL(iterate_objectives_post_kernel, dim3(g), dim3(kBlock), 0, s, n, m, b, cc, lb, ub, c->it_x.get(),
+                           c->it_y.get(), c->it_zl.get(), c->it_zu.get(), c->it_partials.get());
+        std::vector<double> h((size_t)2 * g);
+        c->it_partials.download(h.data(), h.size(), s);
+        IPXK_HIP(hipGetLastError());
+        double pobj = 0.0, dobj = 0.0;
+        for (int i = 0; i < g; i++) { pobj += h[i]; dobj += h[(size_t)g + i]; }
+        out4[0] = pobj; out4[1] = 0.0; out4[2] = dobj; out4[3] = 0.0;
+        return;
+    }
     if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
     hipLaunchKernelGGL(iterate_objectives_kernel, dim3(g), dim3(kBlock), 0, s, n, m, c->it_state.get(), b, cc, lb, ub,
                        c->it_x.get(), c->it_y.get(), c->it_zl.get(), c->it_zu.get(), c->it_partials.get());
@@ -403,6 +435,7 @@ void model_norms_dev(Context* c, const double* b, const double* cc, const double
 void iterate_update_dev(Context* c, double sp, const double* dx, const double* dxl, const double* dxu, double sd,
                         const double* dy, const double* dzl, const double* dzu) {
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
+    IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
     const int n = (int)c->n, m = (int)c->m, N = n + m;
     hipLaunchKernelGGL(iterate_update_kernel, dim3(vec_grid(N)), dim3(kBlock), 0, c->stream, N, m, c->it_state.get(),
                        c->it_x.get(), c->it_xl.get(), c->it_xu.get(), c->it_y.get(), c->it_zl.get(), c->it_zu.get(),

@@ -34,7 +34,9 @@ EXPORTS = [
     "ipxk_iterate_residuals", "ipxk_iterate_complementarity", "ipxk_step_to_boundary", "ipxk_ipm_step", "ipxk_iterate_objectives", "ipxk_ipm_driver", "ipxk_iterate_factorize_diag", "ipxk_comm_unique_id", "ipxk_comm_init", "ipxk_comm_init_columns", "ipxk_comm_info", "ipxk_maxvolume_sequential",
     "ipxk_time_normal_apply", "ipxk_equilibrate", "ipxk_transpose", "ipxk_lu_factorize", "ipxk_lu_factorize_basis",
     "ipxk_lu_get_factors", "ipxk_lu_generation", "ipxk_split_prepare_lu", "ipxk_maxvolume", "ipxk_ipm_driver_basis",
-    "ipxk_ipm_starting_point", "ipxk_ipm_load_starting_point", "ipxk_ipm_starting_basis", "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
+    "ipxk_ipm_starting_point", "ipxk_ipm_load_starting_point", "ipxk_ipm_starting_basis", "ipxk_iterate_postprocess",
+    "ipxk_iterate_dropping_residuals", "ipxk_ipm_set_crossover_start", "ipxk_iterate_drop_to_complementarity", "ipxk_ipm_solve",
+    "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
     "ipxk_dev_download",
 ]
 
@@ -90,6 +92,20 @@ class StartingBasisInfo(C.Structure):
     _fields_ = [("errflag", c_i64), ("dependent_rows", c_i64), ("dependent_cols", c_i64), ("rows_inconsistent", c_i64),
                 ("cols_inconsistent", c_i64), ("updates_start", c_i64), ("stability_pivots", c_i64),
                 ("factorizations", c_i64), ("seconds", c_f64)]
+
+
+class SolveParams(C.Structure):
+    _fields_ = [("kkt_tol", c_f64), ("feasibility_tol", c_f64), ("optimality_tol", c_f64), ("crossover_start", c_f64),
+                ("dependency_tol", c_f64), ("ipm_maxiter", c_i64), ("switchiter", c_i64), ("max_etas", c_i64),
+                ("precond_dense_cols", C.c_int), ("use_resident_point", C.c_int)]
+
+
+class SolveInfo(C.Structure):
+    _fields_ = IpmInfo._fields_ + [
+        ("iter_initial", c_i64), ("status_initial", c_i64), ("dependent_rows", c_i64), ("dependent_cols", c_i64),
+        ("rows_inconsistent", c_i64), ("cols_inconsistent", c_i64), ("updates_start", c_i64), ("abs_presidual", c_f64),
+        ("abs_dresidual", c_f64), ("rel_presidual", c_f64), ("rel_dresidual", c_f64), ("rel_objgap", c_f64),
+        ("pres_dropping", c_f64), ("dres_dropping", c_f64)]
 
 
 class Times(C.Structure):
@@ -590,6 +606,45 @@ class KktContext:
         partition: the forms of iterate_set; collective."""
         vecs = [_F(it[key]) for key in self.IT_KEYS]
         self._check(self.lib.ipxk_ipm_load_starting_point(self.h, *[_fp(v) for v in vecs], _fp(_F(lb)), _fp(_F(ub))))
+
+    # -- the end of the solve -----------------------------------------------------------------
+    def iterate_postprocess(self, c, lb, ub):
+        """Iterate::Postprocess on the resident iterate; afterwards residuals and objectives take the postprocessed
+        branches and the iterate no longer advances until one is loaded again"""
+        self._check(self.lib.ipxk_iterate_postprocess(self.h, _fp(_F(c)), _fp(_F(lb)), _fp(_F(ub))))
+
+    def iterate_dropping_residuals(self, lb, ub):
+        """Iterate::ResidualsFromDropping: (pres, dres)"""
+        out = (C.c_double * 2)()
+        self._check(self.lib.ipxk_iterate_dropping_residuals(self.h, _fp(_F(lb)), _fp(_F(ub)), out))
+        return out[0], out[1]
+
+    def ipm_set_crossover_start(self, value):
+        self._check(self.lib.ipxk_ipm_set_crossover_start(self.h, c_f64(value)))
+
+    def iterate_drop_to_complementarity(self, lb, ub):
+        """Iterate::DropToComplementarity of the postprocessed iterate: (x, y, z), host vectors"""
+        N = self.n + self.m
+        x, y, z = np.zeros(N, f64), np.zeros(self.m, f64), np.zeros(N, f64)
+        self._check(self.lib.ipxk_iterate_drop_to_complementarity(self.h, _fp(_F(lb)), _fp(_F(ub)), _fp(x), _fp(y), _fp(z)))
+        return x, y, z
+
+    def ipm_solve(self, b, c, lb, ub, kkt_tol=0.3, feasibility_tol=1e-6, optimality_tol=1e-8, ipm_maxiter=300, switchiter=-1,
+                  precond_dense_cols=True, crossover_start=0.0, dependency_tol=1e-6, max_etas=100, use_resident_point=False,
+                  interrupt=None):
+        """LpSolver::InteriorPointSolve without presolve / postsolve: starting point, initial iterations, starting basis,
+        main phase, postprocessing and the evaluation of the result, in one call.  Returns the info fields plus the last
+        basis and statuses."""
+        prm = SolveParams(kkt_tol, feasibility_tol, optimality_tol, crossover_start, dependency_tol, ipm_maxiter, switchiter,
+                          max_etas, 1 if precond_dense_cols else 0, 1 if use_resident_point else 0)
+        info = SolveInfo()
+        basis, status = np.zeros(self.m, i64), np.zeros(self.n + self.m, i64)
+        cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
+        self._check(self.lib.ipxk_ipm_solve(self.h, _fp(_F(b)), _fp(_F(c)), _fp(_F(lb)), _fp(_F(ub)), C.byref(prm),
+                                            C.byref(info), _ip(basis), _ip(status), cb, None))
+        out = {name: getattr(info, name) for name, _ in SolveInfo._fields_}
+        out.update(basis=basis, status=status)
+        return out
 
     def kkt_diag_get(self):
         W, rs = np.zeros(self.n + self.m, f64), np.zeros(self.m, f64)
