@@ -10,9 +10,16 @@
 //    refresh with its monotonicity check (:186-207) are evaluated by the control kernel,
 //    which turns all later kernels into no-ops once `done` is set;
 //  * the host enqueues cycles of 5 iterations, stays at most kWindow cycles ahead of the
-//    GPU and learns about termination from a flag in mapped host memory.
-// Steady state per PCR iteration: 4 launches (control+update, SpMV pass 1, SpMV pass 2,
-// direction) touching 12 m-vectors instead of the ~22 of the unfused formulation.
+//    GPU and learns about termination from flags in mapped host memory: a snapshot of `done`
+//    per cycle, by which it leaves the loop, and (single rank) a flag the control kernel sets
+//    together with `done`, after which it enqueues no further iterations.
+// Steady state per PCR iteration: 4 launches (control, SpMV pass 1, SpMV pass 2, direction).
+// The control kernel is the one pass 1 waits for; it updates the residuals only (PcrDiag: reads
+// Cstep, residual, sresidual, diag, resscale, writes residual, sresidual: 7 vector accesses).  The
+// solution update lhs += alpha*step of the same iteration is made by the direction kernel, which
+// loads step anyway (reads (s)residual, step, Cres, Cstep, diag, lhs, writes step, Cstep, lhs: 9);
+// alpha travels through CrState.  16 accesses per iteration, against 17 with the update in the
+// control kernel (IPXK_CR_LAZY=0: that order, same bits) and ~22 in the unfused formulation.
 #include <cmath>
 
 #include "context.hpp"
@@ -23,6 +30,13 @@ namespace ipxk {
 constexpr int kWindow = 2;  // cycles (of 5 iterations) the host may run ahead
 
 enum CrMode { kModePcrDiag = 0, kModePcrSmw = 1, kModePlain = 2 };
+
+// The two vector kernels of an iteration run vec_grid(m) workgroups, which at 1M rows leaves a thread 4 elements of
+// the grid-stride loop.  Taken one at a time, each element's loads wait for the stores of the one before (the
+// vectors may alias as far as the compiler knows): 4 dependent round trips to HBM per thread.  So a thread loads
+// kCrUnroll elements (indices clamped to the last one, so that the loads need no predicate), then updates and
+// stores them in ascending order -- the same operations on the same values, and a thread's sums in the same order.
+constexpr int kCrUnroll = 4;
 
 struct CrVecs {
     int m;
@@ -76,14 +90,20 @@ __global__ __launch_bounds__(kBlock) void cr_init_state_kernel(CrState* st, doub
         st->hist_cap = hist_cap;
         st->diag_rps_old = st->diag_rps_new = 0.0;
         st->mode = mode;
+        st->alpha_pending = 0.0;
+        st->k_pending = -1;
     }
 }
 
-// Loop head + solution update of iteration k = st->k_finished.
+// Loop head + residual update of iteration k = st->k_finished.  The solution update lhs += alpha*step
+// is left to the direction kernel of the same iteration (alpha goes through st->alpha_pending); with
+// lazy == 0 it is done here, as it was before the update was deferred.  host_done (single rank, mapped
+// host memory): set together with st->done, so that the host stops enqueuing without waiting for the
+// cycle's snapshot.
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void cr_control_update_kernel(
     CrState* st, CrVecs v, PartRef res0, PartRef res1, PartRef pdot_ref, PartRef rsdot_ref,
-    double* res_next0, double* res_next1, double* hist) {
+    double* res_next0, double* res_next1, double* hist, int lazy, int* host_done) {
     if (st->done) return;
     __shared__ double red[kBlock / 64 + 1];
     const long long k = st->k_finished;
@@ -123,30 +143,53 @@ __global__ __launch_bounds__(kBlock) void cr_control_update_kernel(
             st->iter = k;
             st->resnorm = resnorm;
             st->done = 1;
+            if (host_done) __hip_atomic_store(host_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         return;
     }
 
-    // :173-175 / :72-73
+    // :173-175 / :72-73, kCrUnroll elements of the grid-stride loop at a time (see kCrUnroll)
     double mx = 0.0;
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < v.m; i += gridDim.x * kBlock) {
-        const double q = v.Cstep[i];
-        v.lhs[i] += alpha * v.step[i];
-        const double r = v.residual[i] - alpha * q;
-        v.residual[i] = r;
-        if (MODE == kModePcrDiag) v.sresidual[i] -= alpha * (q / v.diag[i]);
-        if (MODE == kModePcrSmw) v.sresidual[i] -= alpha * v.pCstep[i];
-        mx = MaxOp::apply(mx, fabs(v.resscale ? v.resscale[i] * r : r));
+    const long long stride = (long long)gridDim.x * kBlock, last = v.m - 1;
+    for (long long i0 = blockIdx.x * kBlock + threadIdx.x; i0 < v.m; i0 += kCrUnroll * stride) {
+        double q[kCrUnroll], r[kCrUnroll], sr[kCrUnroll] = {}, d[kCrUnroll] = {}, sc[kCrUnroll] = {};
+        double s[kCrUnroll] = {}, l[kCrUnroll] = {};
+#pragma unroll
+        for (int u = 0; u < kCrUnroll; u++) {
+            const long long i = min(i0 + u * stride, last);
+            q[u] = v.Cstep[i];
+            r[u] = v.residual[i];
+            if (MODE != kModePlain) sr[u] = v.sresidual[i];
+            if (MODE == kModePcrDiag) d[u] = v.diag[i];
+            if (MODE == kModePcrSmw) d[u] = v.pCstep[i];
+            if (v.resscale) sc[u] = v.resscale[i];
+            if (!lazy) { s[u] = v.step[i]; l[u] = v.lhs[i]; }
+        }
+#pragma unroll
+        for (int u = 0; u < kCrUnroll; u++) {
+            const long long i = i0 + u * stride;
+            if (i > last) break;
+            if (!lazy) v.lhs[i] = l[u] + alpha * s[u];
+            const double rn = r[u] - alpha * q[u];
+            v.residual[i] = rn;
+            if (MODE == kModePcrDiag) v.sresidual[i] = sr[u] - alpha * (q[u] / d[u]);
+            if (MODE == kModePcrSmw) v.sresidual[i] = sr[u] - alpha * d[u];
+            mx = MaxOp::apply(mx, fabs(v.resscale ? sc[u] * rn : rn));
+        }
     }
     mx = block_reduce<MaxOp>(mx, red);
     if (threadIdx.x == 0) ((k & 1) ? res_next0 : res_next1)[blockIdx.x] = mx;
     if (writer) {
         st->k_started = k + 1;
         st->resnorm = resnorm;
+        if (lazy) { st->alpha_pending = alpha; st->k_pending = k; }
     }
 }
 
-// :180-184 / :78-81  new search direction; INIT: step = (s)residual, Cstep = C*(s)residual
+// :180-184 / :78-81  new search direction; INIT: step = (s)residual, Cstep = C*(s)residual.
+// An owed solution update (:173 / :72, lhs += alpha*step with the alpha of this iteration's control
+// kernel) is paid first, with the step[i] that is loaded anyway and before it is overwritten.  The mark
+// is not cleared here (other workgroups may still be reading it): the store of k_finished retires it.
 template <int MODE, bool INIT>
 __global__ __launch_bounds__(kBlock) void cr_direction_kernel(CrState* st, CrVecs v, PartRef cdot_ref,
                                                               double* pdot_partial) {
@@ -156,20 +199,35 @@ __global__ __launch_bounds__(kBlock) void cr_direction_kernel(CrState* st, CrVec
     const double cdotnew = reduce_partials<SumOp>(cdot_ref, red);
     const double beta = INIT ? 0.0 : cdotnew / st->cdot[k & 1];
     const double* src = MODE == kModePlain ? v.residual : v.sresidual;
-    double acc = 0.0;
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < v.m; i += gridDim.x * kBlock) {
-        double p, q;
-        if (INIT) {
-            p = src[i];
-            q = v.Cres[i];
-        } else {
-            p = src[i] + beta * v.step[i];
-            q = v.Cres[i] + beta * v.Cstep[i];
+    const bool owed = !INIT && st->k_pending == k;
+    const double alpha = st->alpha_pending;
+    double acc = 0.0;   // a thread adds its elements in ascending order, unrolled or not: the partials keep their bits
+    const long long stride = (long long)gridDim.x * kBlock, last = v.m - 1;
+    for (long long i0 = blockIdx.x * kBlock + threadIdx.x; i0 < v.m; i0 += kCrUnroll * stride) {
+        double p[kCrUnroll], q[kCrUnroll], s[kCrUnroll] = {}, cs[kCrUnroll] = {}, d[kCrUnroll] = {}, l[kCrUnroll] = {};
+#pragma unroll
+        for (int u = 0; u < kCrUnroll; u++) {
+            const long long i = min(i0 + u * stride, last);
+            p[u] = src[i];
+            q[u] = v.Cres[i];
+            if (!INIT) { s[u] = v.step[i]; cs[u] = v.Cstep[i]; }
+            if (MODE == kModePcrDiag) d[u] = v.diag[i];
+            if (owed) l[u] = v.lhs[i];
         }
-        v.step[i] = p;
-        v.Cstep[i] = q;
-        if (MODE == kModePcrDiag) acc += (q / v.diag[i]) * q;   // pdot of diagonal_precond.cc:152-154
-        if (MODE == kModePlain) acc += q * q;                   // Dot(Cstep,Cstep), :66
+#pragma unroll
+        for (int u = 0; u < kCrUnroll; u++) {
+            const long long i = i0 + u * stride;
+            if (i > last) break;
+            if (!INIT) {
+                if (owed) v.lhs[i] = l[u] + alpha * s[u];
+                p[u] = p[u] + beta * s[u];
+                q[u] = q[u] + beta * cs[u];
+            }
+            v.step[i] = p[u];
+            v.Cstep[i] = q[u];
+            if (MODE == kModePcrDiag) acc += (q[u] / d[u]) * q[u];   // pdot of diagonal_precond.cc:152-154
+            if (MODE == kModePlain) acc += q[u] * q[u];              // Dot(Cstep,Cstep), :66
+        }
     }
     if (MODE != kModePcrSmw) {
         acc = block_reduce<SumOp>(acc, red);
@@ -179,6 +237,16 @@ __global__ __launch_bounds__(kBlock) void cr_direction_kernel(CrState* st, CrVec
         st->cdot[(k + 1) & 1] = cdotnew;
         st->k_finished = k + 1;
     }
+}
+
+// Pays a solution update that no direction kernel paid.  In the order run_cr enqueues the kernels every
+// control kernel that marks an update is followed by the direction kernel of its iteration, and nothing in
+// between can set `done`, so on every way out of the loop this finds nothing owed; it is enqueued once after
+// the loop so that lhs does not depend on that order staying as it is.  Not gated on `done`; writes no state.
+__global__ __launch_bounds__(kBlock) void cr_flush_update_kernel(const CrState* st, CrVecs v) {
+    if (st->k_pending < 0 || st->k_pending != st->k_finished) return;
+    const double alpha = st->alpha_pending;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < v.m; i += gridDim.x * kBlock) v.lhs[i] += alpha * v.step[i];
 }
 
 __global__ __launch_bounds__(kBlock) void finalize_scalar_kernel(PartRef ref, int op, double* out) {
@@ -208,6 +276,13 @@ __global__ void snapshot_flags_kernel(const double* flags, int* host_done, int* 
 // host side
 // ---------------------------------------------------------------------------
 constexpr int kDoneRing = kWindow + 2;
+constexpr int kDoneNow = 2 * kDoneRing;   // slot of h_cycle_done the control kernel sets with st->done (single rank)
+
+// IPXK_CR_LAZY=0: the control kernel updates lhs itself (the order before the update was deferred; A/B runs and tests)
+static bool cr_lazy() {
+    static const bool setting = [] { const char* e = getenv("IPXK_CR_LAZY"); return !e || atoi(e) != 0; }();
+    return setting;
+}
 
 static void ensure_comm_buffers(Context* c) {
     if (c->comm_scalars.size() < 64) c->comm_scalars.resize(64);
@@ -334,8 +409,11 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     int* done = &st->done;
     const int g = vec_grid(m);
     const Pub pub(c);
-    for (int i = 0; i < 2 * kDoneRing; i++) c->h_cycle_done[i] = 0;   // previous solve is synchronized
+    for (int i = 0; i <= kDoneNow; i++) c->h_cycle_done[i] = 0;   // previous solve is synchronized
     const bool multi = comm_active(c);
+    const int lazy = cr_lazy() ? 1 : 0;
+    // partitioned: every rank enqueues the same collectives, so the ranks leave by the agreed snapshots alone
+    int* done_now = multi ? nullptr : c->d_cycle_done + kDoneNow;
     if (multi) ensure_comm_buffers(c);
 
     CrVecs v;
@@ -377,8 +455,11 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     // cycle (a system that needs no iteration returns its result whatever the callback says).  Single rank:
     // a nonzero flag ends the loop at once.  Partitioned: the flag travels with the cycle's `done` snapshot
     // through one all-reduce (max), so every rank leaves in the same cycle, kWindow cycles later.
+    // Single rank: once the control kernel has reported `done` (kDoneNow) everything enqueued from then on would
+    // return at once, so the iterations are no longer enqueued; the cycles' snapshots and events still are, and
+    // the loop is left as before, through the snapshot of the cycle kWindow back.
     ipxint interrupt_flag = 0, my_interrupt = 0;
-    bool agreed_done = false;
+    bool agreed_done = false, tail = false;
     for (long long cycle = 0;; cycle++) {
         const long long k0 = cycle * 5;
         if (k0 > maxiter) break;
@@ -396,9 +477,11 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
             if (!multi && my_interrupt != 0) { interrupt_flag = my_interrupt; break; }
         }
         for (long long k = k0; k < k0 + 5 && k <= maxiter; k++) {
+            if (done_now && *(volatile int*)(c->h_cycle_done + kDoneNow)) tail = true;
+            if (tail) break;
             hipLaunchKernelGGL((cr_control_update_kernel<MODE>), dim3(g), dim3(kBlock), 0, s, st, v,
                                res0, res1, pdot_ref, rsdot, c->part(kPartRes0), c->part(kPartRes1),
-                               c->hist.get());
+                               c->hist.get(), lazy, done_now);
             ncdot = ops.applyC(c, csrc, v.Cres, done);
             // the control kernel of iteration k wrote the residual-norm partials of parity (k+1)&1
             pub.publish(kPartCdot, ncdot, 0, ((k + 1) & 1) ? kPartRes1 : kPartRes0, g, 1);
@@ -423,6 +506,7 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
         }
         IPXK_HIP(hipEventRecord(c->ev_window[cycle % (kWindow + 1)], s));
     }
+    if (lazy) hipLaunchKernelGGL(cr_flush_update_kernel, dim3(g), dim3(kBlock), 0, s, st, v);
     IPXK_HIP(hipEventRecord(c->ev_b, s));
     IPXK_HIP(hipMemcpyAsync(c->h_state, st, sizeof(CrState), hipMemcpyDeviceToHost, s));
     IPXK_HIP(hipStreamSynchronize(s));

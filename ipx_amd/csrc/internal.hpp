@@ -456,6 +456,10 @@ struct CrState {
     long long hist_cap;
     double diag_rps_old, diag_rps_new;   // errflag 204: the two values of the monotonicity check
     int mode;                            // CrMode of the run (cr.hip)
+    // lazy solution update: lhs += alpha_pending * step of iteration k_pending is still owed while
+    // k_pending == k_finished (the direction kernel that pays it moves k_finished on); -1: nothing owed
+    double alpha_pending;
+    long long k_pending;
 };
 
 // ---------------------------------------------------------------------------
