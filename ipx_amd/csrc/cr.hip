@@ -95,45 +95,136 @@ __global__ __launch_bounds__(kBlock) void cr_init_state_kernel(CrState* st, doub
     }
 }
 
+// The elements i0, i0 + stride, ... (kCrUnroll of them) of the control kernel's loop: the loads, from indices clamped to
+// `last`, and the update with its stores, which skips the elements past `last`.
+struct CtlGroup {
+    double q[kCrUnroll], r[kCrUnroll], sr[kCrUnroll], d[kCrUnroll], sc[kCrUnroll], s[kCrUnroll], l[kCrUnroll];
+};
+template <int MODE>
+__device__ __forceinline__ void ctl_load(const CrVecs& v, int lazy, long long i0, long long stride, long long last, CtlGroup& g) {
+#pragma unroll
+    for (int u = 0; u < kCrUnroll; u++) {
+        const long long i = min(i0 + u * stride, last);
+        g.q[u] = v.Cstep[i];
+        g.r[u] = v.residual[i];
+        if (MODE != kModePlain) g.sr[u] = v.sresidual[i];
+        if (MODE == kModePcrDiag) g.d[u] = v.diag[i];
+        if (MODE == kModePcrSmw) g.d[u] = v.pCstep[i];
+        if (v.resscale) g.sc[u] = v.resscale[i];
+        if (!lazy) { g.s[u] = v.step[i]; g.l[u] = v.lhs[i]; }
+    }
+}
+template <int MODE>
+__device__ __forceinline__ void ctl_update(const CrVecs& v, int lazy, double alpha, long long i0, long long stride, long long last,
+                                           const CtlGroup& g, double& mx) {
+#pragma unroll
+    for (int u = 0; u < kCrUnroll; u++) {
+        const long long i = i0 + u * stride;
+        if (i > last) break;
+        if (!lazy) v.lhs[i] = g.l[u] + alpha * g.s[u];
+        const double rn = g.r[u] - alpha * g.q[u];
+        v.residual[i] = rn;
+        if (MODE == kModePcrDiag) v.sresidual[i] = g.sr[u] - alpha * (g.q[u] / g.d[u]);
+        if (MODE == kModePcrSmw) v.sresidual[i] = g.sr[u] - alpha * g.d[u];
+        mx = MaxOp::apply(mx, fabs(v.resscale ? g.sc[u] * rn : rn));
+    }
+}
+
 // Loop head + residual update of iteration k = st->k_finished.  The solution update lhs += alpha*step
 // is left to the direction kernel of the same iteration (alpha goes through st->alpha_pending); with
 // lazy == 0 it is done here, as it was before the update was deferred.  host_done (single rank, mapped
 // host memory): set together with st->done, so that the host stops enqueuing without waiting for the
 // cycle's snapshot.
-template <int MODE>
+// EARLY: none of the vector loads depends on a loop scalar (the addresses come from the arguments), so the thread's
+// first group of loads is issued before anything waits for one: the fields of CrState are read in one batch, then the
+// pdot partials, the group and the residual-norm partials (every fifth iteration the rsdot partials too) are all in
+// flight together, and the two reductions share their barriers.  Those barriers also keep the loads where they are:
+// the `done` test comes after them.  All stores stay behind that test and the errflag decisions, in the order of the
+// other form.  A launch that finds `done` set or leaves through an errflag has then loaded what it does not use: three
+// launches of a solve, from buffers that are valid for the whole solve.  !EARLY (IPXK_CR_EARLY=0) is the order before:
+// the scalars one after another, then the loads.  Same operations on the same values either way.
+template <int MODE, bool EARLY>
 __global__ __launch_bounds__(kBlock) void cr_control_update_kernel(
     CrState* st, CrVecs v, PartRef res0, PartRef res1, PartRef pdot_ref, PartRef rsdot_ref,
     double* res_next0, double* res_next1, double* hist, int lazy, int* host_done) {
-    if (st->done) return;
     __shared__ double red[kBlock / 64 + 1];
-    const long long k = st->k_finished;
     const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+    const long long stride = (long long)gridDim.x * kBlock, last = v.m - 1;
+    const long long first = blockIdx.x * kBlock + threadIdx.x;
+    long long k;
     int errflag = -1;  // -1: continue
-    double resnorm = st->resnorm;
-
-    if (MODE != kModePlain && k > 0 && k % 5 == 0) {
-        // :195-206 monotonicity of residual'*P*residual over the last 5 iterations
-        const double rsdot = reduce_partials<SumOp>(rsdot_ref, red);
-        const long long c5 = k / 5;
-        if (rsdot >= st->rps[(c5 - 1) & 1]) {
-            errflag = 204;                                     // IPX_ERROR_cr_no_progress
-            if (writer) { st->diag_rps_old = st->rps[(c5 - 1) & 1]; st->diag_rps_new = rsdot; }
-        } else if (writer) st->rps[c5 & 1] = rsdot;
-    }
-    double alpha = 0.0;
-    if (errflag < 0) {
-        resnorm = reduce_partials<MaxOp>((k & 1) ? res1 : res0, red);
-        if (writer && k < st->hist_cap) hist[k] = resnorm;
-        const double cdot = st->cdot[k & 1];
-        if (resnorm <= st->tol) errflag = 0;
-        else if (k == st->maxiter) errflag = 201;             // IPX_ERROR_cr_iter_limit
-        else if (cdot <= 0.0) errflag = 202;                  // IPX_ERROR_cr_matrix_not_posdef
-        else {
-            const double pdot = reduce_partials<SumOp>(pdot_ref, red);
-            if (MODE != kModePlain && pdot <= 0.0) errflag = 203;  // IPX_ERROR_cr_precond_not_posdef
+    double resnorm, alpha = 0.0;
+    CtlGroup g0{};
+    if (EARLY) {
+        __shared__ double red2[kBlock / 64 + 1];
+        const int done = st->done;
+        k = st->k_finished;
+        const long long maxiter = st->maxiter, hist_cap = st->hist_cap;
+        const double tol = st->tol, cdot0 = st->cdot[0], cdot1 = st->cdot[1], rps0 = st->rps[0], rps1 = st->rps[1];
+        resnorm = st->resnorm;
+        double pp[kPartialsPerThread], pr[kPartialsPerThread], ps[kPartialsPerThread];
+        load_partials(pdot_ref, pp);
+        ctl_load<MODE>(v, lazy, first, stride, last, g0);
+        const bool check5 = MODE != kModePlain && k > 0 && k % 5 == 0;
+        const PartRef res_ref = (k & 1) ? res1 : res0;
+        load_partials(res_ref, pr);
+        double rsdot = 0.0;
+        if (check5) {
+            load_partials(rsdot_ref, ps);
+            rsdot = block_reduce<SumOp>(fold_partials<SumOp>(rsdot_ref, ps), red);
+        }
+        double rn = fold_partials<MaxOp>(res_ref, pr), pdot = fold_partials<SumOp>(pdot_ref, pp);
+        block_reduce2<MaxOp, SumOp>(rn, pdot, red, red2);
+        if (done) return;
+        if (check5) {
+            // :195-206 monotonicity of residual'*P*residual over the last 5 iterations
+            const long long c5 = k / 5;
+            const double rps_old = ((c5 - 1) & 1) ? rps1 : rps0;
+            if (rsdot >= rps_old) {
+                errflag = 204;                                     // IPX_ERROR_cr_no_progress
+                if (writer) { st->diag_rps_old = rps_old; st->diag_rps_new = rsdot; }
+            } else if (writer) st->rps[c5 & 1] = rsdot;
+        }
+        if (errflag < 0) {
+            resnorm = rn;
+            if (writer && k < hist_cap) hist[k] = resnorm;
+            const double cdot = (k & 1) ? cdot1 : cdot0;
+            if (resnorm <= tol) errflag = 0;
+            else if (k == maxiter) errflag = 201;                 // IPX_ERROR_cr_iter_limit
+            else if (cdot <= 0.0) errflag = 202;                  // IPX_ERROR_cr_matrix_not_posdef
+            else if (MODE != kModePlain && pdot <= 0.0) errflag = 203;  // IPX_ERROR_cr_precond_not_posdef
             else {
                 alpha = cdot / pdot;
-                if (!isfinite(alpha)) errflag = 205;          // IPX_ERROR_cr_inf_or_nan
+                if (!isfinite(alpha)) errflag = 205;              // IPX_ERROR_cr_inf_or_nan
+            }
+        }
+    } else {
+        if (st->done) return;
+        k = st->k_finished;
+        resnorm = st->resnorm;
+        if (MODE != kModePlain && k > 0 && k % 5 == 0) {
+            // :195-206 monotonicity of residual'*P*residual over the last 5 iterations
+            const double rsdot = reduce_partials<SumOp>(rsdot_ref, red);
+            const long long c5 = k / 5;
+            if (rsdot >= st->rps[(c5 - 1) & 1]) {
+                errflag = 204;                                     // IPX_ERROR_cr_no_progress
+                if (writer) { st->diag_rps_old = st->rps[(c5 - 1) & 1]; st->diag_rps_new = rsdot; }
+            } else if (writer) st->rps[c5 & 1] = rsdot;
+        }
+        if (errflag < 0) {
+            resnorm = reduce_partials<MaxOp>((k & 1) ? res1 : res0, red);
+            if (writer && k < st->hist_cap) hist[k] = resnorm;
+            const double cdot = st->cdot[k & 1];
+            if (resnorm <= st->tol) errflag = 0;
+            else if (k == st->maxiter) errflag = 201;             // IPX_ERROR_cr_iter_limit
+            else if (cdot <= 0.0) errflag = 202;                  // IPX_ERROR_cr_matrix_not_posdef
+            else {
+                const double pdot = reduce_partials<SumOp>(pdot_ref, red);
+                if (MODE != kModePlain && pdot <= 0.0) errflag = 203;  // IPX_ERROR_cr_precond_not_posdef
+                else {
+                    alpha = cdot / pdot;
+                    if (!isfinite(alpha)) errflag = 205;          // IPX_ERROR_cr_inf_or_nan
+                }
             }
         }
     }
@@ -150,32 +241,15 @@ __global__ __launch_bounds__(kBlock) void cr_control_update_kernel(
 
     // :173-175 / :72-73, kCrUnroll elements of the grid-stride loop at a time (see kCrUnroll)
     double mx = 0.0;
-    const long long stride = (long long)gridDim.x * kBlock, last = v.m - 1;
-    for (long long i0 = blockIdx.x * kBlock + threadIdx.x; i0 < v.m; i0 += kCrUnroll * stride) {
-        double q[kCrUnroll], r[kCrUnroll], sr[kCrUnroll] = {}, d[kCrUnroll] = {}, sc[kCrUnroll] = {};
-        double s[kCrUnroll] = {}, l[kCrUnroll] = {};
-#pragma unroll
-        for (int u = 0; u < kCrUnroll; u++) {
-            const long long i = min(i0 + u * stride, last);
-            q[u] = v.Cstep[i];
-            r[u] = v.residual[i];
-            if (MODE != kModePlain) sr[u] = v.sresidual[i];
-            if (MODE == kModePcrDiag) d[u] = v.diag[i];
-            if (MODE == kModePcrSmw) d[u] = v.pCstep[i];
-            if (v.resscale) sc[u] = v.resscale[i];
-            if (!lazy) { s[u] = v.step[i]; l[u] = v.lhs[i]; }
-        }
-#pragma unroll
-        for (int u = 0; u < kCrUnroll; u++) {
-            const long long i = i0 + u * stride;
-            if (i > last) break;
-            if (!lazy) v.lhs[i] = l[u] + alpha * s[u];
-            const double rn = r[u] - alpha * q[u];
-            v.residual[i] = rn;
-            if (MODE == kModePcrDiag) v.sresidual[i] = sr[u] - alpha * (q[u] / d[u]);
-            if (MODE == kModePcrSmw) v.sresidual[i] = sr[u] - alpha * d[u];
-            mx = MaxOp::apply(mx, fabs(v.resscale ? sc[u] * rn : rn));
-        }
+    long long i0 = first;
+    if (EARLY) {
+        ctl_update<MODE>(v, lazy, alpha, i0, stride, last, g0, mx);
+        i0 += kCrUnroll * stride;
+    }
+    for (; i0 < v.m; i0 += kCrUnroll * stride) {
+        CtlGroup g{};
+        ctl_load<MODE>(v, lazy, i0, stride, last, g);
+        ctl_update<MODE>(v, lazy, alpha, i0, stride, last, g, mx);
     }
     mx = block_reduce<MaxOp>(mx, red);
     if (threadIdx.x == 0) ((k & 1) ? res_next0 : res_next1)[blockIdx.x] = mx;
@@ -186,48 +260,92 @@ __global__ __launch_bounds__(kBlock) void cr_control_update_kernel(
     }
 }
 
+// one group of the direction kernel's loop, as CtlGroup; lhs is loaded where with_lhs says so
+struct DirGroup {
+    double p[kCrUnroll], q[kCrUnroll], s[kCrUnroll], cs[kCrUnroll], d[kCrUnroll], l[kCrUnroll];
+};
+template <int MODE, bool INIT>
+__device__ __forceinline__ void dir_load(const CrVecs& v, const double* src, bool with_lhs, long long i0, long long stride,
+                                         long long last, DirGroup& g) {
+#pragma unroll
+    for (int u = 0; u < kCrUnroll; u++) {
+        const long long i = min(i0 + u * stride, last);
+        g.p[u] = src[i];
+        g.q[u] = v.Cres[i];
+        if (!INIT) { g.s[u] = v.step[i]; g.cs[u] = v.Cstep[i]; }
+        if (MODE == kModePcrDiag) g.d[u] = v.diag[i];
+        if (!INIT && with_lhs) g.l[u] = v.lhs[i];
+    }
+}
+template <int MODE, bool INIT>
+__device__ __forceinline__ void dir_update(const CrVecs& v, bool owed, double alpha, double beta, long long i0, long long stride,
+                                           long long last, DirGroup& g, double& acc) {
+#pragma unroll
+    for (int u = 0; u < kCrUnroll; u++) {
+        const long long i = i0 + u * stride;
+        if (i > last) break;
+        if (!INIT) {
+            if (owed) v.lhs[i] = g.l[u] + alpha * g.s[u];
+            g.p[u] = g.p[u] + beta * g.s[u];
+            g.q[u] = g.q[u] + beta * g.cs[u];
+        }
+        v.step[i] = g.p[u];
+        v.Cstep[i] = g.q[u];
+        if (MODE == kModePcrDiag) acc += (g.q[u] / g.d[u]) * g.q[u];   // pdot of diagonal_precond.cc:152-154
+        if (MODE == kModePlain) acc += g.q[u] * g.q[u];                // Dot(Cstep,Cstep), :66
+    }
+}
+
 // :180-184 / :78-81  new search direction; INIT: step = (s)residual, Cstep = C*(s)residual.
 // An owed solution update (:173 / :72, lhs += alpha*step with the alpha of this iteration's control
 // kernel) is paid first, with the step[i] that is loaded anyway and before it is overwritten.  The mark
 // is not cleared here (other workgroups may still be reading it): the store of k_finished retires it.
-template <int MODE, bool INIT>
+// EARLY, as in the control kernel: CrState in one batch, the cdot partials and the thread's first group of loads in
+// flight before the reduction's barriers, the `done` test after them.  Whether an update is owed is not known when the
+// group is loaded, so lhs is loaded with it and only the store is conditional; in the order run_cr enqueues the
+// kernels every direction kernel of the loop owes one, so nothing is read for nothing there.
+template <int MODE, bool INIT, bool EARLY>
 __global__ __launch_bounds__(kBlock) void cr_direction_kernel(CrState* st, CrVecs v, PartRef cdot_ref,
                                                               double* pdot_partial) {
-    if (st->done) return;
     __shared__ double red[kBlock / 64 + 1];
-    const long long k = INIT ? -1 : st->k_started - 1;
-    const double cdotnew = reduce_partials<SumOp>(cdot_ref, red);
-    const double beta = INIT ? 0.0 : cdotnew / st->cdot[k & 1];
     const double* src = MODE == kModePlain ? v.residual : v.sresidual;
-    const bool owed = !INIT && st->k_pending == k;
-    const double alpha = st->alpha_pending;
-    double acc = 0.0;   // a thread adds its elements in ascending order, unrolled or not: the partials keep their bits
     const long long stride = (long long)gridDim.x * kBlock, last = v.m - 1;
-    for (long long i0 = blockIdx.x * kBlock + threadIdx.x; i0 < v.m; i0 += kCrUnroll * stride) {
-        double p[kCrUnroll], q[kCrUnroll], s[kCrUnroll] = {}, cs[kCrUnroll] = {}, d[kCrUnroll] = {}, l[kCrUnroll] = {};
-#pragma unroll
-        for (int u = 0; u < kCrUnroll; u++) {
-            const long long i = min(i0 + u * stride, last);
-            p[u] = src[i];
-            q[u] = v.Cres[i];
-            if (!INIT) { s[u] = v.step[i]; cs[u] = v.Cstep[i]; }
-            if (MODE == kModePcrDiag) d[u] = v.diag[i];
-            if (owed) l[u] = v.lhs[i];
-        }
-#pragma unroll
-        for (int u = 0; u < kCrUnroll; u++) {
-            const long long i = i0 + u * stride;
-            if (i > last) break;
-            if (!INIT) {
-                if (owed) v.lhs[i] = l[u] + alpha * s[u];
-                p[u] = p[u] + beta * s[u];
-                q[u] = q[u] + beta * cs[u];
-            }
-            v.step[i] = p[u];
-            v.Cstep[i] = q[u];
-            if (MODE == kModePcrDiag) acc += (q[u] / d[u]) * q[u];   // pdot of diagonal_precond.cc:152-154
-            if (MODE == kModePlain) acc += q[u] * q[u];              // Dot(Cstep,Cstep), :66
-        }
+    const long long first = blockIdx.x * kBlock + threadIdx.x;
+    long long k;
+    double cdotnew, beta, alpha;
+    bool owed;
+    DirGroup g0{};
+    if (EARLY) {
+        const int done = st->done;
+        const long long k_started = st->k_started, k_pending = st->k_pending;
+        const double cdot0 = st->cdot[0], cdot1 = st->cdot[1];
+        alpha = st->alpha_pending;
+        double pc[kPartialsPerThread];
+        load_partials(cdot_ref, pc);
+        dir_load<MODE, INIT>(v, src, true, first, stride, last, g0);
+        cdotnew = block_reduce<SumOp>(fold_partials<SumOp>(cdot_ref, pc), red);
+        if (done) return;
+        k = INIT ? -1 : k_started - 1;
+        beta = INIT ? 0.0 : cdotnew / ((k & 1) ? cdot1 : cdot0);
+        owed = !INIT && k_pending == k;
+    } else {
+        if (st->done) return;
+        k = INIT ? -1 : st->k_started - 1;
+        cdotnew = reduce_partials<SumOp>(cdot_ref, red);
+        beta = INIT ? 0.0 : cdotnew / st->cdot[k & 1];
+        owed = !INIT && st->k_pending == k;
+        alpha = st->alpha_pending;
+    }
+    double acc = 0.0;   // a thread adds its elements in ascending order, unrolled or not: the partials keep their bits
+    long long i0 = first;
+    if (EARLY) {
+        dir_update<MODE, INIT>(v, owed, alpha, beta, i0, stride, last, g0, acc);
+        i0 += kCrUnroll * stride;
+    }
+    for (; i0 < v.m; i0 += kCrUnroll * stride) {
+        DirGroup g{};
+        dir_load<MODE, INIT>(v, src, owed, i0, stride, last, g);
+        dir_update<MODE, INIT>(v, owed, alpha, beta, i0, stride, last, g, acc);
     }
     if (MODE != kModePcrSmw) {
         acc = block_reduce<SumOp>(acc, red);
@@ -281,6 +399,13 @@ constexpr int kDoneNow = 2 * kDoneRing;   // slot of h_cycle_done the control ke
 // IPXK_CR_LAZY=0: the control kernel updates lhs itself (the order before the update was deferred; A/B runs and tests)
 static bool cr_lazy() {
     static const bool setting = [] { const char* e = getenv("IPXK_CR_LAZY"); return !e || atoi(e) != 0; }();
+    return setting;
+}
+
+// IPXK_CR_EARLY=0: the two vector kernels fetch their scalars first and load afterwards (the order before the loads were
+// issued first; A/B runs and tests)
+static bool cr_early() {
+    static const bool setting = [] { const char* e = getenv("IPXK_CR_EARLY"); return !e || atoi(e) != 0; }();
     return setting;
 }
 
@@ -412,6 +537,10 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     for (int i = 0; i <= kDoneNow; i++) c->h_cycle_done[i] = 0;   // previous solve is synchronized
     const bool multi = comm_active(c);
     const int lazy = cr_lazy() ? 1 : 0;
+    const bool early = cr_early() && m > 0;   // (the early loads read element 0 of every vector)
+    const auto control = early ? cr_control_update_kernel<MODE, true> : cr_control_update_kernel<MODE, false>;
+    const auto direction0 = early ? cr_direction_kernel<MODE, true, true> : cr_direction_kernel<MODE, true, false>;
+    const auto direction = early ? cr_direction_kernel<MODE, false, true> : cr_direction_kernel<MODE, false, false>;
     // partitioned: every rank enqueues the same collectives, so the ranks leave by the agreed snapshots alone
     int* done_now = multi ? nullptr : c->d_cycle_done + kDoneNow;
     if (multi) ensure_comm_buffers(c);
@@ -443,7 +572,7 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     const double* csrc = MODE == kModePlain ? v.residual : v.sresidual;
     int ncdot = ops.applyC(c, csrc, v.Cres, nullptr);
     pub.publish(kPartCdot, ncdot, 0);
-    hipLaunchKernelGGL((cr_direction_kernel<MODE, true>), dim3(g), dim3(kBlock), 0, s, st, v,
+    hipLaunchKernelGGL(direction0, dim3(g), dim3(kBlock), 0, s, st, v,
                        pub.ref(kPartCdot, ncdot), c->part(kPartPdot));
     int npdot = g;
     if (MODE == kModePcrSmw) npdot = diag_apply_dev(c, v.Cstep, v.pCstep, kPartPdot, nullptr);
@@ -479,13 +608,13 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
         for (long long k = k0; k < k0 + 5 && k <= maxiter; k++) {
             if (done_now && *(volatile int*)(c->h_cycle_done + kDoneNow)) tail = true;
             if (tail) break;
-            hipLaunchKernelGGL((cr_control_update_kernel<MODE>), dim3(g), dim3(kBlock), 0, s, st, v,
+            hipLaunchKernelGGL(control, dim3(g), dim3(kBlock), 0, s, st, v,
                                res0, res1, pdot_ref, rsdot, c->part(kPartRes0), c->part(kPartRes1),
                                c->hist.get(), lazy, done_now);
             ncdot = ops.applyC(c, csrc, v.Cres, done);
             // the control kernel of iteration k wrote the residual-norm partials of parity (k+1)&1
             pub.publish(kPartCdot, ncdot, 0, ((k + 1) & 1) ? kPartRes1 : kPartRes0, g, 1);
-            hipLaunchKernelGGL((cr_direction_kernel<MODE, false>), dim3(g), dim3(kBlock), 0, s, st, v,
+            hipLaunchKernelGGL(direction, dim3(g), dim3(kBlock), 0, s, st, v,
                                pub.ref(kPartCdot, ncdot), c->part(kPartPdot));
             if (MODE == kModePcrSmw) diag_apply_dev(c, v.Cstep, v.pCstep, kPartPdot, done);
             if (MODE != kModePlain && (k + 1) % 5 == 0) {

@@ -201,12 +201,63 @@ struct PartRef {
     int stride;
 };
 
+// A thread's partials are i = threadIdx.x, threadIdx.x + kBlock, ...: at most kPartialsPerThread of them, since no producer
+// runs more than kMaxPartials workgroups.  Taken one by one each load waits for the one before (a round trip to L2 per
+// partial), so the reduction is split: load_partials issues all of a thread's loads at once, from indices clamped to the
+// last partial so that they need no predicate (part.p[0] is read even when count == 0); fold_partials then applies Op in ascending
+// i to the partials below count, the order of the plain loop.  A kernel may issue the loads long before it folds them.
+constexpr int kPartialsPerThread = kMaxPartials / kBlock;
+
+__device__ __forceinline__ void load_partials(PartRef part, double (&v)[kPartialsPerThread]) {
+    const int last = max(part.count - 1, 0);
+#pragma unroll
+    for (int j = 0; j < kPartialsPerThread; j++)
+        v[j] = part.p[(size_t)min((int)threadIdx.x + j * kBlock, last) * part.stride];
+}
+template <class Op>
+__device__ __forceinline__ double fold_partials(PartRef part, const double (&v)[kPartialsPerThread]) {
+    double r = Op::identity();
+#pragma unroll
+    for (int j = 0; j < kPartialsPerThread; j++)
+        if ((int)threadIdx.x + j * kBlock < part.count) r = Op::apply(r, v[j]);
+    for (int i = threadIdx.x + kMaxPartials; i < part.count; i += kBlock)     // (no caller has that many)
+        r = Op::apply(r, part.p[(size_t)i * part.stride]);
+    return r;
+}
+
 template <class Op>
 __device__ __forceinline__ double reduce_partials(PartRef part, double* scratch) {
-    double v = Op::identity();
-    for (int i = threadIdx.x; i < part.count; i += kBlock)
-        v = Op::apply(v, part.p[(size_t)i * part.stride]);
-    return block_reduce<Op>(v, scratch);
+    double v[kPartialsPerThread];
+    load_partials(part, v);
+    return block_reduce<Op>(fold_partials<Op>(part, v), scratch);
+}
+
+// Two reductions at once: block_reduce of va under OpA and of vb under OpB, each through its own unchanged tree and its own
+// scratch array, behind one pair of barriers.
+template <class OpA, class OpB>
+__device__ __forceinline__ void block_reduce2(double& va, double& vb, double* scratch_a, double* scratch_b) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    va = wave_reduce<OpA>(va);
+    vb = wave_reduce<OpB>(vb);
+    __syncthreads();  // the scratch arrays may still be read by a previous call
+    if (lane == 0) { scratch_a[wave] = va; scratch_b[wave] = vb; }
+    __syncthreads();
+    double ra = scratch_a[0], rb = scratch_b[0];
+#pragma unroll
+    for (int w = 1; w < kBlock / 64; w++) { ra = OpA::apply(ra, scratch_a[w]); rb = OpB::apply(rb, scratch_b[w]); }
+    va = ra;
+    vb = rb;
+}
+// reduce_partials of two PartRefs: both sets of loads in flight together, each value through its own strided-then-tree order
+template <class OpA, class OpB>
+__device__ __forceinline__ void reduce_partials2(PartRef a, PartRef b, double* scratch_a, double* scratch_b, double& ra,
+                                                 double& rb) {
+    double va[kPartialsPerThread], vb[kPartialsPerThread];
+    load_partials(a, va);
+    load_partials(b, vb);
+    ra = fold_partials<OpA>(a, va);
+    rb = fold_partials<OpB>(b, vb);
+    block_reduce2<OpA, OpB>(ra, rb, scratch_a, scratch_b);
 }
 
 }  // namespace ipxk
