@@ -811,6 +811,77 @@ int ipxk_ipm_solve(ipxk_context* ctx, const double* b, const double* c, const do
                    ipxint* basis_out, ipxint* status_out, ipxk_interrupt_fn interrupt,
                    void* interrupt_user);
 
+/* ---- user model: an LP as the user states it, presolved on the device (src/user_model.cc, src/presolver.cc) ----
+ *   min obj'x   s.t.  A x {=,<,>} rhs,  lb <= x <= ub          (A: num_constr x num_var, CSC; bounds may be infinite)
+ * ipxk_lp_create is UserModel::Load + Presolver::PresolveModel into a context the lp owns:
+ *   - validation as UserModel::CopyInput, CheckVectors and CheckMatrix (src/user_model.cc:217-303): dimensions
+ *     (num_constr >= 0, num_var > 0) and NULL arguments, then the reference's checks -1 rhs finite, -2 obj finite,
+ *     -3 bounds finite or the correct infinity with lb <= ub, -4 constr_type one of "=<>", -5 Ap[0] == 0 and monotone,
+ *     -6 values finite, -7 row indices in range, -8 no row index twice in a column (sorted or not).  A failure returns
+ *     IPXK_E_ARGUMENT and ipxk_last_error() reads "... check <number> ... index <i>": the check the reference would
+ *     have failed first, and the first index that fails it (of rhs / obj / the bounds / constr_type / Ap; the position in
+ *     Ax / Ai for -6, -7, -8; for -8 the position of the second occurrence).  The checks run on the device; the first
+ *     index is a minimum over block partials.
+ *   - SparseMatrix::LoadFromArrays (src/sparse_matrix.cc:49-69), the end of CopyInput: explicit zeros are dropped and
+ *     every column is sorted by row index, so ipxk_lp_info::nnz may be below Ap[num_var].
+ *   - ComputeUserModelAttributes (src/presolver.cc:118-133), LoadPrimal (:135-180) or LoadDual (:182-264) --
+ *     dualize < 0: when num_constr > 2 * num_var (:33-34) -- and ScaleModel (:266-292) with ipxk_equilibrate's kernels
+ *     when scale >= 1.  All of it is sign flips, copies and powers of two: the solver form is the reference's bit for bit.
+ *   - the context from the resident matrix as ipxk_create builds it (layouts, dense columns, renumbering).
+ * Between the upload of the arguments and the downloads of the getters only scalars, counts and flag blocks cross
+ * to the host -- and what the construction of any context brings there: the column pointers, the histogram of the
+ * column counts and, below 2^16 entries, the entries for the host layout builders.  The context (ipxk_lp_context)
+ * is owned by the lp and unpartitioned; every ipxk_* call works on it.
+ * Out of scope: Presolver::PresolveIPMStartingPoint (a caller who has a starting point loads it in solver form with
+ * ipxk_ipm_load_starting_point on the lp's context and sets use_resident_point), basic solutions, PostsolveBasis and
+ * crossover, and partitioned contexts (after ipxk_comm_init* on the lp's context ipxk_lp_solve returns what
+ * ipxk_ipm_solve returns on a partitioned context). */
+typedef struct ipxk_lp ipxk_lp;
+typedef struct ipxk_lp_params {
+    ipxint dualize;            /* -1: num_constr > 2 * num_var, 0: never, 1: always (ipx_parameters::dualize) */
+    ipxint scale;              /* 0: none, >= 1: EquilibrateMatrix (ipx_parameters::scale, :271-272) */
+    int device;
+} ipxk_lp_params;              /* NULL: -1, 1, 0 */
+typedef struct ipxk_lp_info {
+    ipxint m, n, nnz;          /* solver form; nnz of the n structural columns */
+    ipxint dualized, num_boxed, num_flipped, num_free_var, num_eqconstr;
+    ipxint scale_rounds;       /* as ipxk_equilibrate's *rounds (-1 also with scale == 0) */
+    ipxint num_dense_cols;
+    double seconds;
+} ipxk_lp_info;
+int ipxk_lp_create(ipxint num_constr, ipxint num_var, const ipxint* Ap, const ipxint* Ai,
+                   const double* Ax, const double* rhs, const char* constr_type,
+                   const double* obj, const double* lb, const double* ub,
+                   const ipxk_lp_params* params, ipxk_lp_info* info, ipxk_lp** out);
+void ipxk_lp_destroy(ipxk_lp* lp);
+ipxk_context* ipxk_lp_context(ipxk_lp* lp);
+/* The solver form (host arrays): the n structural columns of AI (Ap[n+1], Ai, Ax[nnz]), b[m], c, lb, ub [n+m],
+ * colscale[n], rowscale[m] (1.0 where the reference's scaling vectors are empty).  Any may be NULL. */
+int ipxk_lp_get_model(ipxk_lp* lp, ipxint* Ap, ipxint* Ai, double* Ax, double* b, double* c,
+                      double* lb, double* ub, double* colscale, double* rowscale);
+/* ipxk_ipm_solve on the lp's context with the resident b, c, lb, ub (no basis is returned). */
+int ipxk_lp_solve(ipxk_lp* lp, const ipxk_solve_params* params, ipxk_solve_info* info,
+                  ipxk_interrupt_fn interrupt, void* interrupt_user);
+/* Presolver::PostsolveInteriorPoint (src/presolver.cc:618-793) of the context's resident iterate, postprocessed or
+ * not: x, xl, xu, zl, zu [num_var], slack, y [num_constr]; any may be NULL.  A pure elementwise map with the
+ * reference's operations on the reference's operands (one IEEE operation per entry).  The outputs follow the
+ * context's pointer mode. */
+int ipxk_lp_postsolve(ipxk_lp* lp, double* x, double* xl, double* xu, double* slack, double* y,
+                      double* zl, double* zu);
+/* UserModel::EvaluateInteriorPoint (src/user_model.cc:99-171) of the postsolved resident iterate, with the norms of
+ * UserModel::ComputeNorms (:306-316).  Computed on the device; every sum and maximum is a fixed-order tree over
+ * block partials: two calls give the same bits.  ipxk_lp_get_residuals copies out the two residual vectors of the
+ * last evaluation, rb = rhs - slack - A x [num_constr] and rc = obj - zl + zu - A'y [num_var] (host arrays; either
+ * may be NULL). */
+typedef struct ipxk_lp_eval {
+    double abs_presidual, abs_dresidual, rel_presidual, rel_dresidual;
+    double pobjval, dobjval, rel_objgap, complementarity;
+    double normx, normy, normz;
+    double norm_obj, norm_rhs, norm_bounds;
+} ipxk_lp_eval;
+int ipxk_lp_evaluate(ipxk_lp* lp, ipxk_lp_eval* out);
+int ipxk_lp_get_residuals(ipxk_lp* lp, double* rb, double* rc);
+
 /* ---- multi-GPU: rows of AI partitioned over ranks, one RCCL all-reduce per
  *      NormalMatrix apply ---------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and broadcast by the launcher. */

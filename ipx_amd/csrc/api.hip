@@ -944,6 +944,77 @@ int ipxk_transpose(ipxint m, ipxint n, const ipxint* Ap, const ipxint* Ai, const
     });
 }
 
+// ---- user model (user_model.hip) ---------------------------------------------------------
+struct ipxk_lp { ipxk::Lp* p; };
+
+int ipxk_lp_create(ipxint num_constr, ipxint num_var, const ipxint* Ap, const ipxint* Ai, const double* Ax, const double* rhs,
+                   const char* constr_type, const double* obj, const double* lb, const double* ub, const ipxk_lp_params* params,
+                   ipxk_lp_info* info, ipxk_lp** out) {
+    if (out) *out = nullptr;
+    return guarded([&] {
+        IPXK_REQUIRE(out != nullptr, "out is NULL");
+        Lp* p = lp_create(num_constr, num_var, Ap, Ai, Ax, rhs, constr_type, obj, lb, ub, params, info);
+        *out = new ipxk_lp{p};
+    });
+}
+
+void ipxk_lp_destroy(ipxk_lp* lp) {
+    if (!lp) return;
+    lp_destroy(lp->p);
+    delete lp;
+}
+
+ipxk_context* ipxk_lp_context(ipxk_lp* lp) { return lp ? static_cast<ipxk_context*>(lp_context(lp->p)) : nullptr; }
+
+int ipxk_lp_get_model(ipxk_lp* lp, ipxint* Ap, ipxint* Ai, double* Ax, double* b, double* c, double* lb, double* ub, double* colscale,
+                      double* rowscale) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp, "NULL argument");
+        bind_device(lp_context(lp->p));
+        lp_get_model(lp->p, Ap, Ai, Ax, b, c, lb, ub, colscale, rowscale);
+    });
+}
+
+int ipxk_lp_solve(ipxk_lp* lp, const ipxk_solve_params* params, ipxk_solve_info* info, ipxk_interrupt_fn interrupt, void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp && params && info, "NULL argument");
+        bind_device(lp_context(lp->p));
+        lp_solve(lp->p, params, info, interrupt, interrupt_user);
+    });
+}
+
+int ipxk_lp_postsolve(ipxk_lp* lp, double* x, double* xl, double* xu, double* slack, double* y, double* zl, double* zu) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp, "NULL argument");
+        Context* c = lp_context(lp->p);
+        bind_device(c);
+        const double* src[7];
+        lp_postsolve_dev(lp->p, src);
+        int64_t num_constr = 0, num_var = 0;
+        lp_dims(lp->p, &num_constr, &num_var);
+        double* dst[7] = {x, xl, xu, slack, y, zl, zu};
+        for (int k = 0; k < 7; k++)
+            if (dst[k]) copy_out(c, dst[k], src[k], (size_t)(k == 3 || k == 4 ? num_constr : num_var) * sizeof(double));
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_lp_evaluate(ipxk_lp* lp, ipxk_lp_eval* out) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp && out, "NULL argument");
+        bind_device(lp_context(lp->p));
+        lp_evaluate(lp->p, out);
+    });
+}
+
+int ipxk_lp_get_residuals(ipxk_lp* lp, double* rb, double* rc) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp, "NULL argument");
+        bind_device(lp_context(lp->p));
+        lp_get_residuals(lp->p, rb, rc);
+    });
+}
+
 int ipxk_lu_factorize(ipxk_context* c, ipxint dim, const ipxint* Bbegin, const ipxint* Bend, const ipxint* Bi,
                       const double* Bx, double pivottol, int strict_abs_pivottol, ipxk_lu_info* info) {
     return guarded([&] {

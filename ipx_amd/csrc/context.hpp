@@ -186,6 +186,10 @@ struct Context {
 // ---- model.hip: the model on the device, its gather matrices, the dense-column classification ----
 void build_model(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax);
 void upload_plain_model(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax);
+// a model whose plain CSC is on the device already: adopt_plain_model completes the plain copy (host column pointers, row-wise
+// copy), build_model_resident builds everything else of the context (host arrays NULL: none to fall back on)
+void adopt_plain_model(Context* c);
+void build_model_resident(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax);
 void ensure_host_model(Context* c, bool rowwise);
 void fetch_columns(Context* c, const std::vector<ipxint>& cols, std::vector<ipxint>& Cp, std::vector<ipxint>& Ci, std::vector<double>& Cx);
 // partitioned contexts: dense-column classification of the whole matrix (comm_init); true if it changed
@@ -407,11 +411,30 @@ void nmatrix_invalidate(Context* c);
 // prepare returns false when N is not used for this model; apply: work = W_I .* u + N (W_N .* (N' u))
 bool nmatrix_prepare(Context* c, const double* W);
 void nmatrix_apply(Context* c, const double* WI, const double* u, double* work, const int* done);
-// ---- presolve.hip (stand-alone, no context) ----
+// ---- presolve.hip (the resident routine; stand-alone wrappers on host arrays, no context) ----
+template <class P>
+void equilibrate_resident(int64_t m, int64_t n, int64_t nz, const P* dAp, const int* dAi, double* dAx, double* cs, double* rs,
+                          ipxint* rounds, hipStream_t s);
 void equilibrate_device(int device, int64_t m, int64_t n, const ipxint* Ap, const ipxint* Ai, double* Ax,
                         double* colscale, double* rowscale, ipxint* rounds);
 void transpose_device(int device, int64_t m, int64_t n, const ipxint* Ap, const ipxint* Ai, const double* Ax,
                       ipxint* Tp, ipxint* Ti, double* Tx);
+
+// ---- user_model.hip: an LP in user form, presolved on the device into a context it owns ----
+struct Lp;
+Lp* lp_create(int64_t num_constr, int64_t num_var, const ipxint* Ap, const ipxint* Ai, const double* Ax, const double* rhs,
+              const char* constr_type, const double* obj, const double* lb, const double* ub, const ipxk_lp_params* prm,
+              ipxk_lp_info* info);
+void lp_destroy(Lp* lp);
+Context* lp_context(Lp* lp);
+void lp_get_model(Lp* lp, ipxint* Ap, ipxint* Ai, double* Ax, double* b, double* c, double* lb, double* ub, double* colscale,
+                  double* rowscale);
+void lp_solve(Lp* lp, const ipxk_solve_params* prm, ipxk_solve_info* info, ipxk_interrupt_fn interrupt, void* user);
+// the seven user-form vectors of the resident iterate, on the device: x, xl, xu [num_var], slack, y [num_constr], zl, zu [num_var]
+void lp_postsolve_dev(Lp* lp, const double* out[7]);
+void lp_dims(const Lp* lp, int64_t* num_constr, int64_t* num_var);
+void lp_evaluate(Lp* lp, ipxk_lp_eval* out);
+void lp_get_residuals(Lp* lp, double* rb, double* rc);
 
 // ---- comm.hip ----
 void comm_allreduce_sum(Context* c, double* buf, size_t count);

@@ -21,6 +21,8 @@ template <class K>
 void sort_pairs(Tmp& T, const K* kin, K* kout, const unsigned* vin, unsigned* vout, size_t n, int bits, hipStream_t s);
 void sort_keys(Tmp& T, u64* in, u64* out, size_t n, hipStream_t s);       // by all 64 bits
 void scan_int(Tmp& T, const int* in, int* out, size_t n, hipStream_t s);        // exclusive prefix sums
+void narrow_ints(int64_t len, const ipxint* in, int* out, hipStream_t s);       // out[p] = (int)in[p] (model.hip)
+void widen_ints(int64_t len, const int* in, ipxint* out, hipStream_t s);
 
 // scratch of the layout builders: kept for the two gather matrices of a model, released when the model is built
 struct LayoutScratch {

@@ -48,6 +48,29 @@ __global__ void max_len_kernel(int nrows, const int* __restrict__ ptr, int* out)
     best = wave_max(best);
     if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(out, best);
 }
+// hist[len] += 1 for every row (maxcnt: the largest len).  The rows of a sparse matrix share a handful of lengths, so those below
+// kHistLds are counted per workgroup in LDS first, not with one global atomic per row on those few addresses.
+constexpr int kHistLds = 256;
+__global__ __launch_bounds__(kBlock) void count_histogram_kernel(int nrows, const int* __restrict__ ptr, int maxcnt, int* hist) {
+    __shared__ int sh[kHistLds];
+    for (int k = threadIdx.x; k < kHistLds; k += kBlock) sh[k] = 0;
+    __syncthreads();
+    IPXK_GRID_STRIDE(r, nrows) {
+        const int len = ptr[r + 1] - ptr[r];
+        if (len < kHistLds) atomicAdd(sh + len, 1); else atomicAdd(hist + len, 1);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < kHistLds && k <= maxcnt; k += kBlock)
+        if (sh[k]) atomicAdd(hist + k, sh[k]);
+}
+// the rows of at least `len` entries, in no particular order (cap of them: the caller knows how many there are)
+__global__ void rows_at_least_kernel(int nrows, const int* __restrict__ ptr, int len, int cap, int* count, int* __restrict__ list) {
+    IPXK_GRID_STRIDE(r, nrows)
+        if (ptr[r + 1] - ptr[r] >= len) {
+            const int k = atomicAdd(count, 1);
+            if (k < cap) list[k] = (int)r;
+        }
+}
 // entries of a list of columns, one after the other (dense columns: precond.hip)
 __global__ void gather_columns_kernel(int k, const int* __restrict__ cols, const int* __restrict__ off, const int* __restrict__ Ap,
                                       const int* __restrict__ Ai, const double* __restrict__ Ax, ipxint* __restrict__ out_i, double* __restrict__ out_x) {
@@ -56,8 +79,16 @@ __global__ void gather_columns_kernel(int k, const int* __restrict__ cols, const
     const int j = cols[kk], p0 = Ap[j], len = Ap[j + 1] - p0, o = off[kk];
     for (int t = threadIdx.x; t < len; t += blockDim.x) { out_i[o + t] = Ai[p0 + t]; out_x[o + t] = Ax[p0 + t]; }
 }
-__global__ void widen_kernel(int64_t nz, const int* __restrict__ in, ipxint* __restrict__ out) { IPXK_GRID_STRIDE(p, nz) out[p] = in[p]; }
+__global__ void narrow_plain_kernel(int64_t len, const ipxint* __restrict__ in, int* __restrict__ out) { IPXK_GRID_STRIDE(p, len) out[p] = (int)in[p]; }
+__global__ void widen_kernel(int64_t len, const int* __restrict__ in, ipxint* __restrict__ out) { IPXK_GRID_STRIDE(p, len) out[p] = in[p]; }
 }  // namespace
+
+void narrow_ints(int64_t len, const ipxint* in, int* out, hipStream_t s) {
+    if (len > 0) hipLaunchKernelGGL(narrow_plain_kernel, dim3(gridn(len)), dim3(kBlock), 0, s, len, in, out);
+}
+void widen_ints(int64_t len, const int* in, ipxint* out, hipStream_t s) {
+    if (len > 0) hipLaunchKernelGGL(widen_kernel, dim3(gridn(len)), dim3(kBlock), 0, s, len, in, out);
+}
 
 // ---------------------------------------------------------------------------
 // the model on the device: CSC and the row-wise copy, 32-bit indices
@@ -131,10 +162,10 @@ void ensure_host_model(Context* c, bool rowwise) {
                      std::vector<ipxint>& hi, std::vector<double>& hx) {
         DevBuf<ipxint> wide(std::max(std::max(nz, nptr), (size_t)1));
         hp.resize(nptr); hi.resize(nz); hx.resize(nz);
-        hipLaunchKernelGGL(widen_kernel, dim3(gridn((int64_t)nptr)), dim3(kBlock), 0, s, (int64_t)nptr, ptr.get(), wide.get());
+        widen_ints((int64_t)nptr, ptr.get(), wide.get(), s);
         wide.download(hp.data(), nptr, s);
         if (nz) {
-            hipLaunchKernelGGL(widen_kernel, dim3(gridn((int64_t)nz)), dim3(kBlock), 0, s, (int64_t)nz, idx.get(), wide.get());
+            widen_ints((int64_t)nz, idx.get(), wide.get(), s);
             wide.download(hi.data(), nz, s);
             val.download(hx.data(), nz, s);
         }
@@ -214,16 +245,32 @@ static void dense_threshold(const std::vector<int64_t>& hist, int64_t ncols, int
     }
 }
 
+// The counts come from the device's column pointers: their maximum, a histogram (integer atomics: exact in any order) and, if
+// there are dense columns, the list of them (at most 1000; sorted on the host).  No host pass over the columns.
 static void find_dense_columns(Context* c) {
     const int64_t n = c->n, m = c->m;
+    hipStream_t s = c->stream;
     c->dense_cols.clear();
-    ipxint maxcnt = 0;
-    for (int64_t j = 0; j < n; j++) maxcnt = std::max(maxcnt, c->h_Ap[j + 1] - c->h_Ap[j]);
-    std::vector<int64_t> hist((size_t)maxcnt + 1, 0);
-    for (int64_t j = 0; j < n; j++) hist[(size_t)(c->h_Ap[j + 1] - c->h_Ap[j])]++;
+    LayoutScratch S;
+    const int maxcnt = n > 0 ? device_max_row_length(S, (int)n, c->pl_Ap.get(), s) : 0;
+    DevBuf<int> dhist((size_t)maxcnt + 1);
+    IPXK_HIP(hipMemsetAsync(dhist.get(), 0, ((size_t)maxcnt + 1) * sizeof(int), s));
+    if (n > 0) hipLaunchKernelGGL(count_histogram_kernel, dim3(grid_for(n, 1024)), dim3(kBlock), 0, s, (int)n, c->pl_Ap.get(), maxcnt, dhist.get());
+    std::vector<int> h32((size_t)maxcnt + 1);
+    dhist.download(h32.data(), h32.size(), s);
+    const std::vector<int64_t> hist(h32.begin(), h32.end());
     dense_threshold(hist, n, m, &c->num_dense, &c->nz_dense);
-    for (int64_t j = 0; j < n; j++)
-        if (c->h_Ap[j + 1] - c->h_Ap[j] >= c->nz_dense) c->dense_cols.push_back(j);
+    if (c->num_dense > 0) {
+        DevBuf<int> list((size_t)c->num_dense), count(1);
+        IPXK_HIP(hipMemsetAsync(count.get(), 0, sizeof(int), s));
+        hipLaunchKernelGGL(rows_at_least_kernel, dim3(gridn(n)), dim3(kBlock), 0, s, (int)n, c->pl_Ap.get(), (int)c->nz_dense, (int)c->num_dense,
+                           count.get(), list.get());
+        std::vector<int> cols((size_t)c->num_dense);
+        list.download(cols.data(), cols.size(), s);
+        std::sort(cols.begin(), cols.end());
+        c->dense_cols.assign(cols.begin(), cols.end());
+    }
+    IPXK_HIP(hipGetLastError());
 }
 
 // The same classification for the whole partitioned matrix, identical on every rank (comm_init).  Row partition: the
@@ -296,16 +343,55 @@ static double ms_since(std::chrono::steady_clock::time_point& t0) {
 // builders do not cover take the host builders on host copies of the entries -- of the caller's arrays for the CSC, a
 // download of the device's row-wise copy for the other gather matrix.
 void build_model(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax) {
-    const int64_t m = c->m, n = c->n;
     auto t0 = std::chrono::steady_clock::now();
     upload_plain_model(c, Ap, Ai, Ax);
-    const int64_t nz = c->nnz;
     c->create_ms[0] = ms_since(t0);
+    build_model_resident(c, Ap, Ai, Ax);
+}
+
+// The plain copy of a model that is on the device already (pl_Ap, pl_Ai, pl_Ax filled, m, n, nnz set: the user model of
+// user_model.hip, which scales the matrix there): the column pointers on the host and the row-wise copy.
+void adopt_plain_model(Context* c) {
+    const int64_t m = c->m, n = c->n, nz = c->nnz;
+    hipStream_t s = c->stream;
+    IPXK_REQUIRE(m < (int64_t(1) << 31) - 1 && n < (int64_t(1) << 31) - 1, "dimension exceeds 32-bit device indices");
+    IPXK_REQUIRE(nz >= 0 && nz < (int64_t(1) << 31) - kLongSeg, "nnz exceeds 32-bit device indices");
+    const size_t nz1 = (size_t)std::max<int64_t>(nz, 1);
+    DevBuf<ipxint> wide((size_t)n + 1);
+    c->h_Ap.resize((size_t)n + 1);
+    widen_ints(n + 1, c->pl_Ap.get(), wide.get(), s);
+    wide.download(c->h_Ap.data(), (size_t)n + 1, s);
+    c->pl_Ai.ensure(nz1); c->pl_Ax.ensure(nz1); c->pl_Tp.ensure((size_t)m + 1); c->pl_Ti.ensure(nz1); c->pl_Tx.ensure(nz1);
+    if (nz > 0) {
+        DevBuf<int> colof;
+        Tmp T;
+        device_transpose(T, colof, n, m, nz, c->pl_Ap.get(), c->pl_Ai.get(), c->pl_Ax.get(), c->pl_Tp.get(), c->pl_Ti.get(), c->pl_Tx.get(), s);
+    } else {
+        IPXK_HIP(hipMemsetAsync(c->pl_Tp.get(), 0, ((size_t)m + 1) * sizeof(int), s));
+        IPXK_HIP(hipStreamSynchronize(s));
+    }
+    IPXK_HIP(hipGetLastError());
+    c->have_plain = true;
+}
+
+// Everything of a context that follows the plain copy: the layouts of both gather matrices, the dense columns, the renumbering.
+// Ap, Ai, Ax: the caller's host arrays for the host builders, or all NULL -- then they work on a download of the plain copy.
+void build_model_resident(Context* c, const ipxint* Ap, const ipxint* Ai, const double* Ax) {
+    const int64_t m = c->m, n = c->n;
+    auto t0 = std::chrono::steady_clock::now();
+    const int64_t nz = c->nnz;
     LayoutScratch S;
     c->Acols.csr_ptr = c->pl_Ap.get(); c->Acols.csr_idx = c->pl_Ai.get(); c->Acols.csr_val = c->pl_Ax.get();
     c->Arows.csr_ptr = c->pl_Tp.get(); c->Arows.csr_idx = c->pl_Ti.get(); c->Arows.csr_val = c->pl_Tx.get();
-    if (!c->Acols.build_device(S, n, m, nz, c->pl_Ap.get(), c->pl_Ai.get(), c->pl_Ax.get(), c->stream))
-        c->Acols.build(n, m, Ap, Ai, Ax, c->stream);
+    if (!c->Acols.build_device(S, n, m, nz, c->pl_Ap.get(), c->pl_Ai.get(), c->pl_Ax.get(), c->stream)) {
+        if (Ap) {
+            c->Acols.build(n, m, Ap, Ai, Ax, c->stream);
+        } else {
+            ensure_host_model(c, false);
+            c->Acols.build(n, m, c->h_Ap.data(), c->h_Ai.data(), c->h_Ax.data(), c->stream);
+            c->h_Ai = std::vector<ipxint>(); c->h_Ax = std::vector<double>();
+        }
+    }
     c->create_ms[1] = ms_since(t0);
     if (!c->Arows.build_device(S, m, n, nz, c->pl_Tp.get(), c->pl_Ti.get(), c->pl_Tx.get(), c->stream)) {
         ensure_host_model(c, true);

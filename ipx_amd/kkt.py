@@ -38,6 +38,8 @@ EXPORTS = [
     "ipxk_iterate_dropping_residuals", "ipxk_ipm_set_crossover_start", "ipxk_iterate_drop_to_complementarity", "ipxk_ipm_solve",
     "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
     "ipxk_dev_download",
+    "ipxk_lp_create", "ipxk_lp_destroy", "ipxk_lp_context", "ipxk_lp_get_model", "ipxk_lp_solve", "ipxk_lp_postsolve", "ipxk_lp_evaluate",
+    "ipxk_lp_get_residuals",
 ]
 
 
@@ -108,6 +110,22 @@ class SolveInfo(C.Structure):
         ("pres_dropping", c_f64), ("dres_dropping", c_f64)]
 
 
+class LpParams(C.Structure):
+    _fields_ = [("dualize", c_i64), ("scale", c_i64), ("device", C.c_int)]
+
+
+class LpInfo(C.Structure):
+    _fields_ = [("m", c_i64), ("n", c_i64), ("nnz", c_i64), ("dualized", c_i64), ("num_boxed", c_i64), ("num_flipped", c_i64),
+                ("num_free_var", c_i64), ("num_eqconstr", c_i64), ("scale_rounds", c_i64), ("num_dense_cols", c_i64),
+                ("seconds", c_f64)]
+
+
+class LpEval(C.Structure):
+    _fields_ = [("abs_presidual", c_f64), ("abs_dresidual", c_f64), ("rel_presidual", c_f64), ("rel_dresidual", c_f64),
+                ("pobjval", c_f64), ("dobjval", c_f64), ("rel_objgap", c_f64), ("complementarity", c_f64), ("normx", c_f64),
+                ("normy", c_f64), ("normz", c_f64), ("norm_obj", c_f64), ("norm_rhs", c_f64), ("norm_bounds", c_f64)]
+
+
 class Times(C.Structure):
     _fields_ = [("cr", c_f64), ("op", c_f64), ("precond", c_f64), ("solve_B", c_f64),
                 ("solve_Bt", c_f64)]
@@ -139,6 +157,9 @@ def load_library():
         L.ipxk_lu_generation.restype = c_i64
         L.ipxk_split_inverse_refined.restype = c_i64
         L.ipxk_normal_apply_bytes.restype = c_i64
+        L.ipxk_lp_context.restype = C.c_void_p
+        L.ipxk_lp_context.argtypes = [C.c_void_p]
+        L.ipxk_lp_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -810,3 +831,83 @@ class KktContext:
         buf = (C.c_char * 128).from_buffer_copy(unique_id)
         fn = self.lib.ipxk_comm_init_columns if columns else self.lib.ipxk_comm_init
         self._check(fn(self.h, buf, C.c_int(rank), C.c_int(nranks)))
+
+
+class Lp:
+    """An LP in user form, min obj'x s.t. A x {=,<,>} rhs, lb <= x <= ub, presolved on the device (UserModel::Load +
+    Presolver::PresolveModel) into a context the object owns.
+
+    A: object with .nrow, .ncol, .p, .i, .x (int64 CSC, num_constr x num_var); constr_type: str or bytes of '=', '<', '>'.
+    dualize: -1 (when num_constr > 2 * num_var), 0 or 1; scale: 0 or 1.  info: the fields of ipxk_lp_info."""
+
+    PT_KEYS = ("x", "xl", "xu", "slack", "y", "zl", "zu")
+
+    def __init__(self, A, rhs, constr_type, obj, lb, ub, dualize=-1, scale=1, device=0):
+        self.lib = load_library()
+        self.num_constr, self.num_var = int(A.nrow), int(A.ncol)
+        ct = constr_type.encode() if isinstance(constr_type, str) else bytes(constr_type)
+        prm, info, h = LpParams(dualize, scale, device), LpInfo(), C.c_void_p()
+        rc = self.lib.ipxk_lp_create(c_i64(self.num_constr), c_i64(self.num_var), _ip(_I(A.p)), _ip(_I(A.i)), _fp(_F(A.x)),
+                                     _fp(_F(rhs)), C.c_char_p(ct), _fp(_F(obj)), _fp(_F(lb)), _fp(_F(ub)), C.byref(prm),
+                                     C.byref(info), C.byref(h))
+        if rc != 0:
+            raise KktError(rc, self.lib.ipxk_last_error().decode())
+        self.h = h
+        self.info = {name: getattr(info, name) for name, _ in LpInfo._fields_}
+        self.m, self.n, self.nnz = int(info.m), int(info.n), int(info.nnz)
+        # the owned context behind the methods of KktContext (a view: closing it does nothing)
+        ctx = self.context = KktContext.__new__(KktContext)
+        ctx.lib, ctx.m, ctx.n, ctx.device_mode, ctx._keep = self.lib, self.m, self.n, False, None
+        ctx.h = C.c_void_p(self.lib.ipxk_lp_context(self.h))
+        ctx.close = lambda: None
+
+    def _check(self, rc):
+        if rc != 0:
+            raise KktError(rc, self.lib.ipxk_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.context.h = None
+            self.lib.ipxk_lp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def model(self):
+        """The solver form: dict(Ap, Ai, Ax of the n structural columns, b, c, lb, ub, colscale, rowscale)."""
+        m, n = self.m, self.n
+        out = dict(Ap=np.zeros(n + 1, i64), Ai=np.zeros(self.nnz, i64), Ax=np.zeros(self.nnz, f64), b=np.zeros(m, f64),
+                   c=np.zeros(n + m, f64), lb=np.zeros(n + m, f64), ub=np.zeros(n + m, f64), colscale=np.zeros(n, f64),
+                   rowscale=np.zeros(m, f64))
+        self._check(self.lib.ipxk_lp_get_model(self.h, _ip(out["Ap"]), _ip(out["Ai"]), _fp(out["Ax"]), _fp(out["b"]),
+                                               _fp(out["c"]), _fp(out["lb"]), _fp(out["ub"]), _fp(out["colscale"]),
+                                               _fp(out["rowscale"])))
+        return out
+
+    def solve(self, kkt_tol=0.3, feasibility_tol=1e-6, optimality_tol=1e-8, ipm_maxiter=300, switchiter=-1,
+              precond_dense_cols=True, crossover_start=0.0, dependency_tol=1e-6, max_etas=100, use_resident_point=False,
+              interrupt=None):
+        """ipxk_ipm_solve on the presolved model; returns the fields of ipxk_solve_info."""
+        prm = SolveParams(kkt_tol, feasibility_tol, optimality_tol, crossover_start, dependency_tol, ipm_maxiter, switchiter,
+                          max_etas, 1 if precond_dense_cols else 0, 1 if use_resident_point else 0)
+        info = SolveInfo()
+        cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
+        self._check(self.lib.ipxk_lp_solve(self.h, C.byref(prm), C.byref(info), cb, None))
+        return {name: getattr(info, name) for name, _ in SolveInfo._fields_}
+
+    def interior_solution(self):
+        """Presolver::PostsolveInteriorPoint of the resident iterate: dict(x, xl, xu, slack, y, zl, zu)."""
+        out = {k: np.zeros(self.num_constr if k in ("slack", "y") else self.num_var, f64) for k in self.PT_KEYS}
+        self._check(self.lib.ipxk_lp_postsolve(self.h, *[_fp(out[k]) for k in self.PT_KEYS]))
+        return out
+
+    def evaluate(self, residuals=False):
+        """UserModel::EvaluateInteriorPoint of the postsolved iterate; with residuals also rb and rc."""
+        ev = LpEval()
+        self._check(self.lib.ipxk_lp_evaluate(self.h, C.byref(ev)))
+        out = {name: getattr(ev, name) for name, _ in LpEval._fields_}
+        if residuals:
+            out["rb"], out["rc"] = np.zeros(self.num_constr, f64), np.zeros(self.num_var, f64)
+            self._check(self.lib.ipxk_lp_get_residuals(self.h, _fp(out["rb"]), _fp(out["rc"])))
+        return out
