@@ -319,6 +319,13 @@ constexpr int kNumSpmvLayouts = 8;
 inline constexpr const char* kSpmvLayoutNames[kNumSpmvLayouts] = {"phased", "sliced", "fused", "sorted", "sortedfused", "acc", "plain",
                                                                   "accfused"};
 
+// workgroups of the combine kernel on a product of nrows rows (launch_combine, spmv_kernels.hpp), hence its dot partials.
+// IPXK_COMBINE_GRID=<g> caps it (tests: a thread then owns several rows of a small matrix)
+inline int combine_grid_for(int64_t nrows) {
+    static const int cap = [] { const char* e = getenv("IPXK_COMBINE_GRID"); return e && atoi(e) > 0 ? std::min(atoi(e), 1024) : 1024; }();
+    return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (nrows + kBlock - 1) / kBlock));
+}
+
 struct GatherMatrix {
     int nrows = 0, ncols = 0;
     int64_t nnz = 0;
@@ -394,7 +401,7 @@ struct GatherMatrix {
     // which: 0 = the matrix, 1 = the masked value array (mask_values), 2 = the compacted copy (compact_tiles)
     SlicedView sliced_view(int which = 0) const;
     int fused_grid() const { return std::min(sliced.nrb, kMaxPartials); }
-    int combine_grid() const { return (int)std::min<int64_t>(1024, std::max<int64_t>(1, ((int64_t)nrows + kBlock - 1) / kBlock)); }
+    int combine_grid() const { return combine_grid_for(nrows); }
 
     GatherView view(bool masked = false) const;
     int grid() const { return G; }

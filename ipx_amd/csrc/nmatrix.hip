@@ -324,8 +324,7 @@ static void launch_tiles(const SlicedMatrix& P, int nrows, const double* x, cons
     if (V.R == kBlock * 4) hipLaunchKernelGGL((spmv_sliced_tile_kernel<Epi, 4, false, false>), grid, block, lds, s, V, x, epi, (double*)nullptr, done);
     else if (V.R == kBlock * 2) hipLaunchKernelGGL((spmv_sliced_tile_kernel<Epi, 2, false, false>), grid, block, lds, s, V, x, epi, (double*)nullptr, done);
     else hipLaunchKernelGGL((spmv_sliced_tile_kernel<Epi, 1, false, false>), grid, block, lds, s, V, x, epi, (double*)nullptr, done);
-    const int cg = (int)std::min<int64_t>(1024, std::max<int64_t>(1, ((int64_t)nrows + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(cg), dim3(kBlock), 0, s, V, epi, (double*)nullptr, done);
+    launch_combine(V, epi, (double*)nullptr, done, s);
 }
 
 template <class Epi>
@@ -336,8 +335,7 @@ static void launch_acc(const AccMatrix& A, const SlicedMatrix& P, int nrows, con
     launch_acc_tiles<Epi>(W, x, done, s);
     SlicedView V = view_of(P, nrows);
     V.nrows_pad = A.nrows_pad; V.partial = A.partial.get();
-    const int cg = (int)std::min<int64_t>(1024, std::max<int64_t>(1, ((int64_t)nrows + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(cg), dim3(kBlock), 0, s, V, epi, (double*)nullptr, done);
+    launch_combine(V, epi, (double*)nullptr, done, s);
 }
 
 // work = W_I .* u + N (W_N .* (N' u))        (AddNormalProduct on N, plus the slack columns of N: the identity part)

@@ -15,6 +15,8 @@
 // library is built with -ffp-contract=off), like the reference's x86 -O2 build.
 #pragma once
 
+#include <type_traits>
+
 #include "device_utils.hpp"
 #include "internal.hpp"
 
@@ -27,6 +29,26 @@ constexpr int kLdsDoubles = kChunkNnz + kChunkNnz / 32;
 __device__ __forceinline__ int lds_slot(int q) { return q + (q >> 5); }
 
 // ---- epilogues ---------------------------------------------------------------
+// init(r) starts a row sum, finish(r, acc, dot) ends it: both read what they need where they need it.  The combine
+// kernel wants a row's inputs in flight together with its partial sums, so an epilogue may add a two-phase form:
+// `In load(r)` reads the inputs of row r into a struct In, init(in) and finish(r, in, acc, dot) then only compute
+// and store -- the same expressions on the same values.  (No __restrict__ on the members: debug_single_pass passes
+// y == out.)  EpiRow picks that form where an epilogue has it and init(r) / finish(r, ...) where it has not.
+template <class Epi, class = void>
+struct EpiRow {
+    struct In {};
+    static __device__ __forceinline__ In load(const Epi&, long long) { return In{}; }
+    static __device__ __forceinline__ double init(const Epi& e, long long r, const In&) { return e.init((int)r); }
+    static __device__ __forceinline__ void finish(const Epi& e, long long r, const In&, double acc, double& dot) { e.finish((int)r, acc, dot); }
+};
+template <class Epi>
+struct EpiRow<Epi, std::void_t<typename Epi::In>> {
+    using In = typename Epi::In;
+    static __device__ __forceinline__ In load(const Epi& e, long long r) { return e.load(r); }
+    static __device__ __forceinline__ double init(const Epi& e, long long, const In& in) { return e.init(in); }
+    static __device__ __forceinline__ void finish(const Epi& e, long long r, const In& in, double acc, double& dot) { e.finish(r, in, acc, dot); }
+};
+
 struct ProdMul {
     static __device__ __forceinline__ double prod(double xg, double v) { return xg * v; }
 };
@@ -43,6 +65,12 @@ struct EpiScale : ProdMul {
     __device__ __forceinline__ void finish(int r, double acc, double&) const {
         out[r] = w ? acc * w[r] : acc;
     }
+    struct In { double w; };
+    __device__ __forceinline__ In load(long long r) const { return In{w ? w[r] : 0.0}; }
+    __device__ __forceinline__ double init(const In&) const { return 0.0; }
+    __device__ __forceinline__ void finish(long long r, const In& in, double acc, double&) const {
+        out[r] = w ? acc * in.w : acc;
+    }
 };
 // out[r] = y[r]*wI[r] + acc, dot += y[r]*out[r]   (wI == nullptr: no slack term)
 struct EpiNormalRows : ProdMul {
@@ -52,6 +80,13 @@ struct EpiNormalRows : ProdMul {
     __device__ __forceinline__ void finish(int r, double acc, double& dot) const {
         out[r] = acc;
         dot += y[r] * acc;
+    }
+    struct In { double y, wI; };
+    __device__ __forceinline__ In load(long long r) const { return In{y[r], wI ? wI[r] : 0.0}; }
+    __device__ __forceinline__ double init(const In& in) const { return wI ? in.y * in.wI : 0.0; }
+    __device__ __forceinline__ void finish(long long r, const In& in, double acc, double& dot) const {
+        out[r] = acc;
+        dot += in.y * acc;
     }
 };
 // out[r] = wI[r] + sum (v*w)*v
@@ -96,6 +131,15 @@ struct EpiSmwRows : ProdMul {
         const double l = d / diag[r];
         out[r] = l;
         dot += l * rhs[r];
+    }
+    struct In { double rhs, diag; };
+    __device__ __forceinline__ In load(long long r) const { return In{rhs[r], diag[r]}; }
+    __device__ __forceinline__ double init(const In&) const { return 0.0; }
+    __device__ __forceinline__ void finish(long long r, const In& in, double acc, double& dot) const {
+        const double d = in.rhs - acc;
+        const double l = d / in.diag;
+        out[r] = l;
+        dot += l * in.rhs;
     }
 };
 // out[j] = mask[j] * scale2[j] * (a[j] - acc)    (kkt_solver_basis.cc:101-120,178-188)
@@ -754,7 +798,9 @@ template <class Prod>
 __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M, const unsigned* __restrict__ tile_batch,
                                                                        const unsigned* __restrict__ bptr, const double* __restrict__ x,
                                                                        const int* done) {
-    if (done && *done) return;
+    // *done is fetched together with the first batch-table loads and tested when they are there, not in a round trip of its
+    // own in front of them (no `done`: a word of the table, which counts for nothing)
+    const int dn = *(done ? done : reinterpret_cast<const int*>(tile_batch));
     extern __shared__ double ac_sum[];
     constexpr int U = kAccPerThread, T = kAccThreads, NP = kAccParkPairs, PB = kAccParkPerBatch;
     static_assert(NP % PB == 0, "parked pairs per batch");
@@ -769,6 +815,7 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
     int wt = blockIdx.x, wq = 0, wnb = 0;
     unsigned wb0 = 0;
     if (wt < ntiles) { wb0 = tile_batch[wt]; wnb = (int)(tile_batch[wt + 1] - wb0); }
+    if (done && dn) return;
     auto next = [&]() -> Batch {
         Batch b{0u, 0u, -1};
         if (wt >= ntiles) return b;
@@ -997,26 +1044,133 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_fused_kernel(AccView M, 
     }
 }
 
-// out[r] = finish(init(r) (+|-) partial[0][r] (+|-) partial[1][r] ...), slices in ascending order
-template <class Epi>
+// out[r] = finish(init(r) (+|-) partial[0][r] (+|-) partial[1][r] ...), slices in ascending order.
+// EARLY: thread t of workgroup w owns rows r = w*kBlock + t + j*gridDim.x*kBlock as before and takes them in groups of R.
+// Nothing a group loads depends on anything else it loads, so all of it is issued before the first wait: *done, the long-row
+// flags (LONG: the matrix has long rows), the epilogue's inputs (EpiRow) and the R x NS partial sums -- about 16 loads per
+// thread, at rows clamped to the last one so that none needs a predicate; then the adds (ascending slice), the `done` test,
+// and the epilogue and the store row by row (ascending row: the order of the thread's dot contributions).  NS is the slice
+// count the geometry produced (1, 2, 4, 8: R = 2 at 8 slices, 4 otherwise); NS = 0 takes any count, R = 2 rows and the slices
+// in blocks of 8.  Every thread runs the first group, with or without a live row in it, so the `done` test is uniform; *done
+// is read with every group (it only changes between launches), which keeps that load among the group's, and without a
+// `done` the word read is the first of the partial sums and counts for nothing.  A launch that finds `done` set has loaded
+// what it does not use, from buffers that stay valid.  Two empty asm statements hold the order against the compiler: the
+// first keeps the loads above everything that waits (it would sink them to their uses, behind the test), the second has
+// every row's sum formed on every path, a dead row's too, before the first branch -- a way round the adds would carry the
+// group's loads, still counted as outstanding, into the next group, whose s_waitcnt then wait for them between its own loads.
+// !EARLY (IPXK_COMBINE_EARLY=0) is the form before: per row flag -> epilogue inputs -> one partial after the other, each
+// waited for, then the store.  Same operations on the same values either way.
+template <class Epi, int NS, bool EARLY, bool LONG>
 __global__ __launch_bounds__(kBlock) void spmv_sliced_combine_kernel(SlicedView M, Epi epi, double* dot_partials,
                                                                      const int* done) {
-    if (done && *done) return;
     __shared__ double red[kBlock / 64 + 1];
     double dotpart = 0.0;
-    for (int r = blockIdx.x * kBlock + threadIdx.x; r < M.nrows; r += gridDim.x * kBlock) {
-        if (M.row_long && M.row_long[r]) continue;       // finished by the long-row fix-up kernel
-        double acc = epi.init(r);
-        for (int s = 0; s < M.nslices; s++) {
-            const double t = __builtin_nontemporal_load(M.partial + (size_t)s * M.nrows_pad + r);
-            acc = Epi::kNeg ? acc - t : acc + t;
+    if constexpr (EARLY) {
+        using Row = EpiRow<Epi>;
+        constexpr int B = NS ? NS : 8, R = B == 8 ? 2 : 4;
+        const int ns = NS ? NS : M.nslices;
+        const long long stride = (long long)gridDim.x * kBlock, last = M.nrows - 1;
+        const int* const dword = done ? done : reinterpret_cast<const int*>(M.partial);
+        long long r0 = blockIdx.x * kBlock + threadIdx.x;
+        if (M.nrows <= 0) {
+            if (done && *done) return;
+        } else do {
+            long long rc[R];
+            unsigned char lg[R];
+            typename Row::In in[R];
+            double t[R][B];
+            const int dn = __hip_atomic_load(dword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                rc[j] = min(r0 + j * stride, last);
+                lg[j] = LONG ? M.row_long[rc[j]] : (unsigned char)0;
+            }
+#pragma unroll
+            for (int j = 0; j < R; j++) in[j] = Row::load(epi, rc[j]);
+#pragma unroll
+            for (int j = 0; j < R; j++)
+#pragma unroll
+                for (int u = 0; u < B; u++) t[j][u] = __builtin_nontemporal_load(M.partial + (size_t)min(u, ns - 1) * M.nrows_pad + rc[j]);
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);          // (nor may the instruction scheduler move a wait in between the loads)
+            double acc[R];
+            bool live[R];
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                live[j] = r0 + j * stride <= last && !lg[j];       // (a long row is finished by the long-row fix-up kernel)
+                acc[j] = live[j] ? Row::init(epi, rc[j], in[j]) : 0.0;
+            }
+            for (int s0 = 0; s0 < ns; s0 += B) {
+                if (s0 > 0) {                                       // NS == 0 and more than 8 slices: the next block of them
+#pragma unroll
+                    for (int j = 0; j < R; j++)
+#pragma unroll
+                        for (int u = 0; u < B; u++) t[j][u] = __builtin_nontemporal_load(M.partial + (size_t)min(s0 + u, ns - 1) * M.nrows_pad + rc[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < R; j++)
+#pragma unroll
+                    for (int u = 0; u < B; u++)
+                        if (NS || s0 + u < ns) acc[j] = Epi::kNeg ? acc[j] - t[j][u] : acc[j] + t[j][u];
+            }
+#pragma unroll
+            for (int j = 0; j < R; j++) asm volatile("" : "+v"(acc[j]));
+            if (done && dn) return;
+#pragma unroll
+            for (int j = 0; j < R; j++)
+                if (live[j]) Row::finish(epi, rc[j], in[j], acc[j], dotpart);
+            r0 += R * stride;
+        } while (r0 <= last);
+    } else {
+        if (done && *done) return;
+        for (int r = blockIdx.x * kBlock + threadIdx.x; r < M.nrows; r += gridDim.x * kBlock) {
+            if (M.row_long && M.row_long[r]) continue;       // finished by the long-row fix-up kernel
+            double acc = epi.init(r);
+            for (int s = 0; s < M.nslices; s++) {
+                const double t = __builtin_nontemporal_load(M.partial + (size_t)s * M.nrows_pad + r);
+                acc = Epi::kNeg ? acc - t : acc + t;
+            }
+            epi.finish(r, acc, dotpart);
         }
-        epi.finish(r, acc, dotpart);
     }
     if (dot_partials) {
         const double d = block_reduce<SumOp>(dotpart, red);
         if (threadIdx.x == 0) dot_partials[blockIdx.x] = d;
     }
+}
+
+// IPXK_COMBINE_EARLY=0: the combine kernel in the form it had before its loads were issued ahead of the first add (read
+// once per process; tests/test_gpu_combine_loads.py compares the two)
+inline bool combine_early() {
+    static const bool setting = [] { const char* e = getenv("IPXK_COMBINE_EARLY"); return !e || atoi(e) != 0; }();
+    return setting;
+}
+
+inline bool combine_generic() {
+    static const bool setting = [] { const char* e = getenv("IPXK_COMBINE_GENERIC"); return e && atoi(e) != 0; }();
+    return setting;
+}
+
+// The one launch of the combine kernel: on combine_grid_for(V.nrows) workgroups, the instantiation for V.nslices and for
+// whether the matrix has long rows.  IPXK_COMBINE_GENERIC=1 (tests) runs the form for any slice count whatever the count.
+template <class Epi, bool LONG>
+inline void launch_combine_ns(const SlicedView& V, const Epi& epi, double* dot_partials, const int* done, hipStream_t s) {
+    const dim3 grid(combine_grid_for(V.nrows)), block(kBlock);
+    switch (combine_generic() ? 0 : V.nslices) {
+        case 1: hipLaunchKernelGGL((spmv_sliced_combine_kernel<Epi, 1, true, LONG>), grid, block, 0, s, V, epi, dot_partials, done); break;
+        case 2: hipLaunchKernelGGL((spmv_sliced_combine_kernel<Epi, 2, true, LONG>), grid, block, 0, s, V, epi, dot_partials, done); break;
+        case 4: hipLaunchKernelGGL((spmv_sliced_combine_kernel<Epi, 4, true, LONG>), grid, block, 0, s, V, epi, dot_partials, done); break;
+        case 8: hipLaunchKernelGGL((spmv_sliced_combine_kernel<Epi, 8, true, LONG>), grid, block, 0, s, V, epi, dot_partials, done); break;
+        default: hipLaunchKernelGGL((spmv_sliced_combine_kernel<Epi, 0, true, LONG>), grid, block, 0, s, V, epi, dot_partials, done); break;
+    }
+}
+template <class Epi>
+inline void launch_combine(const SlicedView& V, const Epi& epi, double* dot_partials, const int* done, hipStream_t s) {
+    if (!combine_early())
+        hipLaunchKernelGGL((spmv_sliced_combine_kernel<Epi, 0, false, false>), dim3(combine_grid_for(V.nrows)), dim3(kBlock), 0, s, V, epi,
+                           dot_partials, done);
+    else if (V.row_long) launch_combine_ns<Epi, true>(V, epi, dot_partials, done, s);
+    else launch_combine_ns<Epi, false>(V, epi, dot_partials, done, s);
 }
 
 // The tile kernel of the accumulated tiles (every unmasked product, nmatrix.hip's N N' passes too): the persistent kernel on
@@ -1056,8 +1210,7 @@ inline void launch_spmv_sliced(const GatherMatrix& M, const double* x, const Epi
         if (V.R == kBlock * 4) hipLaunchKernelGGL((spmv_sliced_tile_kernel<Epi, 4, false, MASKED>), grid, block, lds, s, V, x, epi, dot_partials, done);
         else if (V.R == kBlock * 2) hipLaunchKernelGGL((spmv_sliced_tile_kernel<Epi, 2, false, MASKED>), grid, block, lds, s, V, x, epi, dot_partials, done);
         else hipLaunchKernelGGL((spmv_sliced_tile_kernel<Epi, 1, false, MASKED>), grid, block, lds, s, V, x, epi, dot_partials, done);
-        hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(M.combine_grid()), dim3(kBlock), 0, s, V, epi,
-                           dot_partials, done);
+        launch_combine(V, epi, dot_partials, done, s);
     }
 }
 
@@ -1101,7 +1254,7 @@ inline int launch_spmv(const GatherMatrix& M, const double* x, const Epi& epi, d
             launch_acc_tiles<Epi>(W, x, done, s);
             SlicedView C = M.sliced_view(0);
             C.nrows_pad = W.nrows_pad; C.partial = W.partial;
-            hipLaunchKernelGGL(spmv_sliced_combine_kernel<Epi>, dim3(M.combine_grid()), dim3(kBlock), 0, s, C, epi, dot_partials, done);
+            launch_combine(C, epi, dot_partials, done, s);
             break;
         }
         case SpmvLayout::sliced:
