@@ -409,6 +409,14 @@ static bool cr_early() {
     return setting;
 }
 
+// IPXK_CR_GRID=<g>: at most g workgroups for the vector kernels of the CR loop, so that a small system gives a thread
+// several elements and runs the later groups of kCrUnroll (tests).  Same operations per element; the partition of the
+// partial sums follows g, so results are bitwise comparable only between runs with the same g.
+static int cr_grid_cap() {
+    static const int setting = [] { const char* e = getenv("IPXK_CR_GRID"); return e ? atoi(e) : 0; }();
+    return setting;
+}
+
 static void ensure_comm_buffers(Context* c) {
     if (c->comm_scalars.size() < 64) c->comm_scalars.resize(64);
     if (c->comm_send.size() < (size_t)kNumPartialSlots) {
@@ -532,7 +540,7 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     if (c->hist.size() < (size_t)hist_cap + 1) c->hist.resize((size_t)hist_cap + 1);
     CrState* st = c->state.get();
     int* done = &st->done;
-    const int g = vec_grid(m);
+    const int g = cr_grid_cap() > 0 ? std::min(vec_grid(m), cr_grid_cap()) : vec_grid(m);
     const Pub pub(c);
     for (int i = 0; i <= kDoneNow; i++) c->h_cycle_done[i] = 0;   // previous solve is synchronized
     const bool multi = comm_active(c);

@@ -122,6 +122,10 @@ def rank_leg(outfile, rank, world, idfile):
     x, y, it, err, _ = ctx.kkt_diag_solve(slab.a, slab.b, 1e-30, RANK_MAXITER)
     out = {}
     put(out, "rank", np.concatenate([x, y]), it, err)
+    # cdot and pdot overflow: errflag 205 at k = 0, the non-finite scalars go through Pub::publish and the all-gather
+    x, y, it, err, _ = ctx.kkt_diag_solve(slab.a * 1e160, slab.b * 1e160, 1e-30, 200)
+    put(out, "rank205", np.concatenate([x, y]), it, err)
+    out["rank205.ny"] = np.array([y.size])
     np.savez(outfile, **out)
     ctx.close()
 

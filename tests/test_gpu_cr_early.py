@@ -6,7 +6,7 @@ loop.  The setting is read once per process: each order runs in a process of its
 
 Legs: every case of tests/cr_lazy_worker.py (3000 rows: PcrDiag, PcrSmw and plain CR on the golden fixtures, the 202 and
 203 exits, errflag 201 around a cycle boundary, no iteration, a nonzero start, the interrupt), its two-rank leg (the
-reduction helper with stride > 1), and tests/cr_early_worker.py (70001 rows: more than one partial per thread, a ragged last
+reduction helper with stride > 1; a 205 exit whose non-finite scalars cross the all-gather), and tests/cr_early_worker.py (70001 rows: more than one partial per thread, a ragged last
 workgroup) as it is, with IPXK_CR_LAZY=0 (the control kernel's loads of step and lhs) and with IPXK_SPMV_LAYOUT=plain
 (2048 cdot partials: the reduction helper's eight loads per thread).  The legs at 70001 rows all name their SpMV layout: left
 to itself a matrix of that size gets the fastest of several layouts by a timing on the spot, and with the layout the number
@@ -113,5 +113,6 @@ def test_row_partitioned_two_ranks(library, tmp_path):
     out = run_legs(LAZY_WORKER, lambda e, r: ["rank", str(tmp_path / ("early%s.rank%d.npz" % (e, r))), str(r), str(world),
                                               str(tmp_path / ("uid" + e))], 1, world, {"IPXK_COMM": "direct"}, "2-rank leg")
     for r in range(world):
-        all_equal(out["0"][r], out["1"][r], 2)
+        all_equal(out["0"][r], out["1"][r], 5)
         assert tuple(out["1"][r]["rank.it_err"]) == (7, 201) and np.any(out["1"][r]["rank.y"] != 0.0)
+        assert tuple(out["1"][r]["rank205.it_err"]) == (0, 205)      # overflow in cdot and pdot, on both ranks

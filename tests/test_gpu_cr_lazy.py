@@ -6,7 +6,9 @@ not close, on every way out of the loop.  The setting is read once per process: 
 its own (tests/cr_lazy_worker.py) and leaves an .npz behind.
 
 A 202 exit: the golden fixtures' indefinite weight vector gives one on dense_300 (at k = 1, after one solution
-update) and a 203 on diag_200 (at k = 0); both are in.  No fixture gives a 204 or a 205."""
+update) and a 203 on diag_200 (at k = 0); both are in.  The two-rank leg ends its second solve with a 205 at k = 0
+(overflow in cdot and pdot); the 204 exit and the 205 and 202 exits of the three modes on one rank are in
+tests/test_gpu_cr_exits.py, which runs both orders of the update too."""
 import os
 import subprocess
 import sys
@@ -120,13 +122,25 @@ def test_kkt_diag_solve(legs):
     assert err == 0 and it > 5 and np.isfinite(xy).all()
 
 
-def test_row_partitioned_two_ranks(tmp_path):
-    """every rank's x and y, bit for bit between the two orders; errflag 201 after 7 iterations on both ranks"""
-    from ipx_amd import kkt
+def test_row_partitioned_two_ranks(tmp_path, oracle):
+    """every rank's x and y, bit for bit between the two orders; errflag 201 after 7 iterations on both ranks, then
+    errflag 205 at k = 0 on both ranks for a right-hand side whose cdot and pdot overflow"""
+    from cr_lazy_worker import RANK_PROBLEM
+    from ipx_amd import kkt, synth
+    from oracle import pyoracle as po
     kkt.load_library()
+    m, n, seed = RANK_PROBLEM
+    A, st = synth.synthetic_lp(m, n, 8, seed), synth.synthetic_ipm_state(m, n, 1.0, seed)
+    ko = oracle.kkt_diag(po.Csc(m, n, A.p, A.i, A.x), precond_dense_cols=False, maxiter=200)
+    assert ko.factorize(st["xl"], st["xu"], st["zl"], st["zu"], st["mu"]) == 0
+    xo, yo, ito, erro, _ = ko.solve(st["a"] * 1e160, st["b"] * 1e160, 1e-30)
+    assert (ito, erro) == (0, 205) and not np.any(yo) and np.isfinite(xo).all()
     world = 2
     out = run_legs(lambda lazy, r: ["rank", str(tmp_path / ("lazy%s.rank%d.npz" % (lazy, r))), str(r), str(world),
                                     str(tmp_path / ("uid" + lazy))], world, {"IPXK_COMM": "direct"}, "2-rank leg")
     for r in range(world):
         xy, it, err, _ = same(out["0"][r], out["1"][r], "rank", hist=False)
         assert (it, err) == (7, 201) and np.any(xy != 0.0)
+        xy, it, err, _ = same(out["0"][r], out["1"][r], "rank205", hist=False)
+        ny = int(out["1"][r]["rank205.ny"][0])
+        assert (it, err) == (0, 205) and not np.any(xy[-ny:]) and np.isfinite(xy[:-ny]).all()      # y zero, x finite
