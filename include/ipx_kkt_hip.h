@@ -979,7 +979,8 @@ ipxint ipxk_split_inverse_refined(const ipxk_context* ctx);
  * sorted.built, nslices, nsub, nrb, RB, nrows_pad, max_sub, slice_elems, fused,
  * nnz, P, G, RT*1e6 + Q*1e3, use_acc, acc.built, nslices, nrb, RB, nrows_pad,
  * slice_elems, # batches, # entries that waited for a later batch, use_acc_fused,
- * accf.built, nrb, RB, # batches, use_plain}.  use_sorted, use_sorted_fused, use_acc,
+ * accf.built, nrb, RB, # batches, use_plain, # steps of the accumulated tiles (runs
+ * of batches the persistent kernel takes as one pipeline step)}.  use_sorted, use_sorted_fused, use_acc,
  * use_acc_fused and use_plain say whether that is the layout of ipxk_spmv_layout (at
  * most one of them is 1); use_sliced whether the sliced or fused tiles are built, which
  * masked products (the basis path) use whatever the layout. */
@@ -991,7 +992,9 @@ int ipxk_layout_info(const ipxk_context* ctx, int which, ipxint info[40],
  * sparse_matrix.cc:120-151) as the device holds it: ptr (i32), idx (i32), val
  * (f64); 11 acc tile_batch (u32), 12 acc bptr (u32), 13 acc pack (u32), 14 acc
  * val (f64); 15-19 the fused accumulated tiles: tile_batch, bptr, pack (u32), val
- * (f64), xmin (i32); 20 xmin of the fused sorted tiles (i32).  Copies min(cap, size)
+ * (f64), xmin (i32); 20 xmin of the fused sorted tiles (i32); 21 acc
+ * tile_step (u32, first step of each tile), 22 acc step records (4 x u32 each: first
+ * entry and three cuts; one more than there are steps).  Copies min(cap, size)
  * bytes into out; *nbytes = the array's size. */
 int ipxk_layout_array(ipxk_context* ctx, int which, int array, void* out,
                       ipxint cap, ipxint* nbytes);

@@ -1265,7 +1265,7 @@ int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[40], double c
         info[24] = L == SpmvLayout::acc; info[25] = M.acc.built; info[26] = M.acc.nslices; info[27] = M.acc.nrb; info[28] = M.acc.RB;
         info[29] = M.acc.nrows_pad; info[30] = M.acc.slice_elems; info[31] = M.acc.nbatches; info[32] = M.acc.deferred;
         info[33] = L == SpmvLayout::accfused; info[34] = M.accf.built; info[35] = M.accf.nrb; info[36] = M.accf.RB; info[37] = M.accf.nbatches;
-        info[38] = L == SpmvLayout::plain;
+        info[38] = L == SpmvLayout::plain; info[39] = M.acc.nsteps;
         if (create_ms) for (int i = 0; i < 4; i++) create_ms[i] = c->create_ms[i];
     });
 }
@@ -1303,6 +1303,8 @@ int ipxk_layout_array(ipxk_context* c, int which, int array, void* out, ipxint c
             case 18: src = M.accf.val.get(); bytes = M.accf.built ? nz * 8 : 0; break;
             case 19: src = M.accf.xmin.get(); bytes = M.accf.built ? (size_t)M.accf.nrb * 4 : 0; break;
             case 20: src = M.sorted.xmin.get(); bytes = M.sorted.built && M.sorted.fused ? (size_t)M.sorted.nrb * 4 : 0; break;
+            case 21: src = M.acc.tile_step.get(); bytes = M.acc.built ? ((size_t)M.acc.nrb * M.acc.nslices + 1) * 4 : 0; break;
+            case 22: src = M.acc.steps.get(); bytes = M.acc.built ? ((size_t)M.acc.nsteps + 1) * 16 : 0; break;
             default: IPXK_REQUIRE(false, "unknown array");
         }
         if (M.nlong > 0 && (array < 8 || array > 10)) bytes = 0;       // long rows: the tiles hold fewer entries than nnz; not inspected

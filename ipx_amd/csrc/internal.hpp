@@ -280,11 +280,20 @@ struct SortedMatrix {
 //   * an entry is one 32-bit word (row in block << 18 | index - first index of the slice) + its value; batch q of
 //     tile t is entries [bptr[tb[t] + q], bptr[tb[t] + q + 1]);
 //   * partial vectors and the combine kernel are the sliced layout's (folding the partials into the last workgroup of
-//     a row block to finish measured SLOWER than the combine launch: 109-145 against 95-101 us per pass).
+//     a row block to finish measured SLOWER than the combine launch: 109-145 against 95-101 us per pass);
+//   * the persistent kernel walks STEPS, not batches: a step is a run of consecutive batches of one tile that is streamed
+//     and gathered as one batch and whose adds run batch after batch with a barrier in between.  Per tile, left to right,
+//     a step takes batches while their total is at most kAccBatch entries and it holds at most kAccStepBatches of them
+//     (so a full batch stays alone, and a tile's short tail batches share one turn of the pipeline).  Step i of tile t is
+//     record tile_step[t] + i of `steps`: {first entry, cut 1, cut 2, cut 3}; its end is the next record's first entry
+//     (the last record is a sentinel at nnz), unused cuts equal the end.  A tile without entries has no record.
+//     acc_build_steps (layout_device.hip) derives the table from tile_batch / bptr for both builders;
+//     IPXK_ACC_STEPS=0 makes every batch a step of its own.
 constexpr int kAccThreads = 512;
 constexpr int kAccPerThread = 4;
 constexpr int kAccBatch = kAccThreads * kAccPerThread;     // 2048 entries between two barriers
 constexpr int kAccMaxRows = 16384;                         // 128 KB of row sums; 14 bits of row in the entry word
+constexpr int kAccStepBatches = 4;                         // batches a step of the persistent kernel holds at most
 //   * FUSED form (one slice = all of x, for matrices whose gathers have locality; round 4): a tile is a row block of RB rows
 //     (as many as give every CU two tiles), the gathered index is stored relative to the tile's smallest one (`xmin`; the
 //     tile's window of x must span less than 2^18 entries), the row sums start from the epilogue's initial value and the
@@ -296,6 +305,8 @@ struct AccView {
     const int* xmin;                   // FUSED: [nrb] smallest gathered index of the tile; else nullptr
     const unsigned* tile_batch;        // [nrb*nslices + 1] first batch of each tile
     const unsigned* bptr;              // [# batches + 1] first entry of each batch
+    const unsigned* tile_step;         // [# tiles + 1] first step of each tile
+    const uint4* steps;                // [# steps + 1] {first entry, three cuts} of each step
     const unsigned* pack;
     const double* val;
     double* partial;                   // [nslices][nrows_pad]
@@ -303,8 +314,9 @@ struct AccView {
 struct AccMatrix {
     bool built = false;
     int nslices = 0, nrb = 0, RB = 0, nrows_pad = 0, slice_elems = 0;
-    int64_t nbatches = 0, deferred = 0;
-    DevBuf<unsigned> tile_batch, bptr, pack;
+    int64_t nbatches = 0, deferred = 0, nsteps = 0;
+    DevBuf<unsigned> tile_batch, bptr, pack, tile_step;
+    DevBuf<uint4> steps;
     DevBuf<double> val, partial;
     bool fused = false;                // the FUSED form
     DevBuf<int> xmin;

@@ -239,6 +239,36 @@ __global__ void acc_bptr_kernel(int ntiles, const unsigned* __restrict__ tile_pt
     if (tile == ntiles - 1 && threadIdx.x == 0) bptr[tile_batch[ntiles]] = nz;
 }
 
+// The steps of one tile (internal.hpp): left to right over its batches, a step takes batches while their total is at most
+// kAccBatch entries and it holds at most maxb of them.  emit(i, b, k): step i of the tile is batches [b, b + k).  Returns the
+// number of steps.  The one statement of the rule: the count and the fill below both walk with it.
+template <class Emit>
+__device__ __forceinline__ unsigned acc_tile_steps(const unsigned* __restrict__ bptr, unsigned b0, unsigned b1, unsigned maxb, Emit emit) {
+    unsigned ns = 0;
+    for (unsigned b = b0; b < b1; ns++) {
+        unsigned k = 1;
+        while (k < maxb && b + k < b1 && bptr[b + k + 1] - bptr[b] <= (unsigned)kAccBatch) k++;
+        emit(ns, b, k);
+        b += k;
+    }
+    return ns;
+}
+__global__ void acc_step_count_kernel(int ntiles, const unsigned* __restrict__ tile_batch, const unsigned* __restrict__ bptr, unsigned maxb,
+                                      unsigned* __restrict__ nstep) {
+    IPXK_GRID_STRIDE(t, ntiles) nstep[t] = acc_tile_steps(bptr, tile_batch[t], tile_batch[t + 1], maxb, [](unsigned, unsigned, unsigned) {});
+}
+__global__ void acc_step_fill_kernel(int ntiles, const unsigned* __restrict__ tile_batch, const unsigned* __restrict__ bptr, unsigned maxb,
+                                     const unsigned* __restrict__ tile_step, unsigned nz, uint4* __restrict__ steps) {
+    IPXK_GRID_STRIDE(t, ntiles) {
+        const unsigned s0 = tile_step[t];
+        acc_tile_steps(bptr, tile_batch[t], tile_batch[t + 1], maxb, [&](unsigned i, unsigned b, unsigned k) {
+            const unsigned end = bptr[b + k];
+            steps[s0 + i] = make_uint4(bptr[b], k > 1 ? bptr[b + 1] : end, k > 2 ? bptr[b + 2] : end, k > 3 ? bptr[b + 3] : end);
+        });
+        if (t == ntiles - 1) steps[tile_step[ntiles]] = make_uint4(nz, nz, nz, nz);
+    }
+}
+
 // ---- one-slice (FUSED) forms: a tile is a row block, offsets are relative to the tile's smallest gathered index ----
 // smallest / largest gathered index per tile, the rows' count bytes (optional), a flag for rows with descending / repeated indices
 __global__ void tile_window_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, int* __restrict__ lo,
@@ -550,11 +580,32 @@ int acc_rows_per_block(int nrows, int ns) {
     return RB;
 }
 
+// The step table of the persistent tile kernel from A.tile_batch / A.bptr (both on the device), for the host and the device
+// builder alike: fills A.tile_step / steps / nsteps.  IPXK_ACC_STEPS=0: every batch is a step (the schedule without steps;
+// A/B runs and the tests' reference).  Synchronizes (the read-back of the step count; the temporary).
+void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, hipStream_t s) {
+    static const bool merge = !(getenv("IPXK_ACC_STEPS") && getenv("IPXK_ACC_STEPS")[0] == '0');
+    static_assert(kAccStepBatches == 4, "a step record holds three cuts");
+    const unsigned maxb = merge ? kAccStepBatches : 1;
+    DevBuf<unsigned> nstep((size_t)ntiles + 1);
+    hipLaunchKernelGGL(acc_step_count_kernel, dim3(gridn(ntiles)), dim3(kBlock), 0, s, (int)ntiles, A.tile_batch.get(), A.bptr.get(), maxb, nstep.get());
+    A.tile_step.ensure((size_t)ntiles + 1);
+    scan_u32((int)ntiles, nstep.get(), A.tile_step.get(), s);
+    unsigned total = 0;
+    IPXK_HIP(hipMemcpyAsync(&total, A.tile_step.get() + ntiles, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    IPXK_HIP(hipStreamSynchronize(s));
+    A.steps.ensure((size_t)total + 1);
+    hipLaunchKernelGGL(acc_step_fill_kernel, dim3(gridn(ntiles)), dim3(kBlock), 0, s, (int)ntiles, A.tile_batch.get(), A.bptr.get(), maxb,
+                       A.tile_step.get(), (unsigned)nnz, A.steps.get());
+    IPXK_HIP(hipStreamSynchronize(s));          // nstep goes out of scope
+    A.nsteps = total;
+}
+
 // The tail both accumulated forms share.  On entry S.q2 / S.v2 hold the entries' keys (tile << 18 | offset) and storage positions
 // in sorted order, T.rowof the row of every entry in storage order, T.tile_ptr the first sorted entry of each tile.  The entry
 // words, the batches of every tile (acc_batch_kernel), the scan of their counts, then batch pointers and the scatter to batch
-// order: fills out.tile_batch / bptr / pack / val, nbatches and deferred.  One synchronization (the read-back of the batch count);
-// the caller synchronizes once more before T goes out of scope.
+// order: fills out.tile_batch / bptr / pack / val, nbatches and deferred, then the step table (acc_build_steps).  Synchronizes for
+// the read-back of the batch count and in acc_build_steps; the caller synchronizes once more before T goes out of scope.
 struct AccTemps {
     DevBuf<int> rowof;
     DevBuf<unsigned> tile_ptr, nbatch, bstart;
@@ -583,6 +634,7 @@ static void acc_batches(LayoutScratch& S, AccMatrix& out, AccTemps& T, int64_t n
     hipLaunchKernelGGL(acc_scatter_kernel, dim3(gridn(nnz)), dim3(kBlock), 0, s, nnz, S.k2.get(), word, S.v2.get(), dval, out.pack.get(),
                        out.val.get());
     out.nbatches = nb_total; out.deferred = (int64_t)ndef;
+    acc_build_steps(out, ntiles, nnz, s);
 }
 
 // The prologue both fused forms share: smallest and largest gathered index of every tile of RB rows (lo, hi: nrb entries each; lo is

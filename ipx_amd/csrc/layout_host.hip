@@ -362,7 +362,7 @@ struct AccBatcher {
             batch++;
         }
     }
-    // the arrays every accumulated form has; tb: first batch of every tile, its last entry still to be set
+    // the arrays every accumulated form has, the step table from them; tb: first batch of every tile, its last entry still to be set
     void finish(AccMatrix& A, std::vector<unsigned>& tb, int64_t nnz, hipStream_t s) {
         tb.back() = (unsigned)bp.size();
         bp.push_back((unsigned)nnz);
@@ -371,6 +371,7 @@ struct AccBatcher {
         A.bptr.upload(bp, s);
         A.pack.upload(pk, s);
         A.val.upload(tv, s);
+        acc_build_steps(A, (int64_t)tb.size() - 1, nnz, s);
     }
 };
 }  // namespace

@@ -176,8 +176,8 @@ void GatherMatrix::select_layout(const std::function<bool(SpmvLayout)>& make, hi
         fprintf(stderr, " fullest-slice share %.2f -> %s\n", share, kSpmvLayoutNames[(int)layout]);
         const AccMatrix& a = layout == L::accfused ? accf : acc;
         if (a.built)
-            fprintf(stderr, "ipxk:   %d rows per tile, %lld batches, %.1f%% of the entries waited\n", a.RB, (long long)a.nbatches,
-                    100.0 * (double)a.deferred / (double)nnz);
+            fprintf(stderr, "ipxk:   %d rows per tile, %lld steps / %lld batches, %.1f%% of the entries waited\n", a.RB, (long long)a.nsteps,
+                    (long long)a.nbatches, 100.0 * (double)a.deferred / (double)nnz);
     }
 }
 
@@ -275,6 +275,7 @@ static AccView view_of(const AccMatrix& A, int nrows) {
     V.nrows = nrows; V.nrows_pad = A.nrows_pad; V.nslices = A.nslices; V.nrb = A.nrb; V.RB = A.RB; V.slice_elems = A.slice_elems;
     V.xmin = A.xmin.get();
     V.tile_batch = A.tile_batch.get(); V.bptr = A.bptr.get(); V.pack = A.pack.get(); V.val = A.val.get(); V.partial = A.partial.get();
+    V.tile_step = A.tile_step.get(); V.steps = A.steps.get();
     return V;
 }
 AccView GatherMatrix::acc_view() const { return view_of(acc, nrows); }

@@ -784,7 +784,8 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, c
 
 // The PERSISTENT form of the tile kernel (launch_acc_tiles; IPXK_ACC_PERSIST=0 selects the kernel above).  The grid is a
 // multiple of nslices (acc_persist_grid); workgroup w takes tiles w, w + G, w + 2G, ..., all of slice w % nslices, and runs
-// the pipeline above over the concatenation of their batches, so the first stream loads and batch pointers of the next tile
+// the pipeline above over the concatenation of their STEPS (internal.hpp: a batch, or a tile's short tail batches taken as
+// one batch of the pipeline and added one after the other), so the first stream loads and step records of the next tile
 // are in flight while the current one finishes.  At a tile boundary each thread moves its row pairs (2 tid + 2 T j) from LDS
 // into registers and zeroes them in place between two barriers; the parked sums leave as 16-byte stores, kAccParkPerBatch
 // pairs after each of the next tile's batches (after that batch's stream loads, so that no s_waitcnt of the pipeline waits
@@ -793,14 +794,14 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, c
 constexpr int kAccParkPairs = kAccMaxRows / (2 * kAccThreads);       // 16 row pairs (64 VGPRs) per thread
 constexpr int kAccParkPerBatch = 2;
 template <class Prod>
-// (the batch tables come as __restrict__ arguments: the partial stores of the loop would otherwise keep the compiler from
-// reading them with scalar loads, and a vector load of a batch pointer waits vmcnt(0) -- for the whole pipeline)
-__global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M, const unsigned* __restrict__ tile_batch,
-                                                                       const unsigned* __restrict__ bptr, const double* __restrict__ x,
+// (the step tables come as __restrict__ arguments: the partial stores of the loop would otherwise keep the compiler from
+// reading them with scalar loads, and a vector load of a step record waits vmcnt(0) -- for the whole pipeline)
+__global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M, const unsigned* __restrict__ tile_step,
+                                                                       const uint4* __restrict__ steps, const double* __restrict__ x,
                                                                        const int* done) {
-    // *done is fetched together with the first batch-table loads and tested when they are there, not in a round trip of its
+    // *done is fetched together with the first step-table loads and tested when they are there, not in a round trip of its
     // own in front of them (no `done`: a word of the table, which counts for nothing)
-    const int dn = *(done ? done : reinterpret_cast<const int*>(tile_batch));
+    const int dn = *(done ? done : reinterpret_cast<const int*>(tile_step));
     extern __shared__ double ac_sum[];
     constexpr int U = kAccPerThread, T = kAccThreads, NP = kAccParkPairs, PB = kAccParkPerBatch;
     static_assert(NP % PB == 0, "parked pairs per batch");
@@ -809,26 +810,31 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
     const int s = blockIdx.x % M.nslices;                       // the same for every tile of the workgroup (G % nslices == 0)
     const double* __restrict__ xs = x + (size_t)s * M.slice_elems;
     double* const part = M.partial + (size_t)s * M.nrows_pad;
-    // walker over the workgroup's batches (wave-uniform: scalar loads); an empty tile yields one empty batch, so that its
-    // partial is written (zeros) like any other
-    struct Batch { unsigned e0, e1; int tile; };                // tile -1: past the workgroup's last tile
+    // walker over the workgroup's steps (wave-uniform: scalar loads; a record and the first word of the next one, the step's
+    // end); an empty tile has no record and yields one empty step, so that its partial is written (zeros) like any other.
+    // A step (internal.hpp) is entries [e0, e1) of one tile: streamed and gathered as one batch, added as the batches
+    // [e0, c1) [c1, c2) [c2, c3) [c3, e1) with a barrier in front of every non-empty one after the first.
+    struct Step { unsigned e0, e1, c1, c2, c3; int tile; };    // tile -1: past the workgroup's last tile
     int wt = blockIdx.x, wq = 0, wnb = 0;
     unsigned wb0 = 0;
-    if (wt < ntiles) { wb0 = tile_batch[wt]; wnb = (int)(tile_batch[wt + 1] - wb0); }
+    if (wt < ntiles) { wb0 = tile_step[wt]; wnb = (int)(tile_step[wt + 1] - wb0); }
     if (done && dn) return;
-    auto next = [&]() -> Batch {
-        Batch b{0u, 0u, -1};
+    auto next = [&]() -> Step {
+        Step b{0u, 0u, 0u, 0u, 0u, -1};
         if (wt >= ntiles) return b;
         b.tile = wt;
-        if (wnb > 0) { b.e0 = bptr[wb0 + wq]; b.e1 = bptr[wb0 + wq + 1]; }
+        if (wnb > 0) {
+            const uint4 r = steps[wb0 + wq];
+            b.e0 = r.x; b.c1 = r.y; b.c2 = r.z; b.c3 = r.w; b.e1 = steps[wb0 + wq + 1].x;
+        }
         if (++wq >= max(wnb, 1)) {
             wt += G; wq = 0;
-            if (wt < ntiles) { wb0 = tile_batch[wt]; wnb = (int)(tile_batch[wt + 1] - wb0); }
+            if (wt < ntiles) { wb0 = tile_step[wt]; wnb = (int)(tile_step[wt + 1] - wb0); }
         }
         return b;
     };
     constexpr int NE = 6;
-    Batch q[NE];                          // q[i] = batch k + i for the current batch k
+    Step q[NE];                           // q[i] = step k + i for the current step k
 #pragma unroll
     for (int i = 0; i < NE; i++) q[i] = next();
     unsigned pk[3][U];
@@ -847,7 +853,7 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
             vb[u] = __builtin_nontemporal_load(M.val + base + i);
         }
     };
-    auto gather = [&](double (&xgb)[U], const unsigned (&pkb)[U], const Batch& b) {
+    auto gather = [&](double (&xgb)[U], const unsigned (&pkb)[U], const Step& b) {
         const bool live = b.e1 > b.e0;
         const double* __restrict__ xb = live ? xs : x;
         const unsigned mask = live ? (1u << kSortedOffBits) - 1u : 0u;
@@ -902,12 +908,29 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
                     cur = q[0].tile;
                     __syncthreads();
                 }
+                // the step's first batch, then (a tile's short tail batches taken as one step) up to three more, each behind a
+                // barrier of its own: the same ds_add_f64 between the same barriers as one batch per step.  The cuts are
+                // scalars, the same in every wave; a step of one batch (c1 == e1) pays one scalar compare for the rest
+                const int n1 = (int)(q[0].c1 - q[0].e0);
 #pragma unroll
                 for (int u = 0; u < U; u++)
-                    if (u * T + tid < ne)
+                    if (u * T + tid < n1)
                         __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), Prod::prod(xg[d & 1][u], v[d % 3][u]), __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_WORKGROUP);
-                stream(pk[d % 3], v[d % 3], q[3].e0, q[3].e1);               // batch k + 3 into the buffer just emptied
+                if (n1 < ne) {
+                    int lo = n1, hi = (int)(q[0].c2 - q[0].e0), hi2 = (int)(q[0].c3 - q[0].e0);
+#pragma unroll 1
+                    for (int p = 1; p < kAccStepBatches && lo < ne; p++) {
+                        __syncthreads();
+#pragma unroll
+                        for (int u = 0; u < U; u++)
+                            if (u * T + tid >= lo && u * T + tid < hi)
+                                __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), Prod::prod(xg[d & 1][u], v[d % 3][u]),
+                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        lo = hi; hi = hi2; hi2 = ne;
+                    }
+                }
+                stream(pk[d % 3], v[d % 3], q[3].e0, q[3].e1);               // step k + 3 into the buffer just emptied
                 if (pleft > 0) store_parked();
 #pragma unroll
                 for (int i = 0; i + 1 < NE; i++) q[i] = q[i + 1];
@@ -1187,7 +1210,7 @@ inline void launch_acc_tiles(const AccView& W, const double* x, const int* done,
     }
     const size_t lds = (size_t)W.RB * sizeof(double);
     const int ntiles = W.nrb * W.nslices, G = acc_persist_grid(W.nslices);
-    if (G > 0) hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod>), dim3(std::min(G, ntiles)), dim3(kAccThreads), lds, s, W, W.tile_batch, W.bptr,
+    if (G > 0) hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod>), dim3(std::min(G, ntiles)), dim3(kAccThreads), lds, s, W, W.tile_step, W.steps,
                                   x, done);
     else hipLaunchKernelGGL((spmv_acc_tile_kernel<Prod>), dim3(ntiles), dim3(kAccThreads), lds, s, W, x, done);
 }
