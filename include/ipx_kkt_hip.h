@@ -980,11 +980,12 @@ ipxint ipxk_split_inverse_refined(const ipxk_context* ctx);
  * nnz, P, G, RT*1e6 + Q*1e3, use_acc, acc.built, nslices, nrb, RB, nrows_pad,
  * slice_elems, # batches, # entries that waited for a later batch, use_acc_fused,
  * accf.built, nrb, RB, # batches, use_plain, # steps of the accumulated tiles (runs
- * of batches the persistent kernel takes as one pipeline step)}.  use_sorted, use_sorted_fused, use_acc,
+ * of batches the persistent kernel takes as one pipeline step), # 16-byte units of
+ * their wide stream (0: not built, IPXK_ACC_WIDE=0); the rest of the 48 is 0}.  use_sorted, use_sorted_fused, use_acc,
  * use_acc_fused and use_plain say whether that is the layout of ipxk_spmv_layout (at
  * most one of them is 1); use_sliced whether the sliced or fused tiles are built, which
  * masked products (the basis path) use whatever the layout. */
-int ipxk_layout_info(const ipxk_context* ctx, int which, ipxint info[40],
+int ipxk_layout_info(const ipxk_context* ctx, int which, ipxint info[48],
                      double create_ms[4]);
 /* array: 0 sliced tile_ptr (u32), 1 sliced cnt (u8), 2 sliced idx (i32), 3
  * sliced val (f64), 4 sorted sub_ptr (u32), 5 sorted cnt (u8), 6 sorted pack
@@ -994,8 +995,15 @@ int ipxk_layout_info(const ipxk_context* ctx, int which, ipxint info[40],
  * val (f64); 15-19 the fused accumulated tiles: tile_batch, bptr, pack (u32), val
  * (f64), xmin (i32); 20 xmin of the fused sorted tiles (i32); 21 acc
  * tile_step (u32, first step of each tile), 22 acc step records (4 x u32 each: first
- * entry and three cuts; one more than there are steps).  Copies min(cap, size)
- * bytes into out; *nbytes = the array's size. */
+ * entry and three cuts; one more than there are steps); 23 the wide stream of the
+ * accumulated tiles (u32; units of 16 bytes: per step of ne entries and Tp =
+ * roundup64(ceil(ne / 4)) threads Tp units {entry words of positions t, Tp + t,
+ * 2 Tp + t, 3 Tp + t}, Tp units {values of the first two}, Tp units {values of the
+ * last two}, as bit patterns; positions >= ne are zero), 24 the first unit of each
+ * step in it (u32, one per step record; the last is the total).  23 and 24 are empty
+ * with IPXK_ACC_WIDE=0, which makes the persistent tile kernel read arrays 13 and 14
+ * as it did before there was a wide stream.  Copies min(cap, size) bytes into out;
+ * *nbytes = the array's size. */
 int ipxk_layout_array(ipxk_context* ctx, int which, int array, void* out,
                       ipxint cap, ipxint* nbytes);
 /* plain device allocation helpers so that callers without torch can hold

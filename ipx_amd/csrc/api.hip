@@ -1248,11 +1248,11 @@ int ipxk_split_inverse_stats(const ipxk_context* c, ipxint* probes, ipxint* reje
 ipxint ipxk_split_inverse_refined(const ipxk_context* c) { return c ? (ipxint)c->split_stats.inverse_refined : 0; }
 
 // Layout inspection (tests/test_gpu_layout.py: the device builders against the host builders, array by array).
-int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[40], double create_ms[4]) {
+int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[48], double create_ms[4]) {
     return guarded([&] {
         IPXK_REQUIRE(c && info && (which == 0 || which == 1), "bad argument");
         const GatherMatrix& M = which == 0 ? c->Acols : c->Arows;
-        for (int i = 0; i < 40; i++) info[i] = 0;
+        for (int i = 0; i < 48; i++) info[i] = 0;
         const SpmvLayout L = M.layout;
         info[0] = M.tile_base() != SpmvLayout::phased; info[1] = L == SpmvLayout::sorted; info[2] = L == SpmvLayout::sortedfused; info[3] = M.nlong;
         info[4] = M.sliced.built; info[5] = M.sliced.R; info[6] = M.sliced.nslices; info[7] = M.sliced.nrb;
@@ -1266,6 +1266,7 @@ int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[40], double c
         info[29] = M.acc.nrows_pad; info[30] = M.acc.slice_elems; info[31] = M.acc.nbatches; info[32] = M.acc.deferred;
         info[33] = L == SpmvLayout::accfused; info[34] = M.accf.built; info[35] = M.accf.nrb; info[36] = M.accf.RB; info[37] = M.accf.nbatches;
         info[38] = L == SpmvLayout::plain; info[39] = M.acc.nsteps;
+        info[40] = M.acc.wide_units;
         if (create_ms) for (int i = 0; i < 4; i++) create_ms[i] = c->create_ms[i];
     });
 }
@@ -1305,6 +1306,8 @@ int ipxk_layout_array(ipxk_context* c, int which, int array, void* out, ipxint c
             case 20: src = M.sorted.xmin.get(); bytes = M.sorted.built && M.sorted.fused ? (size_t)M.sorted.nrb * 4 : 0; break;
             case 21: src = M.acc.tile_step.get(); bytes = M.acc.built ? ((size_t)M.acc.nrb * M.acc.nslices + 1) * 4 : 0; break;
             case 22: src = M.acc.steps.get(); bytes = M.acc.built ? ((size_t)M.acc.nsteps + 1) * 16 : 0; break;
+            case 23: src = M.acc.wide.get(); bytes = M.acc.built ? (size_t)M.acc.wide_units * 16 : 0; break;
+            case 24: src = M.acc.wide_start.get(); bytes = M.acc.built && M.acc.wide_units > 0 ? ((size_t)M.acc.nsteps + 1) * 4 : 0; break;
             default: IPXK_REQUIRE(false, "unknown array");
         }
         if (M.nlong > 0 && (array < 8 || array > 10)) bytes = 0;       // long rows: the tiles hold fewer entries than nnz; not inspected

@@ -218,7 +218,7 @@ bool device_build_sorted(LayoutScratch& S, SortedMatrix& out, const SlicedMatrix
 bool device_build_acc(LayoutScratch& S, AccMatrix& out, const SlicedMatrix& sliced, int nrows, int ncols, int64_t nnz, const int* dptr,
                       const int* didx, const double* dval, hipStream_t s);
 // the persistent tile kernel's step table from A.tile_batch / A.bptr on the device (internal.hpp); the tail of both builders
-void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, hipStream_t s);
+void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, bool wide, hipStream_t s);
 
 // ---- reorder.hip: the locality-recovering renumbering (SURVEY section 7 / 8d "row/column reordering ... a pure permutation") ----
 void reorder_model(Context* c);

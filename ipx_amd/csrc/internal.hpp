@@ -294,6 +294,17 @@ constexpr int kAccPerThread = 4;
 constexpr int kAccBatch = kAccThreads * kAccPerThread;     // 2048 entries between two barriers
 constexpr int kAccMaxRows = 16384;                         // 128 KB of row sums; 14 bits of row in the entry word
 constexpr int kAccStepBatches = 4;                         // batches a step of the persistent kernel holds at most
+//   * the WIDE stream (IPXK_ACC_WIDE=0: not built; the sliced form only): a copy of the entries that the persistent kernel
+//     reads with three 16-byte loads per thread and step instead of four 4-byte and four 8-byte ones.  Derived from pack /
+//     val / steps by acc_build_steps, which are unchanged.  A step of ne entries is taken by Tp = acc_wide_threads(ne)
+//     threads (whole wavefronts; 512 for a full batch, 0 for none); thread t < Tp owns the sorted positions u Tp + t,
+//     u = 0..3 -- for a full batch the entries it always had, and in every step four entries that lie Tp apart, so that
+//     the lanes of a gather instruction still walk neighbouring addresses.  The step occupies 3 Tp units of 16 bytes from
+//     wide_start[step]: Tp units with each thread's four entry words, Tp with its values u = 0, 1, Tp with its values
+//     u = 2, 3 (a wavefront's load is one aligned KiB).  Positions >= ne hold word 0 and value 0.0 and are never added.
+//     wide_start has one entry per step record (the sentinel's: the total).  Only a tile's last step is short: at C3
+//     0.4 % more bytes than pack + val, and as much device memory again as those two (C3: 193 MB per gather matrix).
+__host__ __device__ inline int acc_wide_threads(int ne) { return ne >= kAccBatch ? kAccThreads : ((ne + 3) / 4 + 63) & ~63; }
 //   * FUSED form (one slice = all of x, for matrices whose gathers have locality; round 4): a tile is a row block of RB rows
 //     (as many as give every CU two tiles), the gathered index is stored relative to the tile's smallest one (`xmin`; the
 //     tile's window of x must span less than 2^18 entries), the row sums start from the epilogue's initial value and the
@@ -309,14 +320,16 @@ struct AccView {
     const uint4* steps;                // [# steps + 1] {first entry, three cuts} of each step
     const unsigned* pack;
     const double* val;
-    double* partial;                   // [nslices][nrows_pad]
+    const unsigned* wide_start;        // [# steps + 1] first 16-byte unit of each step in `wide`; nullptr: no wide stream
+    const uint4* wide;                 // [wide_start[# steps]] (the layout: above)
+    double* partial;                  // [nslices][nrows_pad]
 };
 struct AccMatrix {
     bool built = false;
     int nslices = 0, nrb = 0, RB = 0, nrows_pad = 0, slice_elems = 0;
-    int64_t nbatches = 0, deferred = 0, nsteps = 0;
-    DevBuf<unsigned> tile_batch, bptr, pack, tile_step;
-    DevBuf<uint4> steps;
+    int64_t nbatches = 0, deferred = 0, nsteps = 0, wide_units = 0;
+    DevBuf<unsigned> tile_batch, bptr, pack, tile_step, wide_start;
+    DevBuf<uint4> steps, wide;
     DevBuf<double> val, partial;
     bool fused = false;                // the FUSED form
     DevBuf<int> xmin;

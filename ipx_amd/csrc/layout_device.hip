@@ -269,6 +269,33 @@ __global__ void acc_step_fill_kernel(int ntiles, const unsigned* __restrict__ ti
     }
 }
 
+// The wide stream (internal.hpp) of the steps: the 16-byte units of every step, then (one workgroup per step) its three planes.
+__global__ void acc_wide_count_kernel(int nsteps, const uint4* __restrict__ steps, unsigned* __restrict__ units) {
+    IPXK_GRID_STRIDE(k, nsteps) units[k] = 3u * (unsigned)acc_wide_threads((int)(steps[k + 1].x - steps[k].x));
+}
+__global__ __launch_bounds__(kAccThreads) void acc_wide_fill_kernel(int nsteps, const uint4* __restrict__ steps, const unsigned* __restrict__ wide_start,
+                                                                    const unsigned* __restrict__ pack, const double* __restrict__ val,
+                                                                    uint4* __restrict__ wide) {
+    const int t = threadIdx.x;
+    for (int k = blockIdx.x; k < nsteps; k += gridDim.x) {
+        const unsigned e0 = steps[k].x;
+        const int ne = (int)(steps[k + 1].x - e0), tp = acc_wide_threads(ne);
+        if (t >= tp) continue;
+        unsigned w[kAccPerThread];
+        double v[kAccPerThread];
+#pragma unroll
+        for (int u = 0; u < kAccPerThread; u++) {
+            const int p = u * tp + t;
+            w[u] = p < ne ? pack[e0 + p] : 0u;
+            v[u] = p < ne ? val[e0 + p] : 0.0;
+        }
+        uint4* dst = wide + wide_start[k];
+        dst[t] = make_uint4(w[0], w[1], w[2], w[3]);
+        reinterpret_cast<double2*>(dst + tp)[t] = make_double2(v[0], v[1]);
+        reinterpret_cast<double2*>(dst + 2 * tp)[t] = make_double2(v[2], v[3]);
+    }
+}
+
 // ---- one-slice (FUSED) forms: a tile is a row block, offsets are relative to the tile's smallest gathered index ----
 // smallest / largest gathered index per tile, the rows' count bytes (optional), a flag for rows with descending / repeated indices
 __global__ void tile_window_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, int* __restrict__ lo,
@@ -583,8 +610,12 @@ int acc_rows_per_block(int nrows, int ns) {
 // The step table of the persistent tile kernel from A.tile_batch / A.bptr (both on the device), for the host and the device
 // builder alike: fills A.tile_step / steps / nsteps.  IPXK_ACC_STEPS=0: every batch is a step (the schedule without steps;
 // A/B runs and the tests' reference).  Synchronizes (the read-back of the step count; the temporary).
-void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, hipStream_t s) {
+// wide (the sliced form, whose persistent kernel reads it): then the wide stream of those steps from A.pack / A.val, unless
+// IPXK_ACC_WIDE=0 (the kernel then streams pack / val as before; A/B runs and the tests' reference) -- A.wide_start / wide /
+// wide_units.  Not built either when the units could overflow 32 bits (more than 2^21 steps).
+void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, bool wide, hipStream_t s) {
     static const bool merge = !(getenv("IPXK_ACC_STEPS") && getenv("IPXK_ACC_STEPS")[0] == '0');
+    static const bool wide_on = !(getenv("IPXK_ACC_WIDE") && getenv("IPXK_ACC_WIDE")[0] == '0');
     static_assert(kAccStepBatches == 4, "a step record holds three cuts");
     const unsigned maxb = merge ? kAccStepBatches : 1;
     DevBuf<unsigned> nstep((size_t)ntiles + 1);
@@ -599,6 +630,20 @@ void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, hipStream_t s) {
                        A.tile_step.get(), (unsigned)nnz, A.steps.get());
     IPXK_HIP(hipStreamSynchronize(s));          // nstep goes out of scope
     A.nsteps = total;
+    A.wide_start.release(); A.wide.release(); A.wide_units = 0;
+    if (!wide || !wide_on || total == 0 || total > (1u << 21)) return;
+    DevBuf<unsigned> units((size_t)total + 1);
+    hipLaunchKernelGGL(acc_wide_count_kernel, dim3(gridn(total)), dim3(kBlock), 0, s, (int)total, A.steps.get(), units.get());
+    A.wide_start.ensure((size_t)total + 1);
+    scan_u32((int)total, units.get(), A.wide_start.get(), s);
+    unsigned nunits = 0;
+    IPXK_HIP(hipMemcpyAsync(&nunits, A.wide_start.get() + total, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    IPXK_HIP(hipStreamSynchronize(s));
+    A.wide.ensure((size_t)nunits);
+    hipLaunchKernelGGL(acc_wide_fill_kernel, dim3(std::min<unsigned>(total, 8192u)), dim3(kAccThreads), 0, s, (int)total, A.steps.get(),
+                       A.wide_start.get(), A.pack.get(), A.val.get(), A.wide.get());
+    IPXK_HIP(hipStreamSynchronize(s));          // units goes out of scope
+    A.wide_units = nunits;
 }
 
 // The tail both accumulated forms share.  On entry S.q2 / S.v2 hold the entries' keys (tile << 18 | offset) and storage positions
@@ -611,7 +656,8 @@ struct AccTemps {
     DevBuf<unsigned> tile_ptr, nbatch, bstart;
     AccTemps(int64_t ntiles, size_t nz) : rowof(nz), tile_ptr((size_t)ntiles + 1), nbatch((size_t)ntiles + 1), bstart(nz) {}
 };
-static void acc_batches(LayoutScratch& S, AccMatrix& out, AccTemps& T, int64_t ntiles, int RB, int64_t nnz, const double* dval, hipStream_t s) {
+static void acc_batches(LayoutScratch& S, AccMatrix& out, AccTemps& T, int64_t ntiles, int RB, int64_t nnz, const double* dval, bool wide,
+                        hipStream_t s) {
     const size_t nz = (size_t)nnz;
     unsigned* word = S.k1.get();
     hipLaunchKernelGGL(acc_words_kernel, dim3(gridn(nnz)), dim3(kBlock), 0, s, nnz, S.q2.get(), S.v2.get(), T.rowof.get(), RB, word);
@@ -634,7 +680,7 @@ static void acc_batches(LayoutScratch& S, AccMatrix& out, AccTemps& T, int64_t n
     hipLaunchKernelGGL(acc_scatter_kernel, dim3(gridn(nnz)), dim3(kBlock), 0, s, nnz, S.k2.get(), word, S.v2.get(), dval, out.pack.get(),
                        out.val.get());
     out.nbatches = nb_total; out.deferred = (int64_t)ndef;
-    acc_build_steps(out, ntiles, nnz, s);
+    acc_build_steps(out, ntiles, nnz, wide, s);
 }
 
 // The prologue both fused forms share: smallest and largest gathered index of every tile of RB rows (lo, hi: nrb entries each; lo is
@@ -670,7 +716,7 @@ bool device_build_acc(LayoutScratch& S, AccMatrix& out, const SlicedMatrix& slic
     sort_pairs<u64>(S.T, S.q1.get(), S.q2.get(), S.v1.get(), S.v2.get(), nz, kSortedOffBits + bits_for((u64)std::max<int64_t>(ntiles, 2) - 1), s);
     hipLaunchKernelGGL(lower_bounds_kernel<u64>, dim3(gridn(ntiles + 1)), dim3(kBlock), 0, s, ntiles + 1, nnz, S.q2.get(), (u64)1, kSortedOffBits,
                        T.tile_ptr.get());
-    acc_batches(S, out, T, ntiles, RB, nnz, dval, s);
+    acc_batches(S, out, T, ntiles, RB, nnz, dval, true, s);
     IPXK_HIP(hipStreamSynchronize(s));       // the temporaries go out of scope
     IPXK_HIP(hipGetLastError());
     out.nslices = ns; out.nrb = nrb; out.RB = RB; out.nrows_pad = nrb * RB; out.slice_elems = (int)slice;
@@ -738,7 +784,7 @@ bool device_build_acc_fused(LayoutScratch& S, AccMatrix& out, int nrows, int nco
     sort_pairs<u64>(S.T, S.q1.get(), S.q2.get(), S.v1.get(), S.v2.get(), nz, kSortedOffBits + bits_for((u64)std::max(nrb, 2) - 1), s);
     hipLaunchKernelGGL(tile_ptr_from_rows_kernel, dim3(gridn(nrb + 1)), dim3(kBlock), 0, s, nrb, nrows, RB, dptr, T.tile_ptr.get());
     out.xmin.ensure((size_t)nrb);
-    acc_batches(S, out, T, nrb, RB, nnz, dval, s);
+    acc_batches(S, out, T, nrb, RB, nnz, dval, false, s);
     IPXK_HIP(hipMemcpyAsync(out.xmin.get(), lo.get(), (size_t)nrb * sizeof(int), hipMemcpyDeviceToDevice, s));
     IPXK_HIP(hipStreamSynchronize(s));
     IPXK_HIP(hipGetLastError());

@@ -371,7 +371,7 @@ struct AccBatcher {
         A.bptr.upload(bp, s);
         A.pack.upload(pk, s);
         A.val.upload(tv, s);
-        acc_build_steps(A, (int64_t)tb.size() - 1, nnz, s);
+        acc_build_steps(A, (int64_t)tb.size() - 1, nnz, !A.fused, s);
     }
 };
 }  // namespace

@@ -276,6 +276,7 @@ static AccView view_of(const AccMatrix& A, int nrows) {
     V.xmin = A.xmin.get();
     V.tile_batch = A.tile_batch.get(); V.bptr = A.bptr.get(); V.pack = A.pack.get(); V.val = A.val.get(); V.partial = A.partial.get();
     V.tile_step = A.tile_step.get(); V.steps = A.steps.get();
+    V.wide_start = A.wide_start.get(); V.wide = A.wide.get();
     return V;
 }
 AccView GatherMatrix::acc_view() const { return view_of(acc, nrows); }

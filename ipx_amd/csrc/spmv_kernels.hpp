@@ -793,11 +793,20 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, c
 // same sequence of ds_add_f64 as in the one-tile kernel, so the partials are equal bit for bit.
 constexpr int kAccParkPairs = kAccMaxRows / (2 * kAccThreads);       // 16 row pairs (64 VGPRs) per thread
 constexpr int kAccParkPerBatch = 2;
-template <class Prod>
+// WIDE: the entries come from the wide stream (internal.hpp) -- per thread and step three 16-byte loads, of its four entry words
+// and its four values, instead of four 4-byte and four 8-byte ones (the same bytes in flight as 72 instead of 190 load
+// instructions per CU).  Tp = acc_wide_threads(ne) threads take part in a step, thread t holds the sorted positions u Tp + t;
+// the padding positions >= ne are gathered (word 0: the slice's first element) and never added.  Which thread adds an entry
+// cannot change a sum (the rows of a batch are distinct), so every row sum is the same sequence of ds_add_f64 between the same
+// barriers as without.
+typedef unsigned acc_u32x4 __attribute__((ext_vector_type(4)));
+typedef double acc_f64x2 __attribute__((ext_vector_type(2)));
+template <class Prod, bool WIDE>
 // (the step tables come as __restrict__ arguments: the partial stores of the loop would otherwise keep the compiler from
 // reading them with scalar loads, and a vector load of a step record waits vmcnt(0) -- for the whole pipeline)
 __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M, const unsigned* __restrict__ tile_step,
-                                                                       const uint4* __restrict__ steps, const double* __restrict__ x,
+                                                                       const uint4* __restrict__ steps, const unsigned* __restrict__ wide_start,
+                                                                       const acc_u32x4* __restrict__ wide, const double* __restrict__ x,
                                                                        const int* done) {
     // *done is fetched together with the first step-table loads and tested when they are there, not in a round trip of its
     // own in front of them (no `done`: a word of the table, which counts for nothing)
@@ -814,18 +823,20 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
     // end); an empty tile has no record and yields one empty step, so that its partial is written (zeros) like any other.
     // A step (internal.hpp) is entries [e0, e1) of one tile: streamed and gathered as one batch, added as the batches
     // [e0, c1) [c1, c2) [c2, c3) [c3, e1) with a barrier in front of every non-empty one after the first.
-    struct Step { unsigned e0, e1, c1, c2, c3; int tile; };    // tile -1: past the workgroup's last tile
+    // WIDE: w0 = the step's first unit of the wide stream (an empty step: 0)
+    struct Step { unsigned e0, e1, c1, c2, c3, w0; int tile; };    // tile -1: past the workgroup's last tile
     int wt = blockIdx.x, wq = 0, wnb = 0;
     unsigned wb0 = 0;
     if (wt < ntiles) { wb0 = tile_step[wt]; wnb = (int)(tile_step[wt + 1] - wb0); }
     if (done && dn) return;
     auto next = [&]() -> Step {
-        Step b{0u, 0u, 0u, 0u, 0u, -1};
+        Step b{0u, 0u, 0u, 0u, 0u, 0u, -1};
         if (wt >= ntiles) return b;
         b.tile = wt;
         if (wnb > 0) {
             const uint4 r = steps[wb0 + wq];
             b.e0 = r.x; b.c1 = r.y; b.c2 = r.z; b.c3 = r.w; b.e1 = steps[wb0 + wq + 1].x;
+            if (WIDE) b.w0 = wide_start[wb0 + wq];
         }
         if (++wq >= max(wnb, 1)) {
             wt += G; wq = 0;
@@ -842,15 +853,27 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
     // The loads of an empty batch are issued too, from entry 0 and x[0] (the product has at least one entry and one column):
     // a load issued on one path only makes the compiler's s_waitcnt after the join count the other path's loads, and an
     // empty batch k + 1 then turned the adds of batch k into a wait for everything in flight (vmcnt(0)) in every batch.
-    auto stream = [&](unsigned (&pkb)[U], double (&vb)[U], unsigned e0, unsigned e1) {     // entries [e0, e1) of a batch
-        const int ne = (int)(e1 - e0);
-        const unsigned base = ne > 0 ? e0 : 0u;
-        const int last = max(ne - 1, 0);
+    // WIDE: unit min(tid, Tp - 1) of each of the step's three planes; an empty step (Tp = 0, w0 = 0) loads unit 0 three times
+    auto stream = [&](unsigned (&pkb)[U], double (&vb)[U], const Step& b) {     // entries [e0, e1) of a step
+        const int ne = (int)(b.e1 - b.e0);
+        if constexpr (WIDE) {
+            static_assert(U == 4, "a unit of the wide stream holds a thread's four entries");
+            const int tp = acc_wide_threads(ne);
+            const acc_u32x4* src = wide + b.w0 + min(tid, max(tp - 1, 0));
+            const acc_u32x4 w = __builtin_nontemporal_load(src);
+            const acc_f64x2 v01 = __builtin_nontemporal_load(reinterpret_cast<const acc_f64x2*>(src + tp));
+            const acc_f64x2 v23 = __builtin_nontemporal_load(reinterpret_cast<const acc_f64x2*>(src + 2 * tp));
+            pkb[0] = w.x; pkb[1] = w.y; pkb[2] = w.z; pkb[3] = w.w;
+            vb[0] = v01.x; vb[1] = v01.y; vb[2] = v23.x; vb[3] = v23.y;
+        } else {
+            const unsigned base = ne > 0 ? b.e0 : 0u;
+            const int last = max(ne - 1, 0);
 #pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int i = min(u * T + tid, last);
-            pkb[u] = __builtin_nontemporal_load(M.pack + base + i);
-            vb[u] = __builtin_nontemporal_load(M.val + base + i);
+            for (int u = 0; u < U; u++) {
+                const int i = min(u * T + tid, last);
+                pkb[u] = __builtin_nontemporal_load(M.pack + base + i);
+                vb[u] = __builtin_nontemporal_load(M.val + base + i);
+            }
         }
     };
     auto gather = [&](double (&xgb)[U], const unsigned (&pkb)[U], const Step& b) {
@@ -864,7 +887,7 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
     for (int d = 0; d < 3; d++) {
 #pragma unroll
         for (int u = 0; u < U; u++) { pk[d][u] = 0u; v[d][u] = 0.0; }
-        stream(pk[d], v[d], q[d].e0, q[d].e1);
+        stream(pk[d], v[d], q[d]);
     }
     for (int r = tid; r < M.RB; r += T) ac_sum[r] = 0.0;
     gather(xg[0], pk[0], q[0]);
@@ -911,10 +934,13 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
                 // the step's first batch, then (a tile's short tail batches taken as one step) up to three more, each behind a
                 // barrier of its own: the same ds_add_f64 between the same barriers as one batch per step.  The cuts are
                 // scalars, the same in every wave; a step of one batch (c1 == e1) pays one scalar compare for the rest
+                // (S: the distance of a thread's entries -- T, or the step's Tp with the wide stream, whose threads >= Tp hold none)
                 const int n1 = (int)(q[0].c1 - q[0].e0);
+                const int S = WIDE ? acc_wide_threads(ne) : T;
+                const bool mine = !WIDE || tid < S;
 #pragma unroll
                 for (int u = 0; u < U; u++)
-                    if (u * T + tid < n1)
+                    if (mine && u * S + tid < n1)
                         __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), Prod::prod(xg[d & 1][u], v[d % 3][u]), __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (n1 < ne) {
@@ -924,13 +950,13 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
                         __syncthreads();
 #pragma unroll
                         for (int u = 0; u < U; u++)
-                            if (u * T + tid >= lo && u * T + tid < hi)
+                            if (mine && u * S + tid >= lo && u * S + tid < hi)
                                 __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), Prod::prod(xg[d & 1][u], v[d % 3][u]),
                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         lo = hi; hi = hi2; hi2 = ne;
                     }
                 }
-                stream(pk[d % 3], v[d % 3], q[3].e0, q[3].e1);               // step k + 3 into the buffer just emptied
+                stream(pk[d % 3], v[d % 3], q[3]);               // step k + 3 into the buffer just emptied
                 if (pleft > 0) store_parked();
 #pragma unroll
                 for (int i = 0; i + 1 < NE; i++) q[i] = q[i + 1];
@@ -1204,14 +1230,21 @@ inline void launch_acc_tiles(const AccView& W, const double* x, const int* done,
     if (!lds_attr_set) {
         IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_tile_kernel<Prod>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)(kAccMaxRows * sizeof(double))));
-        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(kAccMaxRows * sizeof(double))));
+        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)(kAccMaxRows * sizeof(double))));
         lds_attr_set = true;
     }
     const size_t lds = (size_t)W.RB * sizeof(double);
     const int ntiles = W.nrb * W.nslices, G = acc_persist_grid(W.nslices);
-    if (G > 0) hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod>), dim3(std::min(G, ntiles)), dim3(kAccThreads), lds, s, W, W.tile_step, W.steps,
-                                  x, done);
+    const dim3 pgrid(std::min(G, ntiles));
+    if (G > 0 && W.wide)       // (the wide stream: built unless IPXK_ACC_WIDE=0)
+        hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, true>), pgrid, dim3(kAccThreads), lds, s, W, W.tile_step, W.steps, W.wide_start,
+                           reinterpret_cast<const acc_u32x4*>(W.wide), x, done);
+    else if (G > 0)
+        hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, false>), pgrid, dim3(kAccThreads), lds, s, W, W.tile_step, W.steps,
+                           (const unsigned*)nullptr, (const acc_u32x4*)nullptr, x, done);
     else hipLaunchKernelGGL((spmv_acc_tile_kernel<Prod>), dim3(ntiles), dim3(kAccThreads), lds, s, W, x, done);
 }
 
