@@ -321,7 +321,8 @@ class KktContext:
         return ("none", "rccl", "direct")[t.value], n.value, r.value
 
     def spmv_layout(self):
-        """(layout of A'y, layout of A t) as 'phased'/'sliced', and the build-time timings in us."""
+        """(layout of A'y, layout of A t), each one of 'phased', 'sliced', 'fused', 'sorted', 'sortedfused', 'acc', 'plain',
+        'accfused', and the build-time timings in us."""
         lay = (C.c_int * 2)()
         us = (C.c_double * 6)()
         self._check(self.lib.ipxk_spmv_layout(self.h, lay, us))
