@@ -104,7 +104,7 @@ __device__ __forceinline__ T wave_max(T v) { return wave_reduce<PlainMaxOp, kWid
 __device__ __forceinline__ void take_larger(double& v, int& i, double ov, int oi) {
     if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
-__device__ __forceinline__ void take_smaller(double& v, int& i, double ov, int oi) {
+__host__ __device__ __forceinline__ void take_smaller(double& v, int& i, double ov, int oi) {   // host: step_to_boundary_dev's fold
     if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
 template <int kWidth = 64>

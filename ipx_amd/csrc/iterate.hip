@@ -218,8 +218,9 @@ __global__ void subtract_slack_kernel(int m, const double* __restrict__ xI, doub
 }
 
 // the four step-to-boundary problems of a step (xl, xu, zl, zu), problem k's block partials at part + 2 g k (alpha,
-// then index).  Wave k reduces them to the first block that holds the smallest alpha below alpha0 -- the block-order
-// scan of step_to_boundary_dev -- and writes row[6k..6k+5] = alpha, GLOBAL blocking index (structural c0 + j, slack
+// then index).  Wave k reduces them to the smallest alpha below alpha0 and the smallest index attaining it -- the fold
+// of step_to_boundary_dev; a block's index may lie in a later grid pass than a higher block's, so the fold compares
+// indices, not block numbers -- and writes row[6k..6k+5] = alpha, GLOBAL blocking index (structural c0 + j, slack
 // n_global + i; -1: none), and the x, dx, z, dz at the candidate that StepSizes reads (the l pair for problems 0 and 2,
 // the u pair for 1 and 3).
 __global__ __launch_bounds__(256) void boundary_row_kernel(int g, const double* __restrict__ part, double alpha0, int n,
@@ -228,16 +229,15 @@ __global__ __launch_bounds__(256) void boundary_row_kernel(int g, const double* 
     const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const double* a = part + (size_t)2 * g * k;
     double alpha = alpha0;
-    int blk = g;                            // g: none; i ascends per lane, so its first block is kept
+    int idx = INT_MAX;                      // none; a block that holds a step below alpha0 holds its index too
     for (int i = lane; i < g; i += 64)
-        if (a[i] < alpha) { alpha = a[i]; blk = i; }
-    wave_argmin(alpha, blk);
+        if (a[i] < alpha0) take_smaller(alpha, idx, a[i], (int)a[g + i]);
+    wave_argmin(alpha, idx);
     if (lane != 0) return;
-    const double idx = blk < g ? a[g + blk] : -1.0;
     double* r = row + 6 * k;
     r[0] = alpha;
-    if (idx >= 0.0) {
-        const int j = (int)idx;
+    if (idx != INT_MAX) {
+        const int j = idx;
         const bool lower = (k & 1) == 0;
         r[1] = j < n ? c0 + j : n_global + (j - n);
         r[2] = lower ? V.xl[j] : V.xu[j];
@@ -469,11 +469,13 @@ double step_to_boundary_dev(Context* c, const double* x, const double* dx, int64
     std::vector<double> h((size_t)2 * g);
     c->it_partials.download(h.data(), h.size(), c->stream);
     IPXK_HIP(hipGetLastError());
+    // the smallest step below alpha0 and the smallest index attaining it.  Block b holds the elements b*kBlock + t of
+    // every grid pass, so among tied blocks the smallest index need not be the first block's: compare the indices
     double alpha = alpha0;
-    ipxint blk = -1;
+    int idx = INT_MAX;
     for (int i = 0; i < g; i++)
-        if (h[i] < alpha) { alpha = h[i]; blk = (ipxint)h[(size_t)g + i]; }   // blocks ascend: first index kept
-    if (blocking) *blocking = blk;
+        if (h[i] < alpha0) take_smaller(alpha, idx, h[i], (int)h[(size_t)g + i]);
+    if (blocking) *blocking = idx == INT_MAX ? -1 : idx;
     return alpha;
 }
 
