@@ -925,9 +925,9 @@ ipxint ipxk_normal_apply_bytes(const ipxk_context* ctx);
 /* Which device layout the two sparse products of NormalMatrix::_Apply
  * (normal_matrix.cc:45-126) use on this model: layout[0] for t = W.*(A'y),
  * layout[1] for lhs = A t; 0 = phased (time-tiled), 1 = XCD-sliced tiles,
- * 2 = fused tiles (one slice, epilogue in the tile kernel), 3 = sorted
- * sub-tiles (the sliced layout's slices with the gathers of a tile issued in
- * address order; same partial sums as 1, bit for bit), 4 = sorted fused tiles
+ * 2 = fused tiles (one slice, epilogue in the tile kernel), 3 = retired (it
+ * was the sorted sub-tiles: the sliced layout's slices with the gathers of a
+ * tile issued in address order; never returned), 4 = sorted fused tiles
  * (one slice, gathers in address order, epilogue in the tile kernel: bit-identical
  * to 0 and 2, for matrices whose gathers have locality), 5 = accumulated tiles
  * (the sliced layout's slices, a row block's sums kept in LDS, the entries of a
@@ -939,11 +939,12 @@ ipxint ipxk_normal_apply_bytes(const ipxk_context* ctx);
  * with one slice and the epilogue in the tile kernel, for matrices whose gathers have
  * locality and whose rows are stored sorted: bit-identical to 0, 2, 4, 6).  The sliced layouts are
  * chosen by a property of the matrix (x larger than an XCD's L2 and gathers that
- * spread over the slices): 5 when it can be built, else the faster of 1 and 3;
- * otherwise a timing at ipxk_create picks among the bit-identical 0, 2, 4, 6 and 7
- * (IPXK_SPMV_LAYOUT=phased|sliced|fused|sorted|sortedfused|acc|plain|accfused
+ * spread over the slices): 5 when it can be built (the host builders do not
+ * build it for a matrix with long rows), else 1, no timing takes part; otherwise a timing at ipxk_create picks among the
+ * bit-identical 0, 2, 4, 6 and 7
+ * (IPXK_SPMV_LAYOUT=phased|sliced|fused|sortedfused|acc|plain|accfused
  * overrides).  us[6] receives the measured microseconds {pass 1: phased, the layout
- * in use if it is 1, 3 or 5 (else sliced), the layout in use if it is 2, 4, 6 or 7
+ * in use if it is 1 or 5 (else sliced), the layout in use if it is 2, 4, 6 or 7
  * (else fused); pass 2 likewise} (0 = not timed). */
 int ipxk_spmv_layout(const ipxk_context* ctx, int layout[2], double us[6]);
 /* The guard of the explicit inverses of SplittedNormalMatrix::Prepare's device
@@ -974,26 +975,29 @@ ipxint ipxk_split_inverse_refined(const ipxk_context* ctx);
  * "construct = store a reference" is one upload + transpose + layout build per
  * model, timed in create_ms {upload + transpose, A' layouts, A layouts, rest}.
  * which: 0 = the gather matrix of A'y (rows = columns of A), 1 = of A t.
- * info: {use_sliced, use_sorted, use_sorted_fused, nlong, sliced.built, R,
+ * info: {use_sliced, retired, use_sorted_fused, nlong, sliced.built, R,
  * nslices, nrb, nrows_pad, max_tile, bits of the fullest-slice share (double),
- * sorted.built, nslices, nsub, nrb, RB, nrows_pad, max_sub, slice_elems, fused,
+ * sorted.built, retired, retired, nrb, RB, nrows_pad, max_sub, retired, retired,
  * nnz, P, G, RT*1e6 + Q*1e3, use_acc, acc.built, nslices, nrb, RB, nrows_pad,
  * slice_elems, # batches, # entries that waited for a later batch, use_acc_fused,
  * accf.built, nrb, RB, # batches, use_plain, # steps of the accumulated tiles (runs
  * of batches the persistent kernel takes as one pipeline step), # 16-byte units of
- * their wide stream (0: not built, IPXK_ACC_WIDE=0); the rest of the 48 is 0}.  use_sorted, use_sorted_fused, use_acc,
+ * their wide stream (0: not built, IPXK_ACC_WIDE=0); the rest of the 48 is 0}.
+ * `sorted`: the sorted fused tiles.  The retired slots [1], [12], [13], [18], [19]
+ * described the sorted sub-tiles (use_sorted, their slice and sub-slice counts, their
+ * slice width, the fused flag) and are always 0.  use_sorted_fused, use_acc,
  * use_acc_fused and use_plain say whether that is the layout of ipxk_spmv_layout (at
  * most one of them is 1); use_sliced whether the sliced or fused tiles are built, which
  * masked products (the basis path) use whatever the layout. */
 int ipxk_layout_info(const ipxk_context* ctx, int which, ipxint info[48],
                      double create_ms[4]);
 /* array: 0 sliced tile_ptr (u32), 1 sliced cnt (u8), 2 sliced idx (i32), 3
- * sliced val (f64), 4 sorted sub_ptr (u32), 5 sorted cnt (u8), 6 sorted pack
- * (u32), 7 sorted val (f64), 8 / 9 / 10 the row-wise copy of the model (Transpose,
+ * sliced val (f64), 4-7 the sorted fused tiles: sub_ptr (u32), cnt (u8), pack
+ * (u32), val (f64); 8 / 9 / 10 the row-wise copy of the model (Transpose,
  * sparse_matrix.cc:120-151) as the device holds it: ptr (i32), idx (i32), val
  * (f64); 11 acc tile_batch (u32), 12 acc bptr (u32), 13 acc pack (u32), 14 acc
  * val (f64); 15-19 the fused accumulated tiles: tile_batch, bptr, pack (u32), val
- * (f64), xmin (i32); 20 xmin of the fused sorted tiles (i32); 21 acc
+ * (f64), xmin (i32); 20 xmin of the sorted fused tiles (i32); 21 acc
  * tile_step (u32, first step of each tile), 22 acc step records (4 x u32 each: first
  * entry and three cuts; one more than there are steps); 23 the wide stream of the
  * accumulated tiles (u32; units of 16 bytes: per step of ne entries and Tp =

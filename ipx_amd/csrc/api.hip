@@ -1254,13 +1254,14 @@ int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[48], double c
         const GatherMatrix& M = which == 0 ? c->Acols : c->Arows;
         for (int i = 0; i < 48; i++) info[i] = 0;
         const SpmvLayout L = M.layout;
-        info[0] = M.tile_base() != SpmvLayout::phased; info[1] = L == SpmvLayout::sorted; info[2] = L == SpmvLayout::sortedfused; info[3] = M.nlong;
+        info[0] = M.tile_base() != SpmvLayout::phased; info[2] = L == SpmvLayout::sortedfused; info[3] = M.nlong;
         info[4] = M.sliced.built; info[5] = M.sliced.R; info[6] = M.sliced.nslices; info[7] = M.sliced.nrb;
         info[8] = M.sliced.nrows_pad; info[9] = M.sliced.max_tile;
         { double d = M.sliced.dominant_fraction; memcpy(&info[10], &d, sizeof d); }
-        info[11] = M.sorted.built; info[12] = M.sorted.nslices; info[13] = M.sorted.nsub; info[14] = M.sorted.nrb;
-        info[15] = M.sorted.RB; info[16] = M.sorted.nrows_pad; info[17] = M.sorted.max_sub; info[18] = M.sorted.slice_elems;
-        info[19] = M.sorted.fused; info[20] = M.nnz;
+        // ([1], [12], [13], [18], [19] described the sorted sub-tiles, retired: always 0)
+        info[11] = M.sorted.built; info[14] = M.sorted.nrb;
+        info[15] = M.sorted.RB; info[16] = M.sorted.nrows_pad; info[17] = M.sorted.max_sub;
+        info[20] = M.nnz;
         info[21] = M.P; info[22] = M.G; info[23] = (ipxint)M.RT * 1000000 + (ipxint)M.Q * 1000 + 0;
         info[24] = L == SpmvLayout::acc; info[25] = M.acc.built; info[26] = M.acc.nslices; info[27] = M.acc.nrb; info[28] = M.acc.RB;
         info[29] = M.acc.nrows_pad; info[30] = M.acc.slice_elems; info[31] = M.acc.nbatches; info[32] = M.acc.deferred;
@@ -1271,7 +1272,8 @@ int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[48], double c
     });
 }
 // array: 0 sliced.tile_ptr (u32) 1 sliced.cnt (u8) 2 sliced.idx (i32) 3 sliced.val (f64) 4 sorted.sub_ptr (u32)
-// 5 sorted.cnt (u8) 6 sorted.pack (u32) 7 sorted.val (f64) 8 plain row-wise ptr (i32) 9 idx (i32) 10 val (f64).
+// 5 sorted.cnt (u8) 6 sorted.pack (u32) 7 sorted.val (f64) 8 plain row-wise ptr (i32) 9 idx (i32) 10 val (f64);
+// `sorted`: the sorted fused tiles.
 // Copies min(cap, size) bytes to `out` (host), *nbytes = size of the array in bytes.
 int ipxk_layout_array(ipxk_context* c, int which, int array, void* out, ipxint cap, ipxint* nbytes) {
     return guarded([&] {
@@ -1280,15 +1282,15 @@ int ipxk_layout_array(ipxk_context* c, int which, int array, void* out, ipxint c
         const GatherMatrix& M = which == 0 ? c->Acols : c->Arows;
         const void* src = nullptr;
         size_t bytes = 0;
-        const size_t ntiles = (size_t)M.sliced.nrb * M.sliced.nslices, nsubs = (size_t)M.sorted.nrb * std::max(M.sorted.nslices, 1) * std::max(M.sorted.nsub, 1);
+        const size_t ntiles = (size_t)M.sliced.nrb * M.sliced.nslices, nsorted = (size_t)M.sorted.nrb;
         const size_t nz = (size_t)M.nnz;
         switch (array) {
             case 0: src = M.sliced.tile_ptr.get(); bytes = M.sliced.built ? (ntiles + 1) * 4 : 0; break;
             case 1: src = M.sliced.cnt.get(); bytes = M.sliced.built ? ntiles * M.sliced.R : 0; break;
             case 2: src = M.sliced.idx.get(); bytes = M.sliced.built ? nz * 4 : 0; break;
             case 3: src = M.sliced.val.get(); bytes = M.sliced.built ? nz * 8 : 0; break;
-            case 4: src = M.sorted.sub_ptr.get(); bytes = M.sorted.built ? (nsubs + 1) * 4 : 0; break;
-            case 5: src = M.sorted.cnt.get(); bytes = M.sorted.built ? nsubs * M.sorted.RB : 0; break;
+            case 4: src = M.sorted.sub_ptr.get(); bytes = M.sorted.built ? (nsorted + 1) * 4 : 0; break;
+            case 5: src = M.sorted.cnt.get(); bytes = M.sorted.built ? nsorted * M.sorted.RB : 0; break;
             case 6: src = M.sorted.pack.get(); bytes = M.sorted.built ? nz * 4 : 0; break;
             case 7: src = M.sorted.val.get(); bytes = M.sorted.built ? nz * 8 : 0; break;
             case 8: src = c->pl_Tp.get(); bytes = ((size_t)c->m + 1) * 4; break;
@@ -1303,7 +1305,7 @@ int ipxk_layout_array(ipxk_context* c, int which, int array, void* out, ipxint c
             case 17: src = M.accf.pack.get(); bytes = M.accf.built ? nz * 4 : 0; break;
             case 18: src = M.accf.val.get(); bytes = M.accf.built ? nz * 8 : 0; break;
             case 19: src = M.accf.xmin.get(); bytes = M.accf.built ? (size_t)M.accf.nrb * 4 : 0; break;
-            case 20: src = M.sorted.xmin.get(); bytes = M.sorted.built && M.sorted.fused ? (size_t)M.sorted.nrb * 4 : 0; break;
+            case 20: src = M.sorted.xmin.get(); bytes = M.sorted.built ? (size_t)M.sorted.nrb * 4 : 0; break;
             case 21: src = M.acc.tile_step.get(); bytes = M.acc.built ? ((size_t)M.acc.nrb * M.acc.nslices + 1) * 4 : 0; break;
             case 22: src = M.acc.steps.get(); bytes = M.acc.built ? ((size_t)M.acc.nsteps + 1) * 16 : 0; break;
             case 23: src = M.acc.wide.get(); bytes = M.acc.built ? (size_t)M.acc.wide_units * 16 : 0; break;
@@ -1331,7 +1333,7 @@ int ipxk_spmv_layout(const ipxk_context* c, int layout[2], double us[6]) {
             const SpmvLayout L = M[k]->layout;
             layout[k] = (int)L;
             if (!us) continue;
-            const bool tiles = L == SpmvLayout::sliced || L == SpmvLayout::sorted || L == SpmvLayout::acc;
+            const bool tiles = L == SpmvLayout::sliced || L == SpmvLayout::acc;
             const bool fused = L == SpmvLayout::fused || L == SpmvLayout::sortedfused || L == SpmvLayout::plain || L == SpmvLayout::accfused;
             us[3 * k] = M[k]->tuned_us[(int)SpmvLayout::phased];
             us[3 * k + 1] = M[k]->tuned_us[(int)(tiles ? L : SpmvLayout::sliced)];

@@ -213,8 +213,6 @@ bool device_build_sorted_fused(LayoutScratch& S, SortedMatrix& out, int nrows, i
                                const double* dval, hipStream_t s);
 bool device_build_acc_fused(LayoutScratch& S, AccMatrix& out, int nrows, int ncols, int64_t nnz, const int* dptr, const int* didx,
                             const double* dval, hipStream_t s);
-bool device_build_sorted(LayoutScratch& S, SortedMatrix& out, const SlicedMatrix& sliced, int nrows, int ncols, int64_t nnz, const int* dptr,
-                         const int* didx, const double* dval, hipStream_t s);
 bool device_build_acc(LayoutScratch& S, AccMatrix& out, const SlicedMatrix& sliced, int nrows, int ncols, int64_t nnz, const int* dptr,
                       const int* didx, const double* dval, hipStream_t s);
 // the persistent tile kernel's step table from A.tile_batch / A.bptr on the device (internal.hpp); the tail of both builders

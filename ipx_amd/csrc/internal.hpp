@@ -217,49 +217,39 @@ struct SlicedMatrix {
     DevBuf<double> val, partial;
 };
 
-// Sorted sub-tiles: the sliced layout with the gathers of a tile issued in ADDRESS order.
+// Sorted fused tiles: the gathers of a tile issued in ADDRESS order, for matrices whose gathers have locality.
 // Measured (profiles/r03_gather_sorted_microbench.txt): random 8-byte gathers from an L2-resident slice cost
 // ~41 us per 16M for issue + ~48 us per 16M L1->L2 line requests; lanes of one instruction (and consecutive
 // instructions of a CU) that fall on the same 128-byte line share a request, so a tile whose entries are sorted by
 // gathered index needs only as many requests as it touches lines: 0.63 of its entries when it holds as many
-// entries as its slice has lines (72 instead of 88 us), 0.43 at two entries per line (60 us).  Layout:
-//   * row blocks of RB = 256 * RPT rows (8192 at C3), slices as in the sliced layout, every slice cut into `nsub`
-//     sub-slices; sub-tile (rb, s, h) holds the entries of the block in sub-slice h of slice s SORTED by gathered
-//     index, at most kSortedMaxSub of them;
-//   * an entry is one 32-bit word (slot << 18 | index - first index of the slice) + its value: slot = the place of
-//     the entry when the sub-tile's entries are listed row by row in storage order -- the product goes to that LDS
-//     slot, and after one barrier every thread adds up the products of its RPT consecutive rows from consecutive
-//     slots, continuing the running sums of the previous sub-tile: a row's sum is formed slice by slice in storage
-//     order exactly as in the sliced layout (bit-identical partial sums), one workgroup per (rb, s) -- few, large
-//     workgroups that stream their entries batch after batch without a barrier in between (measured: two
-//     workgroups of 1024 threads per CU that process a sub-tile in one batch between two barriers lose more to
-//     the exposed load -> gather -> stage chain than the sorted gathers win);
-//   * partial vectors and the combine kernel are the sliced layout's.
+// entries as its window has lines (72 instead of 88 us), 0.43 at two entries per line (60 us); a banded tile touches
+// a few hundred lines with thousands of entries, so almost all its gathers share requests.  Layout:
+//   * one slice = all of x; tile t holds the entries of row block t (RB = 256 * RPT rows, as many as give the chip
+//     1024 tiles; at most kSortedMaxSub entries) SORTED by gathered index;
+//   * an entry is one 32-bit word (slot << 18 | index - `xmin`, the tile's smallest index: the tile's window must span
+//     less than 2^18 entries) + its value: slot = the place of the entry when the tile's entries are listed row by
+//     row in storage order -- the product goes to that LDS slot, batch after batch without a barrier in between, and
+//     after one barrier every thread sums its RPT consecutive rows from consecutive slots;
+//   * the thread starts each row from the epilogue's initial value, adds the row's products in storage order and
+//     applies the epilogue itself -- bit-identical to the phased and fused layouts; no partial vectors, no combine.
 constexpr int kSortedThreads = 256;
-constexpr int kSortedMaxSub = 8192;    // entries per sub-tile: 13 bits of slot
-constexpr int kSortedOffBits = 18;     // index inside a slice of at most 2 MiB of x
-//   * FUSED form (one slice = all of x, one sub-tile per row block; for matrices whose gathers have locality): the
-//     gathered index is stored relative to the tile's smallest index (`xmin`, the tile's window must span less
-//     than 2^18 entries), the thread starts each row from the epilogue's initial value, adds the row's products
-//     in storage order and applies the epilogue itself -- bit-identical to the phased and fused layouts; a banded
-//     tile touches a few hundred lines with thousands of entries, so almost all its gathers share requests.
+constexpr int kSortedMaxSub = 8192;    // entries per tile: 13 bits of slot
+constexpr int kSortedOffBits = 18;     // index inside a tile's window (accumulated tiles: a slice of at most 2 MiB of x)
 struct SortedView {
-    int nrows, nrows_pad, nslices, nsub, nrb, RB, slice_elems;
-    const int* xmin;                   // FUSED: [nrb] smallest gathered index of the tile; else nullptr
-    const unsigned char* row_long;     // FUSED: rows left to the long-row kernels, or nullptr
-    const unsigned* sub_ptr;           // [nrb*nslices*nsub + 1]
-    const unsigned char* cnt;          // [nrb*nslices*nsub][RB] entries per row of the sub-tile
+    int nrows, nrows_pad, nrb, RB;
+    const int* xmin;                   // [nrb] smallest gathered index of the tile
+    const unsigned char* row_long;     // rows left to the long-row kernels, or nullptr
+    const unsigned* sub_ptr;           // [nrb + 1] first entry of each tile
+    const unsigned char* cnt;          // [nrb][RB] entries per row of the tile
     const unsigned* pack;
     const double* val;
-    double* partial;                   // [nslices][nrows_pad]
 };
 struct SortedMatrix {
     bool built = false;
-    int nslices = 0, nsub = 0, nrb = 0, RB = 0, nrows_pad = 0, max_sub = 0, slice_elems = 0;
+    int nrb = 0, RB = 0, nrows_pad = 0, max_sub = 0;
     DevBuf<unsigned> sub_ptr, pack;
     DevBuf<unsigned char> cnt;
-    DevBuf<double> val, partial;
-    bool fused = false;                // the FUSED form
+    DevBuf<double> val;
     DevBuf<int> xmin;
 };
 
@@ -337,11 +327,13 @@ struct AccMatrix {
 
 struct LayoutScratch;                 // layout_scratch.hpp
 
-// The layout of a gather matrix's unmasked products; the values are the codes ipxk_spmv_layout reports.
-enum class SpmvLayout { phased, sliced, fused, sorted, sortedfused, acc, plain, accfused };
-constexpr int kNumSpmvLayouts = 8;
-// their names (IPXK_SPMV_LAYOUT, verbose lines; ipx_amd/kkt.py uses the same)
-inline constexpr const char* kSpmvLayoutNames[kNumSpmvLayouts] = {"phased", "sliced", "fused", "sorted", "sortedfused", "acc", "plain",
+// The layout of a gather matrix's unmasked products; the values are the codes ipxk_spmv_layout reports (ABI: they do not move).
+// Code 3 was the sorted sub-tiles (docs/DESIGN_HISTORY.md), retired: no layout has it.
+enum class SpmvLayout { phased = 0, sliced = 1, fused = 2, sortedfused = 4, acc = 5, plain = 6, accfused = 7 };
+constexpr int kNumSpmvLayouts = 8;             // codes, the retired one included: tuned_us[] is indexed by code
+// their names by code (IPXK_SPMV_LAYOUT, verbose lines; ipx_amd/kkt.py uses the same); nullptr: the retired code, which every
+// loop over the table skips
+inline constexpr const char* kSpmvLayoutNames[kNumSpmvLayouts] = {"phased", "sliced", "fused", nullptr, "sortedfused", "acc", "plain",
                                                                   "accfused"};
 
 // workgroups of the combine kernel on a product of nrows rows (launch_combine, spmv_kernels.hpp), hence its dot partials.
@@ -377,7 +369,7 @@ struct GatherMatrix {
                const double* hval, hipStream_t s);
     // Builds from the plain device copy (ptr / idx 32 bits) with radix sorts on the device (layout_device.hip), every array equal
     // to the host builders'.  Long rows are taken out first (device_strip_long_rows) and the tiles built from the rest; a matrix
-    // whose x needs slicing and whose gathers spread over the slices gets the sliced, accumulated and sorted tiles, every other
+    // whose x needs slicing and whose gathers spread over the slices gets the sliced and accumulated tiles, every other
     // one -- x fits an XCD's L2, or the gathers have locality -- the fused, sorted fused and fused accumulated tiles and the plain
     // rows (build_device_local).  Returns false -- the caller then runs build() on host arrays -- for small matrices
     // (nnz < 2^16, also after the long rows are out), tune_level < 2, keep_plain, a forced layout, IPXK_LAYOUT_BUILD=host and
@@ -399,9 +391,8 @@ struct GatherMatrix {
     void select_layout(const std::function<bool(SpmvLayout)>& make, hipStream_t s);
     // XCD-sliced tiles (several slices) or fused tiles (one slice)
     SlicedMatrix sliced;
-    // the sliced layout's tiles with sorted gathers, or their FUSED form (independent of the sliced layout)
+    // sorted fused tiles (independent of the sliced layout)
     SortedMatrix sorted;
-    void build_sorted(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
     void build_sorted_fused(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s);
     // accumulated tiles (the sliced layout's slices, row sums in LDS), and their FUSED form
     AccMatrix acc;
@@ -460,7 +451,7 @@ struct GatherMatrix {
             case SpmvLayout::sortedfused: n = sorted_fused_grid(); break;
             case SpmvLayout::plain: n = plain_grid(); break;
             case SpmvLayout::accfused: n = accf.nrb; break;
-            default: n = combine_grid(); break;         // sliced, sorted, acc: the combine kernel
+            default: n = combine_grid(); break;         // sliced, acc: the combine kernel
         }
         return n + (nlong > 0 ? 1 : 0);
     }

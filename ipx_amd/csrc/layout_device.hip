@@ -3,11 +3,11 @@
 //   * a STABLE sort of the entries, enumerated in storage order, by (tile, row in tile) IS the sliced layout:
 //     tile pointers by binary search in the sorted keys, per-row byte counts from the runs of equal keys, indices
 //     and values by a gather through the sorted positions;
-//   * the sorted sub-tiles need two sorts: by (sub-tile, row) -- which numbers the slots -- and then, stably, by
-//     (sub-tile, offset in the slice): ties keep the slot order, exactly the host builder's comparator;
-//   * the accumulated tiles: one sort by (tile, offset), then the greedy batches of a tile by one wavefront.
-// Every array equals the host builder's (layout_host.hip) bit for bit (tests/test_gpu_layout.py compares them all); slices,
-// sub-slices and row blocks come from layout_geometry.hpp on both sides.  GatherMatrix::build_device (spmv.hip) drives the builders.
+//   * the accumulated tiles: one sort by (tile, offset), then the greedy batches of a tile by one wavefront;
+//   * the sorted fused tiles: the entries keep their storage order as slots (a row block's entries are contiguous), one sort
+//     by (tile, gathered index) whose ties keep the slot order, exactly the host builder's comparator.
+// Every array equals the host builder's (layout_host.hip) bit for bit (tests/test_gpu_layout.py compares them all); slices
+// and row blocks come from layout_geometry.hpp on both sides.  GatherMatrix::build_device (spmv.hip) drives the builders.
 #include <numeric>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -62,40 +62,6 @@ __global__ void sliced_keys_kernel(int nrows, const int* __restrict__ ptr, const
         }
     }
 }
-// key of the sorted layout's first sort: (sub-tile, row in row block)
-__global__ void sorted_keys1_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, int ns, int nsub, int slice,
-                                    int half, unsigned* __restrict__ key, unsigned* __restrict__ pos) {
-    IPXK_GRID_STRIDE(r, nrows) {
-        const unsigned tile0 = (unsigned)(r / RB) * (unsigned)ns, rr = (unsigned)(r % RB);
-        for (int p = ptr[r]; p < ptr[r + 1]; p++) {
-            const int sl = idx[p] / slice, off = idx[p] - sl * slice;
-            const unsigned sub = (tile0 + (unsigned)sl) * (unsigned)nsub + (unsigned)min(off / half, nsub - 1);
-            key[p] = sub * (unsigned)RB + rr;
-            pos[p] = (unsigned)p;
-        }
-    }
-}
-// second sort: (sub-tile, offset in the slice), enumerated in slot order
-__global__ void sorted_keys2_kernel(int64_t nz, const unsigned* __restrict__ key1s, const unsigned* __restrict__ perm1, const int* __restrict__ idx,
-                                    int RB, int ns, int nsub, int slice, u64* __restrict__ key2, unsigned* __restrict__ pos) {
-    IPXK_GRID_STRIDE(e, nz) {
-        const unsigned sub = key1s[e] / (unsigned)RB;
-        const int sl = (int)((sub / (unsigned)nsub) % (unsigned)ns);
-        const int off = idx[perm1[e]] - sl * slice;
-        key2[e] = ((u64)sub << kSortedOffBits) | (u64)(unsigned)off;
-        pos[e] = (unsigned)e;
-    }
-}
-__global__ void sorted_fill_kernel(int64_t nz, const u64* __restrict__ key2s, const unsigned* __restrict__ perm2, const unsigned* __restrict__ perm1,
-                                   const unsigned* __restrict__ sub_ptr, const double* __restrict__ val, unsigned* __restrict__ pack,
-                                   double* __restrict__ out_val) {
-    IPXK_GRID_STRIDE(f, nz) {
-        const u64 k = key2s[f];
-        const unsigned e = perm2[f], sub = (unsigned)(k >> kSortedOffBits), off = (unsigned)(k & ((1u << kSortedOffBits) - 1u));
-        pack[f] = ((e - sub_ptr[sub]) << kSortedOffBits) | off;
-        out_val[f] = val[perm1[e]];
-    }
-}
 // byte counts per key from the runs of equal keys (cnt is zero on entry); a run of more than 255 raises *overflow
 __global__ void run_counts_kernel(int64_t nz, const unsigned* __restrict__ sorted, unsigned char* __restrict__ cnt, int* overflow) {
     IPXK_GRID_STRIDE(e, nz) {
@@ -131,12 +97,6 @@ __global__ void tile_stats_kernel(int nrb, int ns, const unsigned* __restrict__ 
         atomicMax(out, best_tile);
         if (dom) atomicAdd(reinterpret_cast<u64*>(out + 2), dom);
     }
-}
-__global__ void max_range_kernel(int64_t count, const unsigned* __restrict__ ptr, int* out) {
-    int best = 0;
-    IPXK_GRID_STRIDE(t, count) best = max(best, (int)(ptr[t + 1] - ptr[t]));
-    best = wave_max(best);
-    if ((threadIdx.x & 63) == 0 && best > 0) atomicMax(out, best);
 }
 // ---- accumulated tiles -----------------------------------------------------------------------
 // key = (tile << 18 | offset in the slice), enumerated in storage order (a stable sort keeps that order among ties)
@@ -507,66 +467,6 @@ bool device_build_sliced(LayoutScratch& S, SlicedMatrix& out, int nrows, int nco
 }
 
 // ---------------------------------------------------------------------------
-// sorted sub-tiles (the arrays of GatherMatrix::build_sorted, bit for bit); needs the sliced layout's slices
-// ---------------------------------------------------------------------------
-bool device_build_sorted(LayoutScratch& S, SortedMatrix& out, const SlicedMatrix& sliced, int nrows, int ncols, int64_t nnz, const int* dptr,
-                         const int* didx, const double* dval, hipStream_t s) {
-    out = SortedMatrix();
-    if (!sliced.built || sliced.nslices < 2 || nnz == 0) return false;
-    const int ns = sliced.nslices;
-    const int64_t slice = slice_width(ncols, ns);
-    if (!offsets_fit(slice)) return false;
-    const SubSlices sub_slices = sub_slices_of(slice);
-    const int nsub = sub_slices.nsub;
-    const int64_t half = sub_slices.width;
-    const size_t nz = (size_t)nnz;
-    S.k1.ensure(nz); S.k2.ensure(nz); S.v1.ensure(nz); S.v2.ensure(nz); S.v3.ensure(nz); S.v4.ensure(nz); S.q1.ensure(nz); S.q2.ensure(nz);
-    S.stats.ensure(8);
-    RowBlockSearch search = sorted_rows();
-    int RB = 0, nrb = 0, max_sub = 0;
-    int64_t nsubs = 0;
-    for (;; search.next()) {
-        RB = search.rows;
-        if (search.gave_up()) return false;
-        nrb = (nrows + RB - 1) / RB;
-        nsubs = (int64_t)nrb * ns * nsub;
-        if ((u64)nsubs * (u64)RB >= (u64(1) << 32)) return false;         // device only: the first sort's key (sub-tile, row) has 32 bits
-        hipLaunchKernelGGL(sorted_keys1_kernel, dim3(gridn(nrows)), dim3(kBlock), 0, s, nrows, dptr, didx, RB, ns, nsub, (int)slice, (int)half,
-                           S.k1.get(), S.v1.get());
-        sort_pairs<unsigned>(S.T, S.k1.get(), S.k2.get(), S.v1.get(), S.v2.get(), nz, bits_for((u64)nsubs * (u64)RB - 1), s);
-        out.sub_ptr.ensure((size_t)nsubs + 1);
-        hipLaunchKernelGGL(lower_bounds_kernel<unsigned>, dim3(gridn(nsubs + 1)), dim3(kBlock), 0, s, nsubs + 1, nnz, S.k2.get(), (u64)RB, 0,
-                           out.sub_ptr.get());
-        IPXK_HIP(hipMemsetAsync(S.stats.get(), 0, 8 * sizeof(int), s));
-        hipLaunchKernelGGL(max_range_kernel, dim3(gridn(nsubs)), dim3(kBlock), 0, s, nsubs, out.sub_ptr.get(), S.stats.get());
-        IPXK_HIP(hipMemcpyAsync(&max_sub, S.stats.get(), sizeof(int), hipMemcpyDeviceToHost, s));
-        IPXK_HIP(hipStreamSynchronize(s));
-        if (search.fits(max_sub)) break;
-    }
-    const size_t nslots = (size_t)nsubs * RB;
-    out.cnt.ensure(nslots); out.pack.ensure(nz); out.val.ensure(nz);
-    IPXK_HIP(hipMemsetAsync(out.cnt.get(), 0, nslots, s));
-    IPXK_HIP(hipMemsetAsync(S.stats.get(), 0, 8 * sizeof(int), s));
-    hipLaunchKernelGGL(run_counts_kernel, dim3(gridn(nnz)), dim3(kBlock), 0, s, nnz, S.k2.get(), out.cnt.get(), S.stats.get());
-    // second sort: by (sub-tile, offset), stable on the slot order
-    hipLaunchKernelGGL(sorted_keys2_kernel, dim3(gridn(nnz)), dim3(kBlock), 0, s, nnz, S.k2.get(), S.v2.get(), didx, RB, ns, nsub, (int)slice,
-                       S.q1.get(), S.v3.get());
-    sort_pairs<u64>(S.T, S.q1.get(), S.q2.get(), S.v3.get(), S.v4.get(), nz, kSortedOffBits + bits_for((u64)nsubs - 1), s);
-    hipLaunchKernelGGL(sorted_fill_kernel, dim3(gridn(nnz)), dim3(kBlock), 0, s, nnz, S.q2.get(), S.v4.get(), S.v2.get(), out.sub_ptr.get(), dval,
-                       out.pack.get(), out.val.get());
-    int over = 0;
-    IPXK_HIP(hipMemcpyAsync(&over, S.stats.get(), sizeof(int), hipMemcpyDeviceToHost, s));
-    IPXK_HIP(hipStreamSynchronize(s));
-    IPXK_HIP(hipGetLastError());
-    if (over) { out = SortedMatrix(); return false; }
-    out.nslices = ns; out.nsub = nsub; out.nrb = nrb; out.RB = RB; out.nrows_pad = nrb * RB;
-    out.max_sub = max_sub; out.slice_elems = (int)slice;
-    out.partial.resize((size_t)ns * out.nrows_pad);
-    out.built = true;
-    return true;
-}
-
-// ---------------------------------------------------------------------------
 // accumulated tiles (the arrays of GatherMatrix::build_acc, bit for bit); needs the sliced layout's slices
 // ---------------------------------------------------------------------------
 // (layout_geometry.hpp; here because it asks the device for its CU count)
@@ -756,7 +656,7 @@ bool device_build_sorted_fused(LayoutScratch& S, SortedMatrix& out, int nrows, i
     IPXK_HIP(hipMemcpyAsync(out.xmin.get(), lo.get(), (size_t)nrb * sizeof(int), hipMemcpyDeviceToDevice, s));
     IPXK_HIP(hipStreamSynchronize(s));
     IPXK_HIP(hipGetLastError());
-    out.nslices = 1; out.nsub = 1; out.nrb = nrb; out.RB = RB; out.nrows_pad = nrb * RB; out.max_sub = h[1]; out.slice_elems = 0; out.fused = true;
+    out.nrb = nrb; out.RB = RB; out.nrows_pad = nrb * RB; out.max_sub = h[1];
     out.built = true;
     return true;
 }

@@ -1,6 +1,6 @@
 // The geometry of the tile layouts (internal.hpp), stated once.  Every layout has a host builder (layout_host.hip) and a device
 // builder (layout_device.hip) whose arrays must be equal bit for bit, and nmatrix.hip cuts N by the same rules: the number and
-// width of the slices and sub-slices, the row blocks a builder tries, and when a layout does not apply all come from here.
+// width of the slices, the row blocks a builder tries, and when a layout does not apply all come from here.
 // Plain host code, no HIP calls.  What stays with a builder is the measurement of its fullest tile (a host loop on one side, a
 // kernel and a read-back on the other) and guards that belong to one implementation only (the width of the radix keys).
 #pragma once
@@ -39,16 +39,6 @@ inline Slices model_slices(int64_t ncols, int ns_request) { return slices_of(nco
 inline bool offsets_fit(int64_t slice) { return slice <= (int64_t(1) << kSortedOffBits); }
 inline bool window_fits(int64_t span) { return span < (int64_t(1) << kSortedOffBits); }
 
-// ---- sub-slices of the sorted sub-tiles ----
-// (sub-slices per slice: 2.  Round 3, measured at C3 with IPXK_SORTED_NSUB: 4 sub-slices let the row block double at the
-// same staging buffer, i.e. twice the entries per line of the gathered window -- but the apply went 238 -> 276 us, 8 ->
-// 351 us: two more barriers, a scan and a count word per row and sub-tile cost more than the shared requests save)
-struct SubSlices { int nsub; int64_t width; };
-inline SubSlices sub_slices_of(int64_t slice) {
-    static const int nsub = [] { const char* e = getenv("IPXK_SORTED_NSUB"); return e && atoi(e) > 0 ? std::min(atoi(e), 16) : 2; }();
-    return {nsub, (slice / nsub + 15) / 16 * 16};
-}
-
 // ---- rows per tile ----
 // A builder tries `rows`, measures its fullest tile and halves until that fits; below `least` the layout is not used.
 struct RowBlockSearch {
@@ -67,7 +57,6 @@ inline RowBlockSearch sliced_rows(int nrows, int ns, bool fill_chip = true) {
     while (fill_chip && R > kBlock && row_blocks(nrows, R) * ns < 2048) R /= 2;
     return {R, kBlock, kSlicedMaxTile};
 }
-inline RowBlockSearch sorted_rows() { return {32 * kSortedThreads, 4 * kSortedThreads, kSortedMaxSub}; }
 // sorted fused tiles: enough tiles to fill the chip (IPXK_SF_MAXSUB: a smaller tile, measurements)
 inline RowBlockSearch sorted_fused_rows(int nrows) {
     static const int cap = [] { const char* e = getenv("IPXK_SF_MAXSUB"); return e && atoi(e) >= 256 ? std::min(atoi(e), kSortedMaxSub) : kSortedMaxSub; }();

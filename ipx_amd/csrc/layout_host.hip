@@ -138,7 +138,6 @@ void GatherMatrix::build(int64_t nrows_, int64_t ncols_, const ipxint* hptr, con
             case SpmvLayout::phased: return true;
             case SpmvLayout::sliced:
             case SpmvLayout::fused: build_sliced(hptr, hidx, hval, s, L == SpmvLayout::fused ? 1 : 0); return sliced.built;
-            case SpmvLayout::sorted: build_sorted(hptr, hidx, hval, s); return sorted.built;
             case SpmvLayout::sortedfused: build_sorted_fused(hptr, hidx, hval, s); return sorted.built;
             case SpmvLayout::acc: build_acc(hptr, hidx, hval, s); return acc.built;
             case SpmvLayout::accfused: build_acc_fused(hptr, hidx, hval, s); return accf.built;
@@ -239,94 +238,6 @@ void GatherMatrix::build_sliced(const ipxint* hptr, const ipxint* hidx, const do
     sliced.partial.resize(ns > 1 ? (size_t)ns * sliced.nrows_pad : 1);
     IPXK_HIP(hipStreamSynchronize(s));
     sliced.built = true;
-}
-
-// Sorted sub-tiles (internal.hpp): the slices of the sliced layout, which must exist.
-void GatherMatrix::build_sorted(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s) {
-    sorted = SortedMatrix();
-    if (!sliced.built || sliced.nslices < 2) return;
-    const int ns = sliced.nslices;
-    const int64_t slice = slice_width(ncols, ns);
-    if (!offsets_fit(slice)) return;
-    const SubSlices sub_slices = sub_slices_of(slice);
-    const int nsub = sub_slices.nsub;
-    const int64_t half = sub_slices.width;
-    const std::vector<unsigned char>& rlong = h_row_long;
-    const bool verbose = getenv("IPXK_VERBOSE") != nullptr;
-    RowBlockSearch search = sorted_rows();
-    int RB = 0, nrb = 0, max_sub = 0;
-    int64_t nsubs = 0, nshort = 0;
-    std::vector<unsigned> sptr;
-    std::vector<unsigned char> cnt;
-    for (;; search.next()) {
-        RB = search.rows;
-        if (search.gave_up()) {
-            if (verbose) fprintf(stderr, "ipxk: sorted layout not used for %d x %d: a sub-tile of %d rows holds %d entries\n", nrows, ncols, 2 * RB, max_sub);
-            return;
-        }
-        nrb = (nrows + RB - 1) / RB;
-        nsubs = (int64_t)nrb * ns * nsub;
-        sptr.assign((size_t)nsubs + 1, 0);
-        cnt.assign((size_t)nsubs * RB, 0);
-        bool ok = true;
-        for (int r = 0; r < nrows && ok; r++) {
-            if (!rlong.empty() && rlong[r]) continue;
-            const int64_t tile0 = (int64_t)(r / RB) * ns;
-            for (ipxint p = hptr[r]; p < hptr[r + 1]; p++) {
-                const int64_t sl = hidx[p] / slice, off = hidx[p] - sl * slice;
-                const int64_t sub = (tile0 + sl) * nsub + std::min<int64_t>(off / half, nsub - 1);
-                unsigned char& cc = cnt[(size_t)sub * RB + r % RB];
-                if (cc == 255) { ok = false; break; }
-                cc++;
-                sptr[sub + 1]++;
-            }
-        }
-        if (!ok) return;                 // a row with > 255 entries in one sub-slice
-        max_sub = 0;
-        for (int64_t t = 0; t < nsubs; t++) { max_sub = std::max(max_sub, (int)sptr[t + 1]); sptr[t + 1] += sptr[t]; }
-        nshort = sptr[nsubs];
-        if (search.fits(max_sub)) break;
-    }
-    if (nshort == 0) return;
-    // entries row by row (slot = place in that order), then every sub-tile sorted by gathered index
-    std::vector<unsigned> pk((size_t)nshort);
-    std::vector<double> tv((size_t)nshort);
-    {
-        std::vector<unsigned> cursor(sptr.begin(), sptr.end() - 1);
-        for (int r = 0; r < nrows; r++) {
-            if (!rlong.empty() && rlong[r]) continue;
-            const int64_t tile0 = (int64_t)(r / RB) * ns;
-            for (ipxint p = hptr[r]; p < hptr[r + 1]; p++) {
-                const int64_t sl = hidx[p] / slice, off = hidx[p] - sl * slice;
-                const int64_t sub = (tile0 + sl) * nsub + std::min<int64_t>(off / half, nsub - 1);
-                const unsigned put = cursor[sub]++;
-                pk[put] = ((put - sptr[sub]) << kSortedOffBits) | (unsigned)off;
-                tv[put] = hval[p];
-            }
-        }
-        std::vector<std::pair<unsigned, double>> tmp;
-        const unsigned mask = (1u << kSortedOffBits) - 1u;
-        for (int64_t t = 0; t < nsubs; t++) {
-            const unsigned a = sptr[t], b = sptr[t + 1];
-            if (b - a < 2) continue;
-            tmp.resize(b - a);
-            for (unsigned e = a; e < b; e++) tmp[e - a] = {pk[e], tv[e]};
-            std::sort(tmp.begin(), tmp.end(), [&](const std::pair<unsigned, double>& x, const std::pair<unsigned, double>& y) {
-                const unsigned ox = x.first & mask, oy = y.first & mask;
-                return ox != oy ? ox < oy : x.first < y.first;
-            });
-            for (unsigned e = a; e < b; e++) { pk[e] = tmp[e - a].first; tv[e] = tmp[e - a].second; }
-        }
-    }
-    sorted.nslices = ns; sorted.nsub = nsub; sorted.nrb = nrb; sorted.RB = RB; sorted.nrows_pad = nrb * RB;
-    sorted.max_sub = max_sub; sorted.slice_elems = (int)slice;
-    sorted.sub_ptr.upload(sptr, s);
-    sorted.cnt.upload(cnt, s);
-    sorted.pack.upload(pk, s);
-    sorted.val.upload(tv, s);
-    sorted.partial.resize((size_t)ns * sorted.nrows_pad);
-    IPXK_HIP(hipStreamSynchronize(s));
-    sorted.built = true;
 }
 
 namespace {
@@ -450,7 +361,7 @@ void GatherMatrix::build_acc_fused(const ipxint* hptr, const ipxint* hidx, const
     accf.built = true;
 }
 
-// FUSED sorted tiles (internal.hpp): one slice, the epilogue in the tile kernel.
+// Sorted fused tiles (internal.hpp): one slice, the epilogue in the tile kernel.
 void GatherMatrix::build_sorted_fused(const ipxint* hptr, const ipxint* hidx, const double* hval, hipStream_t s) {
     sorted = SortedMatrix();
     if (nrows == 0 || nnz == 0 || ncols == 0) return;
@@ -508,8 +419,7 @@ void GatherMatrix::build_sorted_fused(const ipxint* hptr, const ipxint* hidx, co
             tv[sptr[t] + e] = tmp[e].second.second;
         }
     }
-    sorted.nslices = 1; sorted.nsub = 1; sorted.nrb = nrb; sorted.RB = RB; sorted.nrows_pad = nrb * RB;
-    sorted.max_sub = max_sub; sorted.slice_elems = 0; sorted.fused = true;
+    sorted.nrb = nrb; sorted.RB = RB; sorted.nrows_pad = nrb * RB; sorted.max_sub = max_sub;
     sorted.sub_ptr.upload(sptr, s);
     sorted.cnt.upload(cnt, s);
     sorted.pack.upload(pk, s);

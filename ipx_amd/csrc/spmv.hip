@@ -103,9 +103,10 @@ float GatherMatrix::time_layout(SpmvLayout L, hipStream_t s) {
 //   * the sliced layout associates a row's sum per slice, hence whether it is used must not depend on a timing: it is chosen by a
 //     property of the matrix alone -- x does not fit an XCD's L2 and the gathers of a row block spread over the slices (share of
 //     its fullest slice <= 1.5 / #slices: that is where confining every XCD to one slice of x pays; measured, C3-sized: uniformly
-//     random indices 256 against 300 us per apply, banded ones 240-400 against 190-220).  Its sorted sub-tiles give bit-identical
-//     partial sums (the faster of the two is kept); the accumulated tiles give them for rows stored with ascending indices only,
-//     so they are used whenever they can be built, never by a timing.
+//     random indices 256 against 300 us per apply, banded ones 240-400 against 190-220).  The accumulated tiles give its partial
+//     sums bit for bit for rows stored with ascending indices only, so they are used whenever they can be built (the host
+//     builder refuses a matrix with long rows, the device path builds them from the matrix without its long rows;
+//     IPXK_SPMV_ACC=0: never), never by a timing: no timing takes part in the choice for such a matrix.
 // Masked products (the basis path's N N') keep the tile base whatever the choice; the arrays of the candidates that lost are
 // released unless IPXK_BUILD_ALL_LAYOUTS is set (tests: the device builders against the host builders).
 void GatherMatrix::select_layout(const std::function<bool(SpmvLayout)>& make, hipStream_t s) {
@@ -114,8 +115,8 @@ void GatherMatrix::select_layout(const std::function<bool(SpmvLayout)>& make, hi
     sliced = SlicedMatrix(); sorted = SortedMatrix(); acc = AccMatrix(); accf = AccMatrix();
     if (const char* e = getenv("IPXK_SPMV_LAYOUT")) {
         for (int f = 0; f < kNumSpmvLayouts; f++) {
-            if (strcmp(e, kSpmvLayoutNames[f]) != 0) continue;
-            if (L(f) == L::sorted || L(f) == L::acc) make(L::sliced);          // their slices
+            if (!kSpmvLayoutNames[f] || strcmp(e, kSpmvLayoutNames[f]) != 0) continue;
+            if (L(f) == L::acc) make(L::sliced);          // its slices
             layout = make(L(f)) ? L(f) : tile_base();
             return;
         }
@@ -125,7 +126,7 @@ void GatherMatrix::select_layout(const std::function<bool(SpmvLayout)>& make, hi
     const bool keep_all = getenv("IPXK_BUILD_ALL_LAYOUTS") != nullptr;
     auto drop = [&](L l) {                       // (never the tile base: the masked products use it)
         if (keep_all) return;
-        if (l == L::sorted || l == L::sortedfused) sorted = SortedMatrix();
+        if (l == L::sortedfused) sorted = SortedMatrix();
         else if (l == L::acc) acc = AccMatrix();
         else if (l == L::accfused) accf = AccMatrix();
     };
@@ -140,14 +141,7 @@ void GatherMatrix::select_layout(const std::function<bool(SpmvLayout)>& make, hi
     if (spread) {
         sliced = std::move(slicedm);
         layout = L::sliced;
-        const bool with_acc = !env_off("IPXK_SPMV_ACC") && make(L::acc);
-        // the sorted sub-tiles: the fall-back of the accumulated tiles
-        if (!env_off("IPXK_SPMV_SORTED") && (!with_acc || keep_all) && make(L::sorted)) {
-            const char* e = getenv("IPXK_SPMV_SORTED");
-            if (time_layout(L::sorted, s) < tuned_us[(int)L::sliced] || (e && e[0] == '1')) layout = L::sorted;
-            else drop(L::sorted);
-        }
-        if (with_acc) {
+        if (!env_off("IPXK_SPMV_ACC") && make(L::acc)) {
             time_layout(L::acc, s);
             layout = L::acc;
         }
@@ -172,7 +166,7 @@ void GatherMatrix::select_layout(const std::function<bool(SpmvLayout)>& make, hi
     if (getenv("IPXK_VERBOSE")) {
         fprintf(stderr, "ipxk: gather matrix %d x %d nnz %lld:", nrows, ncols, (long long)nnz);
         for (int l = 0; l < kNumSpmvLayouts; l++)
-            if (tuned_us[l] > 0.f) fprintf(stderr, " %s %.1f us,", kSpmvLayoutNames[l], tuned_us[l]);
+            if (kSpmvLayoutNames[l] && tuned_us[l] > 0.f) fprintf(stderr, " %s %.1f us,", kSpmvLayoutNames[l], tuned_us[l]);
         fprintf(stderr, " fullest-slice share %.2f -> %s\n", share, kSpmvLayoutNames[(int)layout]);
         const AccMatrix& a = layout == L::accfused ? accf : acc;
         if (a.built)
@@ -215,14 +209,13 @@ bool GatherMatrix::build_device_local(LayoutScratch& S, int64_t nrows_, int64_t 
     return true;
 }
 
-// The device path (layout_device.hip): sliced, accumulated and sorted layouts by radix sorts, for matrices whose gathered vector needs
+// The device path (layout_device.hip): sliced and accumulated layouts by radix sorts, for matrices whose gathered vector needs
 // slicing and whose gathers spread over the slices -- the same decision build() takes from the same property of the
 // matrix, so a model gets the same layouts whichever path builds them.
 bool GatherMatrix::build_device(LayoutScratch& S, int64_t nrows_, int64_t ncols_, int64_t nnz_, const int* dptr, const int* didx,
                                 const double* dval, hipStream_t s) {
     if (const char* e = getenv("IPXK_LAYOUT_BUILD")) if (e[0] == 'h') return false;           // host: the test reference
     if (const char* e = getenv("IPXK_SPMV_LAYOUT")) if (std::string(e) != "auto") return false;
-    if (env_off("IPXK_SPMV_SORTED")) return false;
     if (tune_level < 2 || keep_plain || nnz_ < (1 << 16) || getenv("IPXK_STAMPS")) return false;
     if (nrows_ >= (int64_t(1) << 31) - 1 || ncols_ >= (int64_t(1) << 31) - 1 || nnz_ >= (int64_t(1) << 31) - kLongSeg) return false;
     nlong = 0; nseg = 0;
@@ -256,12 +249,6 @@ bool GatherMatrix::build_device(LayoutScratch& S, int64_t nrows_, int64_t ncols_
                 acc = std::move(ac);
                 return true;
             }
-            case SpmvLayout::sorted: {
-                SortedMatrix so;
-                if (!device_build_sorted(S, so, sliced, nrows, ncols, nnz_, dptr, didx, dval, s)) return false;
-                sorted = std::move(so);
-                return true;
-            }
             default: return false;
         }
     }, s);
@@ -284,12 +271,10 @@ AccView GatherMatrix::acc_fused_view() const { return view_of(accf, nrows); }
 
 SortedView GatherMatrix::sorted_view() const {
     SortedView V;
-    V.xmin = sorted.fused ? sorted.xmin.get() : nullptr;
-    V.row_long = sorted.fused && nlong > 0 ? row_long.get() : nullptr;
-    V.nrows = nrows; V.nrows_pad = sorted.nrows_pad; V.nslices = sorted.nslices; V.nsub = sorted.nsub; V.nrb = sorted.nrb;
-    V.RB = sorted.RB; V.slice_elems = sorted.slice_elems;
+    V.xmin = sorted.xmin.get();
+    V.row_long = nlong > 0 ? row_long.get() : nullptr;
+    V.nrows = nrows; V.nrows_pad = sorted.nrows_pad; V.nrb = sorted.nrb; V.RB = sorted.RB;
     V.sub_ptr = sorted.sub_ptr.get(); V.cnt = sorted.cnt.get(); V.pack = sorted.pack.get(); V.val = sorted.val.get();
-    V.partial = sorted.partial.get();
     return V;
 }
 

@@ -479,125 +479,15 @@ __global__ __launch_bounds__(kBlock) void spmv_sliced_tile_kernel(SlicedView M, 
     }
 }
 
-// ---- sorted sub-tiles (internal.hpp, SortedMatrix) ---------------------------------------------
-// One workgroup of 256 threads per (row block, slice).  For every sub-tile the workgroup streams the entries in
-// batches of 2048 (packed word + value, coalesced, non-temporal, 8 per thread in flight), gathers x at ASCENDING
-// addresses (neighbouring lanes share lines: fewer L1->L2 requests than entries) and writes each product to its LDS
-// slot (the entry's place in row order) -- batch after batch without a barrier, slots are distinct; after ONE
-// barrier every thread adds the products of its RPT consecutive rows from consecutive slots to its running sums,
-// which pass from one sub-tile to the next: a row's partial sum is formed in storage order exactly as in the sliced
-// layout.  The partial sums leave through LDS so that the store is coalesced.
-template <int RPT, class Prod, bool MASKED = false>
-__global__ __launch_bounds__(kSortedThreads, kSortedThreads / 128) void spmv_sorted_tile_kernel(SortedView M, const double* __restrict__ x, const int* done) {
-    if (done && *done) return;
-    extern __shared__ double so_prod[];
-    __shared__ int wave_sum[kSortedThreads / 64];
-    static_assert(RPT == 4 || RPT == 8 || RPT == 16 || RPT == 32, "rows per thread (sliced form)");
-    constexpr int U = 8;
-    constexpr int kBatch = kSortedThreads * U;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tile = blockIdx.x, s = tile % M.nslices, rb = tile / M.nslices;
-    const double* __restrict__ xs = x + (size_t)s * M.slice_elems;
-    constexpr int RB = kSortedThreads * RPT;
-    double acc[RPT];
-#pragma unroll
-    for (int q = 0; q < RPT; q++) acc[q] = 0.0;
-    // Software pipeline over the batches of ALL sub-tiles of the tile: while the gathers of a batch are in flight,
-    // the stream loads of the next batch (of this or the next sub-tile) are issued, so that the load -> gather ->
-    // stage chain of a workgroup overlaps with itself (few, large workgroups: 8 waves per CU).
-    const int sub0 = tile * M.nsub;
-    unsigned pk[U];
-    double v[U];
-    auto stream = [&](int sub, int base) {         // (pk, v) of the batch starting at `base` of sub-tile `sub`
-        const unsigned e0 = M.sub_ptr[sub];
-        const int ne = (int)(M.sub_ptr[sub + 1] - e0);
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int i = min(base + u * kSortedThreads + tid, max(ne - 1, 0));
-            pk[u] = __builtin_nontemporal_load(M.pack + e0 + i);
-            v[u] = __builtin_nontemporal_load(M.val + e0 + i);
-        }
-    };
-    stream(sub0, 0);
-    for (int h = 0; h < M.nsub; h++) {
-        const int sub = sub0 + h;
-        const int ne = (int)(M.sub_ptr[sub + 1] - M.sub_ptr[sub]);
-        // my RPT row counts: RPT bytes (16-byte loads)
-        unsigned cw[RPT / 4];
-        {
-            const unsigned* cbase = reinterpret_cast<const unsigned*>(M.cnt + (size_t)sub * RB) + (size_t)tid * (RPT / 4);
-#pragma unroll
-            for (int q = 0; q < RPT / 4; q++) cw[q] = cbase[q];
-        }
-        for (int base = 0; base < ne || base == 0; base += kBatch) {
-            double xg[U];
-            unsigned slot[U];
-            double vv[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const unsigned off = pk[u] & ((1u << kSortedOffBits) - 1u);
-                slot[u] = pk[u] >> kSortedOffBits;
-                vv[u] = v[u];
-                if (MASKED) xg[u] = v[u] != 0.0 ? xs[off] : 0.0;
-                else xg[u] = xs[off];
-            }
-            // next batch: of this sub-tile, else the first one of the next sub-tile
-            if (base + kBatch < ne) stream(sub, base + kBatch);
-            else if (h + 1 < M.nsub) stream(sub + 1, 0);
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int i = base + u * kSortedThreads + tid;
-                if (i < ne) so_prod[lds_slot((int)slot[u])] = Prod::prod(xg[u], vv[u]);
-            }
-        }
-        // first slot of my rows: exclusive scan of the per-thread entry counts over the workgroup
-        int mine = 0;
-#pragma unroll
-        for (int q = 0; q < RPT / 4; q++) mine += (int)((cw[q] & 255u) + ((cw[q] >> 8) & 255u) + ((cw[q] >> 16) & 255u) + (cw[q] >> 24));
-        int incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int nb = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += nb;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        int p = incl - mine;
-        for (int w = 0; w < wave; w++) p += wave_sum[w];
-        // first product of every row with independent LDS reads, the rest of a row (rare) one by one
-        double first[RPT];
-        int p0[RPT];
-#pragma unroll
-        for (int q = 0; q < RPT; q++) {
-            const int cq = (int)((cw[q / 4] >> (8 * (q & 3))) & 255u);
-            p0[q] = p;
-            first[q] = cq > 0 ? so_prod[lds_slot(p)] : 0.0;
-            p += cq;
-        }
-#pragma unroll
-        for (int q = 0; q < RPT; q++) {
-            const int cq = (int)((cw[q / 4] >> (8 * (q & 3))) & 255u);
-            if (cq > 0) acc[q] += first[q];
-            for (int kk = 1; kk < cq; kk++) acc[q] += so_prod[lds_slot(p0[q] + kk)];
-        }
-        __syncthreads();                  // the staging buffer and wave_sum are reused by the next sub-tile
-    }
-    // coalesced store of the RB partial sums: through LDS (thread t holds rows t*RPT .. t*RPT + RPT - 1)
-#pragma unroll
-    for (int q = 0; q < RPT; q++) so_prod[lds_slot(tid * RPT + q)] = acc[q];
-    __syncthreads();
-    double* dst = M.partial + (size_t)s * M.nrows_pad + (size_t)rb * RB;
-#pragma unroll
-    for (int q = 0; q < RPT; q += 2) {
-        const int r = (q / 2) * (2 * kSortedThreads) + 2 * tid;
-        reinterpret_cast<double2*>(dst + r)[0] = make_double2(so_prod[lds_slot(r)], so_prod[lds_slot(r + 1)]);
-    }
-}
-
-// The FUSED form: one slice, one sub-tile per row block, gathered indices relative to the tile's smallest one; the
-// thread starts each row from epi.init, adds the row's products in storage order (the reference's order, bit for
-// bit as in the phased and fused layouts) and applies epi.finish itself.  A workgroup walks tiles blockIdx.x,
-// blockIdx.x + gridDim.x, ...; its dot partial goes to dot_partials[blockIdx.x].
+// ---- sorted fused tiles (internal.hpp, SortedMatrix) -------------------------------------------
+// One workgroup of 256 threads walks tiles (row blocks) blockIdx.x, blockIdx.x + gridDim.x, ...  It streams a tile's entries in
+// batches of 2048 (packed word + value, coalesced, non-temporal, 8 per thread in flight; the next batch's loads -- of this or
+// the workgroup's next tile -- are issued while the gathers of the current one return), gathers x at ASCENDING addresses
+// relative to the tile's smallest index (neighbouring lanes share lines: fewer L1->L2 requests than entries) and writes each
+// product to its LDS slot (the entry's place in row order) -- batch after batch without a barrier, slots are distinct.  After
+// ONE barrier the thread starts each of its RPT consecutive rows from epi.init, adds the row's products from consecutive
+// slots in storage order (the reference's order, bit for bit as in the phased and fused layouts) and applies epi.finish
+// itself.  The workgroup's dot partial goes to dot_partials[blockIdx.x].
 template <class Epi, int RPT>
 __global__ __launch_bounds__(kSortedThreads, kSortedThreads / 128) void spmv_sorted_fused_kernel(SortedView M, const double* __restrict__ x, Epi epi,
                                                                                            double* dot_partials, const int* done) {
@@ -706,21 +596,30 @@ __global__ __launch_bounds__(kSortedThreads, kSortedThreads / 128) void spmv_sor
 }
 
 // ---- accumulated tiles (internal.hpp, AccMatrix) -----------------------------------------------
-// One workgroup of 512 threads per (row block, slice); the RB row sums live in LDS.  Batch after batch (at most 2048
+// One workgroup of 512 threads per tile; the RB row sums live in LDS.  Batch after batch (at most 2048
 // entries, 4 per thread): packed word + value streamed non-temporally, x gathered at ascending addresses (neighbouring
 // lanes share lines), one barrier, one ds_add_f64 per entry -- the layout guarantees that a batch holds at most one
 // entry of a row, so the adds of a batch hit distinct addresses and a row is summed in batch order.  The stream loads
-// of batch k+1 are in flight while the gathers of batch k return.  The row sums leave as one partial vector per slice.
-template <class Prod>
-__global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, const double* __restrict__ x, const int* done) {
-    if (done && *done) return;
+// of batch k+1 are in flight while the gathers of batch k return.
+//
+// The pipeline of the two one-tile kernels below (the sliced form, one tile per (row block, slice), and the FUSED form): the
+// batches [b0, b0 + nb) of a tile, gathered from xs (the slice's, or the tile window's, first element of x), added to
+// ac_sum[0 .. M.RB), which starts from init(row in the tile); NEG: the products are subtracted.  On return every add is done
+// and a barrier has passed.
+struct AccRowsFromZero {
+    __device__ double operator()(int) const { return 0.0; }
+};
+template <class Epi>
+struct AccRowsFromEpi {             // rows r0 .. of the product start from the epilogue's value (padding rows: 0)
+    const Epi& epi;
+    int r0, nrows;
+    __device__ double operator()(int r) const { return r0 + r < nrows ? epi.init(r0 + r) : 0.0; }
+};
+template <class Prod, bool NEG, class Init>
+__device__ __forceinline__ void acc_tile_pipeline(const AccView& M, const double* __restrict__ xs, unsigned b0, int nb, Init init) {
     extern __shared__ double ac_sum[];
     constexpr int U = kAccPerThread, T = kAccThreads;
     const int tid = threadIdx.x;
-    const int tile = blockIdx.x, s = tile % M.nslices, rb = tile / M.nslices;
-    const double* __restrict__ xs = x + (size_t)s * M.slice_elems;
-    const unsigned b0 = M.tile_batch[tile];
-    const int nb = (int)(M.tile_batch[tile + 1] - b0);
     // first entry of batch k of this tile (wave-uniform: scalar loads), fetched well ahead of its use
     auto first = [&](int k) -> unsigned { return M.bptr[b0 + min(k, nb)]; };
     constexpr int NE = 6;
@@ -753,7 +652,8 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, c
         for (int u = 0; u < U; u++) { pk[d][u] = 0u; v[d][u] = 0.0; }
         stream(pk[d], v[d], e[d], e[d + 1]);
     }
-    for (int r = tid; r < M.RB; r += T) ac_sum[r] = 0.0;
+    // (the rows are started here, behind the prologue's stream loads and in front of the first gather, which waits for them)
+    for (int r = tid; r < M.RB; r += T) ac_sum[r] = init(r);
     if (nb > 0) gather(xg[0], pk[0]);
     for (int k0 = 0; k0 < nb; k0 += 6) {
 #pragma unroll
@@ -763,13 +663,14 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, c
                 const int ne = (int)(e[1] - e[0]);
                 if (k + 1 < nb) gather(xg[(d + 1) & 1], pk[(d + 1) % 3]);          // batch k + 1
                 const unsigned enew = first(k + NE);
-                __syncthreads();                  // the adds of the previous batch (first batch: the zeroing) are done
+                __syncthreads();                  // the adds of the previous batch (first batch: the rows' start values) are done
                 // (a plain read-modify-write -- the rows of a batch are distinct -- measured 3 % slower than ds_add_f64)
 #pragma unroll
                 for (int u = 0; u < U; u++)
-                    if (u * T + tid < ne)
-                        __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), Prod::prod(xg[d & 1][u], v[d % 3][u]), __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (u * T + tid < ne) {
+                        const double p = Prod::prod(xg[d & 1][u], v[d % 3][u]);
+                        __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), NEG ? -p : p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
                 stream(pk[d % 3], v[d % 3], e[3], e[4]);               // batch k + 3 into the buffer just emptied
 #pragma unroll
                 for (int i = 0; i + 1 < NE; i++) e[i] = e[i + 1];
@@ -778,6 +679,19 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, c
         }
     }
     __syncthreads();
+}
+
+// The sliced form: tile (row block rb, slice s); the row sums start from zero and leave as one partial vector per slice.
+template <class Prod>
+__global__ __launch_bounds__(kAccThreads) void spmv_acc_tile_kernel(AccView M, const double* __restrict__ x, const int* done) {
+    if (done && *done) return;
+    extern __shared__ double ac_sum[];
+    constexpr int T = kAccThreads;
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x, s = tile % M.nslices, rb = tile / M.nslices;
+    const double* __restrict__ xs = x + (size_t)s * M.slice_elems;
+    const unsigned b0 = M.tile_batch[tile];
+    acc_tile_pipeline<Prod, false>(M, xs, b0, (int)(M.tile_batch[tile + 1] - b0), AccRowsFromZero{});
     double* dst = M.partial + (size_t)s * M.nrows_pad + (size_t)rb * M.RB;
     for (int r = 2 * tid; r < M.RB; r += 2 * T) reinterpret_cast<double2*>(dst + r)[0] = make_double2(ac_sum[r], ac_sum[r + 1]);
 }
@@ -1009,74 +923,21 @@ __global__ __launch_bounds__(kBlock) void spmv_rowgroup_kernel(int nrows, const 
 }
 
 // The FUSED form: one slice, a tile per row block, gathered indices relative to the tile's smallest one; the row sums
-// start from epi.init, the products are added batch by batch (ascending address = storage order of sorted rows) and the
-// kernel applies epi.finish itself; the tile's dot partial goes to dot_partials[tile].  The pipeline is the sliced
-// form's: adds of batch k, gathers of k + 1, stream loads of k + 2 and k + 3 in flight.
+// start from epi.init, the products are added batch by batch (ascending address = storage order of sorted rows) by
+// acc_tile_pipeline and the kernel applies epi.finish itself; the tile's dot partial goes to dot_partials[tile].
 template <class Epi>
 __global__ __launch_bounds__(kAccThreads) void spmv_acc_fused_kernel(AccView M, const double* __restrict__ x, Epi epi, double* dot_partials,
                                                                      const int* done) {
     if (done && *done) return;
     extern __shared__ double ac_sum[];
     __shared__ double red[kAccThreads / 64];
-    constexpr int U = kAccPerThread, T = kAccThreads;
+    constexpr int T = kAccThreads;
     const int tid = threadIdx.x;
     const int tile = blockIdx.x;
     const double* __restrict__ xs = x + M.xmin[tile];
     const unsigned b0 = M.tile_batch[tile];
-    const int nb = (int)(M.tile_batch[tile + 1] - b0);
-    auto first = [&](int k) -> unsigned { return M.bptr[b0 + min(k, nb)]; };
-    constexpr int NE = 6;
-    unsigned e[NE];
-#pragma unroll
-    for (int i = 0; i < NE; i++) e[i] = first(i);
-    unsigned pk[3][U];
-    double v[3][U], xg[2][U];
-    auto stream = [&](unsigned (&pkb)[U], double (&vb)[U], unsigned e0, unsigned e1) {
-        const int ne = (int)(e1 - e0);
-        if (ne <= 0) return;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int i = min(u * T + tid, ne - 1);
-            pkb[u] = __builtin_nontemporal_load(M.pack + e0 + i);
-            vb[u] = __builtin_nontemporal_load(M.val + e0 + i);
-        }
-    };
-    auto gather = [&](double (&xgb)[U], const unsigned (&pkb)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; u++) xgb[u] = xs[pkb[u] & ((1u << kSortedOffBits) - 1u)];
-    };
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-#pragma unroll
-        for (int u = 0; u < U; u++) { pk[d][u] = 0u; v[d][u] = 0.0; }
-        stream(pk[d], v[d], e[d], e[d + 1]);
-    }
     const int r0 = tile * M.RB;
-    for (int r = tid; r < M.RB; r += T) ac_sum[r] = r0 + r < M.nrows ? epi.init(r0 + r) : 0.0;
-    if (nb > 0) gather(xg[0], pk[0]);
-    for (int k0 = 0; k0 < nb; k0 += 6) {
-#pragma unroll
-        for (int d = 0; d < 6; d++) {
-            const int k = k0 + d;
-            if (k < nb) {
-                const int ne = (int)(e[1] - e[0]);
-                if (k + 1 < nb) gather(xg[(d + 1) & 1], pk[(d + 1) % 3]);
-                const unsigned enew = first(k + NE);
-                __syncthreads();
-#pragma unroll
-                for (int u = 0; u < U; u++)
-                    if (u * T + tid < ne) {
-                        const double p = Epi::prod(xg[d & 1][u], v[d % 3][u]);
-                        __hip_atomic_fetch_add(ac_sum + (pk[d % 3][u] >> kSortedOffBits), Epi::kNeg ? -p : p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                stream(pk[d % 3], v[d % 3], e[3], e[4]);
-#pragma unroll
-                for (int i = 0; i + 1 < NE; i++) e[i] = e[i + 1];
-                e[NE - 1] = enew;
-            }
-        }
-    }
-    __syncthreads();
+    acc_tile_pipeline<Epi, Epi::kNeg>(M, xs, b0, (int)(M.tile_batch[tile + 1] - b0), AccRowsFromEpi<Epi>{epi, r0, M.nrows});
     double dotpart = 0.0;
     for (int r = tid; r < M.RB; r += T)
         if (r0 + r < M.nrows) epi.finish(r0 + r, ac_sum[r], dotpart);
@@ -1315,7 +1176,6 @@ inline int launch_spmv(const GatherMatrix& M, const double* x, const Epi& epi, d
         }
         case SpmvLayout::sliced:
         case SpmvLayout::fused:
-        case SpmvLayout::sorted:        // (runs the sliced layout's kernels)
             if (MASKED && M.compact.valid) launch_spmv_sliced<Epi, false, true>(M, x, epi, dot_partials, done, s);
             else launch_spmv_sliced<Epi, MASKED>(M, x, epi, dot_partials, done, s);
             break;

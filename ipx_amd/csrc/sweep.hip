@@ -164,7 +164,7 @@ __device__ __forceinline__ double ordered_combine(double acc, double prod, int c
     return acc;
 }
 
-// A MERGED chunk (trisolve.hpp): `nsub` consecutive tiny levels in one chunk.  The dependencies outside the
+// A MERGED chunk (trisolve.hpp): `sub` consecutive tiny levels in one chunk.  The dependencies outside the
 // chunk have been polled (bits); the wavefront runs the levels in order, every lane recomputes its row in every
 // round and keeps the value of the round that is its own level -- by then all its dependencies inside the chunk
 // (rows of earlier levels: other lanes of this wavefront) hold their results, which travel by lane shuffles.

@@ -321,11 +321,12 @@ class KktContext:
         return ("none", "rccl", "direct")[t.value], n.value, r.value
 
     def spmv_layout(self):
-        """(layout of A'y, layout of A t), each one of 'phased', 'sliced', 'fused', 'sorted', 'sortedfused', 'acc', 'plain',
-        'accfused', and the build-time timings in us."""
+        """(layout of A'y, layout of A t), each one of 'phased', 'sliced', 'fused', 'sortedfused', 'acc', 'plain', 'accfused',
+        and the build-time timings in us."""
         lay = (C.c_int * 2)()
         us = (C.c_double * 6)()
         self._check(self.lib.ipxk_spmv_layout(self.h, lay, us))
+        # by layout code; code 3 (the sorted sub-tiles) is retired: a placeholder that no context reports
         names = ("phased", "sliced", "fused", "sorted", "sortedfused", "acc", "plain", "accfused")
         return (names[lay[0]], names[lay[1]]), [float(v) for v in us]
 
@@ -344,12 +345,13 @@ class KktContext:
         info = (C.c_int64 * 48)()
         ms = (C.c_double * 4)()
         self._check(self.lib.ipxk_layout_info(self.h, which, info, ms))
-        keys = ("use_sliced", "use_sorted", "use_sorted_fused", "nlong", "sliced_built", "R", "nslices", "nrb", "nrows_pad",
-                "max_tile", "dominant_bits", "sorted_built", "so_nslices", "so_nsub", "so_nrb", "so_RB", "so_nrows_pad",
-                "so_max_sub", "so_slice_elems", "so_fused", "nnz", "P", "G", "RTQ", "use_acc", "acc_built", "acc_nslices", "acc_nrb",
+        # by slot; None: a retired slot (the sorted sub-tiles' scalars, always 0), left out of the result
+        keys = ("use_sliced", None, "use_sorted_fused", "nlong", "sliced_built", "R", "nslices", "nrb", "nrows_pad",
+                "max_tile", "dominant_bits", "sorted_built", None, None, "so_nrb", "so_RB", "so_nrows_pad",
+                "so_max_sub", None, None, "nnz", "P", "G", "RTQ", "use_acc", "acc_built", "acc_nslices", "acc_nrb",
                 "acc_RB", "acc_nrows_pad", "acc_slice_elems", "acc_nbatches", "acc_deferred", "use_acc_fused", "accf_built", "accf_nrb", "accf_RB",
                 "accf_nbatches", "use_plain", "acc_nsteps", "acc_wide_units")
-        d = {k: int(v) for k, v in zip(keys, info)}
+        d = {k: int(v) for k, v in zip(keys, info) if k is not None}
         d["dominant_fraction"] = float(np.array([d.pop("dominant_bits")], dtype=np.int64).view(np.float64)[0])
         return d, [float(v) for v in ms]
 

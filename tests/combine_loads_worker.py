@@ -16,7 +16,7 @@ from ipx_amd import kkt, synth  # noqa: E402
 
 # m, n, seed, IPXK_SLICE_TEST_KB, IPXK_SLICE_FORCE2
 SHAPES = ((9000, 20011, 1, "16", False), (20000, 45000, 2, "128", True), (33333, 70001, 3, "128", False))
-SLICE_KEY = {"acc": "acc_nslices", "sliced": "nslices", "sorted": "so_nslices"}
+SLICE_KEY = {"acc": "acc_nslices", "sliced": "nslices"}
 
 
 def record_layout(out, tag, ctx):

@@ -1,11 +1,11 @@
-"""GPU: the combine kernel of the sliced, sorted and accumulated layouts with a row group's loads issued before the first
+"""GPU: the combine kernel of the sliced and accumulated layouts with a row group's loads issued before the first
 add (the default) against the form before (IPXK_COMBINE_EARLY=0: per row the flag, the epilogue's inputs and one partial
 sum after the other, each waited for), bit for bit.  Only the order of the loads differs -- the slices of a row are added
 in ascending order, a thread's rows contribute to its dot partial in ascending order, the grid and the thread-to-row map
 are the same -- so every product, every dot and everything a solve returns must be equal, not close.  The setting is read
 once per process: each form runs in a process of its own (tests/combine_loads_worker.py) and leaves an .npz behind.
 
-Legs: IPXK_SPMV_LAYOUT = acc, sliced, sorted (the three that end in the combine kernel; without the accumulated tiles
+Legs: IPXK_SPMV_LAYOUT = acc, sliced (the two that end in the combine kernel; without the accumulated tiles
 the N N' products of the basis path take nmatrix.hip's sliced tiles), each on the kernel's own grid -- at most one row per
 thread at these sizes, so a group with one live row and clamped loads for the rest -- and with IPXK_COMBINE_GRID=4: a
 thread owns 8 to 9 rows of the 9000-row product and up to 69 of the largest, full groups and a ragged last one, some
@@ -85,12 +85,12 @@ def library():
     kkt.load_library()
 
 
-@pytest.mark.parametrize("layout", ("acc", "sliced", "sorted"))
+@pytest.mark.parametrize("layout", ("acc", "sliced"))
 def test_one_group_per_thread(library, tmp_path, layout):
     check(tmp_path, layout, {})
 
 
-@pytest.mark.parametrize("layout", ("acc", "sliced", "sorted"))
+@pytest.mark.parametrize("layout", ("acc", "sliced"))
 def test_several_groups_per_thread(library, tmp_path, layout):
     check(tmp_path, layout, {"IPXK_COMBINE_GRID": "4"})
 

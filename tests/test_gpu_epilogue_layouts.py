@@ -7,8 +7,8 @@ holds every entry of every output to the derived gate of the reference,
     |device - long double| <= (len_r + c_epi + 2) * 2^-53 * S_r,
 
 and, where the layout keeps the storage order (phased, fused, sortedfused, accfused, plain), rows of at most 255 entries to
-the sequential double value bit for bit (long rows are summed by segments and get the gate only).  `sorted` and `acc` must
-reproduce `sliced` bit for bit: their rows are stored with ascending indices.
+the sequential double value bit for bit (long rows are summed by segments and get the gate only).  `acc` must reproduce
+`sliced` bit for bit: the rows are stored with ascending indices.
 
 What runs per case (the reference's inputs are the call's own returned vectors, so the check sits at the kernel boundary):
   EpiIterRb, EpiIterRc        iterate_residuals, before and after iterate_postprocess (both branches of EpiIterRc)
@@ -40,19 +40,19 @@ return at nlong > 0), so the long-row model runs under every other layout.
 Worst error / gate per epilogue and layout, over all models, from the run on an MI355X (0 = equal to the long-double value
 rounded; the ordered layouts are also bit-equal to the sequential value):
 
-  output              default      phased       fused      sliced      sorted         acc sortedfused    accfused       plain
-  rb                    0.265       0.265       0.265       0.265       0.265       0.265       0.119       0.119       0.265
-  rc                    0.198       0.198       0.198       0.155       0.155       0.155       0.137       0.137       0.198
-  rb post               0.265       0.265       0.265       0.265       0.265       0.265       0.119       0.119       0.265
-  rc post               0.198       0.198       0.198       0.155       0.155       0.155       0.137       0.137       0.198
-  diagonal              0.277       0.277       0.277       0.277       0.277       0.277       0.224       0.224       0.277
-  x                     0.243       0.243       0.231       0.288       0.288       0.256       0.164       0.163       0.248
-  x slack               0.190       0.190       0.290       0.169       0.169       0.169       0.119       0.108       0.211
-  dzl                   0.225       0.225       0.234       0.232       0.232       0.232       0.181       0.242       0.222
-  dzu                   0.260       0.260       0.214       0.195       0.195       0.195       0.151       0.193       0.235
-  rb partitioned        0.265       0.265       0.265       0.265       0.265       0.265       0.119       0.119       0.265
-  dobjective          0.00010     0.00010     0.00023     0.00006     0.00006     0.00006     0.00001     0.00005     0.00010
-  x nonbasic            0.167       0.167       0.167       0.185       0.185       0.185           -           -       0.167
+  output              default      phased       fused      sliced         acc sortedfused    accfused       plain
+  rb                    0.265       0.265       0.265       0.265       0.265       0.119       0.119       0.265
+  rc                    0.198       0.198       0.198       0.155       0.155       0.137       0.137       0.198
+  rb post               0.265       0.265       0.265       0.265       0.265       0.119       0.119       0.265
+  rc post               0.198       0.198       0.198       0.155       0.155       0.137       0.137       0.198
+  diagonal              0.277       0.277       0.277       0.277       0.277       0.224       0.224       0.277
+  x                     0.243       0.243       0.231       0.288       0.256       0.164       0.163       0.248
+  x slack               0.190       0.190       0.290       0.169       0.169       0.119       0.108       0.211
+  dzl                   0.225       0.225       0.234       0.232       0.232       0.181       0.242       0.222
+  dzu                   0.260       0.260       0.214       0.195       0.195       0.151       0.193       0.235
+  rb partitioned        0.265       0.265       0.265       0.265       0.265       0.119       0.119       0.265
+  dobjective          0.00010     0.00010     0.00023     0.00006     0.00006     0.00001     0.00005     0.00010
+  x nonbasic            0.167       0.167       0.167       0.185       0.185           -           -       0.167
 
 (`acc` has no long-row model, `sortedfused` and `accfused` run on the banded model only, hence their smaller maxima; the
 inputs of x, x slack, dzl and dzu are each call's own returned y or dy, which differ between layouts by the CR loop's
@@ -69,12 +69,12 @@ from helpers import basis_problem
 pytestmark = pytest.mark.gpu
 LD = np.longdouble
 ORDERED = ("phased", "fused", "sortedfused", "accfused", "plain")
-SLICED = ("sliced", "sorted", "acc")
+SLICED = ("sliced", "acc")
 # slices of (the vector Acols gathers: m entries, the vector Arows gathers: n entries)
 SLICES = {"mixed": (4, 8), "square": (2, 4), "wide": (8, 8), "long": (4, 8)}
 assert {s for pair in SLICES.values() for s in pair} == {2, 4, 8}
 NLONG = {"long": (3, 1)}
-GENERAL = [None, "phased", "fused", "sliced", "sorted", "acc", "plain"]
+GENERAL = [None, "phased", "fused", "sliced", "acc", "plain"]
 CASES = ([(mdl, lay) for mdl in ("mixed", "square", "wide") for lay in GENERAL]
          + [("long", lay) for lay in GENERAL if lay != "acc"]
          + [("banded", "sortedfused"), ("banded", "accfused")])
@@ -122,7 +122,7 @@ def check_layout(ctx, name, layout):
     infos = [ctx.layout_info(w)[0] for w in (0, 1)]
     assert tuple(i["nlong"] for i in infos) == NLONG.get(name, (0, 0))
     if layout in SLICED:
-        key = {"sliced": "nslices", "sorted": "so_nslices", "acc": "acc_nslices"}[layout]
+        key = {"sliced": "nslices", "acc": "acc_nslices"}[layout]
         assert tuple(i[key] for i in infos) == SLICES[name], (name, layout, [i[key] for i in infos])
     return used
 
@@ -243,7 +243,7 @@ def test_epilogues(kkt, name, layout):
     worst = float(abs(LD(dot_dev) - dot.ld) / dot.gate)
     print("%-8s %-12s %-15s worst error / gate %.5f (value %.6e)" % (name, layout or "default", "dobjective", worst, dot_dev))
     assert dot_dev != 0.0 and worst <= 1.0, (name, layout, "dobjective", worst)
-    if layout in ("sorted", "acc"):
+    if layout == "acc":
         ref, (ref_dot, _) = run_case(kkt, name, "sliced")
         for what, entry in out.items():
             assert np.array_equal(entry[0], ref[what][0]), (name, layout, what)
@@ -278,7 +278,7 @@ def run_basis(kkt, name, layout):
 def test_basis_epilogues(kkt, name, layout):
     x, y, entry = run_basis(kkt, name, layout)
     hold(name, layout, "x nonbasic", entry, {})
-    if layout in ("sorted", "acc"):
+    if layout == "acc":
         xs, ys, _ = run_basis(kkt, name, "sliced")
         assert np.array_equal(x, xs) and np.array_equal(y, ys)
 
