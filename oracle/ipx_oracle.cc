@@ -2063,9 +2063,14 @@ extern "C" Int orc_basis_exchange_if_stable(orc_basis* B, Int jb, Int jn, double
 // log (may be NULL, capacity log_cap pairs): the accepted exchanges (jb, jn) in order.
 // Maxvolume::RunSequential (src/maxvolume.cc:14-106), selected by update_heuristic == 0 (src/kkt_solver_basis.cc:47-51):
 // passes over the columns in decreasing order of their scaling factor; for every NONBASIC candidate the tableau column
-// (SolveForUpdate), the largest scaled entry v = |x_p| * invscale_basic[p] * d_j (first position on ties: the
-// reference's for_each_nonzero order is the pattern order of its IndexedVector, an LU detail -- ties are measure zero);
-// an exchange if v > max(volume_tol, 1).  ExchangeIfStable is called with sys = -1 (src/maxvolume.cc:83): the
+// (SolveForUpdate), the largest scaled entry v = |x_p| * invscale_basic[p] * d_j (first position on ties);
+// an exchange if v > max(volume_tol, 1).
+// CAVEAT on ties, here and in ScaleFtran of the heuristic below: the reference visits a SPARSE tableau column in the pattern
+// order of its IndexedVector (for_each_nonzero), an LU detail, so at an exact tie the reference itself may pick another
+// position than the first.  Ties are not measure zero on real LPs (+-1 coefficients, equal scaling factors, duplicated
+// columns).  The contract that is pinned is device = this restatement, which takes the FIRST strictly larger entry in
+// position order (tests/test_gpu_basis_ties.py on exact dyadic data); FindLargest's loop over the columns is in index order
+// in the reference too.  ExchangeIfStable is called with sys = -1 (src/maxvolume.cc:83): the
 // reference computes the BTRAN of the leaving variable for its LU update there; here the same BTRAN yields the pivot
 // from the row, compared with the pivot from the column (exchange_if_stable above).
 // info[8] = updates, skipped, passes, volinc, refused, errflag, tblnnz of the last pass, tblmax of the last pass.
