@@ -190,14 +190,15 @@ int ipxk_diag_get(const ipxk_context* ctx, double* diagonal, double* chol);
  * interrupt (may be NULL) plays Control::InterruptCheck()
  * (src/control.cc:17-22): a nonzero return value stops the solve and becomes
  * *errflag.  Granularity: the reference polls after every iteration
- * (src/conjugate_residuals.cc:209); here the callback is polled once per cycle
- * of 5 iterations that the host enqueues, first after the first cycle (a
+ * (src/conjugate_residuals.cc:209); here the callback is polled once per 5
+ * iterations that the host enqueues, first after the first five (a
  * system whose initial residual meets tol returns errflag 0 whatever the
- * callback says, like the reference), and the host runs up to 2 cycles ahead
- * of the device: *iter is the last iteration that finished, up to 15
- * iterations after the callback first returned nonzero.  On a partitioned
- * system the flag is reduced (max) over the ranks together with the loop's
- * `done` snapshot, so every rank leaves the loop in the same cycle.
+ * callback says, like the reference).  What is in the queue is finished:
+ * *iter is the number of iterations enqueued when the callback returned
+ * nonzero.  On a partitioned system the host runs up to 2 cycles of 5
+ * iterations ahead and the flag is reduced (max) over the ranks together
+ * with the loop's `done` snapshot, so every rank leaves the loop in the
+ * same cycle, up to 15 iterations after the callback first returned nonzero.
  * resnorm_hist (may be NULL): termination-test residual norm of each pass
  * through the loop head, at most hist_cap entries (always a host pointer). */
 typedef ipxint (*ipxk_interrupt_fn)(void* user);
@@ -209,6 +210,14 @@ int ipxk_pcr_solve(ipxk_context* ctx, const double* rhs, double tol,
 
 /* numbers of the last CR run (any of ipxk_pcr_solve, ipxk_cr_solve, the KKT solves) */
 int ipxk_cr_diagnostics(ipxk_context* ctx, ipxk_cr_diag* out);
+/* what the last CR run put into the queue, counted on the host: out[0] iterations enqueued, out[1] launches of the
+ * loop's own kernels (control, direction, the diagonal preconditioner, initialisation and tail; the kernels of the
+ * operator and of the dense-column preconditioner are not counted), out[2] launches that hand a snapshot of `done`
+ * to the host, out[3] events recorded inside the loop.  On a single GPU the host follows a progress word the
+ * direction kernel stores: out[2] = out[3] = 0 and out[0] <= *iter + 1 + R with R the run-ahead (3 iterations;
+ * IPXK_CR_AHEAD).  IPXK_CR_PACE=cycles selects the driver that partitioned systems keep: cycles of 5 iterations,
+ * one snapshot and one event each. */
+int ipxk_cr_loop_stats(ipxk_context* ctx, ipxint out[4]);
 
 /* ---- KKTSolverDiag (src/kkt_solver_diag.h:23-49) ------------------------- */
 /* _Factorize (src/kkt_solver_diag.cc:18-65).  xl == NULL is Factorize(nullptr)

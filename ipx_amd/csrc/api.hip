@@ -1083,6 +1083,13 @@ int ipxk_cr_diagnostics(ipxk_context* c, ipxk_cr_diag* out) {
     });
 }
 
+int ipxk_cr_loop_stats(ipxk_context* c, ipxint out[4]) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && out, "NULL argument");
+        cr_loop_stats_dev(c, out);
+    });
+}
+
 int ipxk_split_rescale(ipxk_context* c, const ipxint* status, const double* colscale) {
     return guarded([&] {
         IPXK_REQUIRE(c && status && colscale, "NULL argument");

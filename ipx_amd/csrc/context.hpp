@@ -112,6 +112,9 @@ struct Context {
     DevBuf<double> hist;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
     std::vector<hipEvent_t> ev_window;
+    // what the last CR run enqueued (ipxk_cr_loop_stats): iterations, kernel launches of the loop's own kernels,
+    // snapshot launches, events recorded inside the loop
+    long long cr_loop_stats[4] = {0, 0, 0, 0};
 
     // ---- KKTSolverDiag ----
     DevBuf<double> resscale;            // m
@@ -247,8 +250,9 @@ void debug_single_pass(Context* c, int which, const double* x, double* out);
 void prepare_dense_columns(Context* c);   // model-dependent part of the dense-column preconditioner (precond.hip)
 void reset_dense_columns(Context* c);     // drops what was built from an earlier classification
 void diag_factorize_dev(Context* c, const double* W, bool precond_dense_cols, ipxint* errflag);
-// lhs = P rhs; partial dot rhs'lhs -> part(slot); returns # partials
-int diag_apply_dev(Context* c, const double* rhs, double* lhs, int slot, const int* done);
+// lhs = P rhs; partial dot rhs'lhs -> part(slot); returns # partials.  grid > 0: that many workgroups (hence partials) for
+// the diagonal form, so that a caller's own kernels can produce the same partials (cr.hip); 0: vec_grid(m)
+int diag_apply_dev(Context* c, const double* rhs, double* lhs, int slot, const int* done, int grid = 0);
 
 // ---- cr.hip ----
 struct CrResult { ipxint iter; ipxint errflag; };
@@ -260,6 +264,7 @@ CrResult cr_solve_dev(Context* c, const double* rhs, double tol, const double* r
                       void* user, double* hist_host, ipxint hist_cap, ipxk_times* times);
 double reduce_partials_host(Context* c, int slot, int count, bool is_max);
 void cr_diagnostics_dev(Context* c, ipxk_cr_diag* out);
+void cr_loop_stats_dev(const Context* c, ipxint out[4]);
 // partitioned runs: finalize this rank's partials of `slot`, all-gather, return the per-rank view
 struct PartRef publish_scalar(Context* c, int slot, int count, int op);
 // finalize this rank's partials of `slot`, all-reduce the scalar; returns a one-element view

@@ -9,25 +9,37 @@
 //  * the termination test, the error checks (:139-171) and the every-5th-iteration
 //    refresh with its monotonicity check (:186-207) are evaluated by the control kernel,
 //    which turns all later kernels into no-ops once `done` is set;
-//  * the host enqueues cycles of 5 iterations, stays at most kWindow cycles ahead of the
-//    GPU and learns about termination from flags in mapped host memory: a snapshot of `done`
-//    per cycle, by which it leaves the loop, and (single rank) a flag the control kernel sets
-//    together with `done`, after which it enqueues no further iterations.
-// Steady state per PCR iteration: 4 launches (control, SpMV pass 1, SpMV pass 2, direction).
+//  * single rank: the host follows two words in mapped host memory.  The direction kernel stores the number
+//    of finished iterations into the progress word, the control kernel sets a flag together with `done`.
+//    The host enqueues iteration k once progress >= k - R (R = kAhead iterations of run-ahead) and leaves
+//    the loop when the flag is set: at most R + 1 iterations are enqueued past the final one, whatever the
+//    timing, and nothing but the iterations themselves goes into the queue (no snapshot kernel, no event);
+//  * partitioned, and single rank with IPXK_CR_PACE=cycles (the driver before; A/B runs and tests): the host
+//    enqueues cycles of 5 iterations, stays at most kWindow cycles ahead of the GPU and leaves the loop by a
+//    snapshot of `done` per cycle (partitioned: agreed between the ranks by an all-reduce).
+// Steady state per PCR iteration: 4 launches (control, SpMV pass 1, SpMV pass 2, direction).  PcrDiag, single
+// rank: the refresh of every fifth iteration (sresidual = residual ./ diag and the partials of
+// residual'*sresidual) is made by that iteration's direction kernel (REFRESH), which has sresidual[i] and
+// diag[i] in registers already; IPXK_CR_REFRESH=0 keeps it a launch of its own (same bits).
 // The control kernel is the one pass 1 waits for; it updates the residuals only (PcrDiag: reads
 // Cstep, residual, sresidual, diag, resscale, writes residual, sresidual: 7 vector accesses).  The
 // solution update lhs += alpha*step of the same iteration is made by the direction kernel, which
 // loads step anyway (reads (s)residual, step, Cres, Cstep, diag, lhs, writes step, Cstep, lhs: 9);
 // alpha travels through CrState.  16 accesses per iteration, against 17 with the update in the
 // control kernel (IPXK_CR_LAZY=0: that order, same bits) and ~22 in the unfused formulation.
+#include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <string>
+#include <thread>
 
 #include "context.hpp"
 #include "spmv_kernels.hpp"
 
 namespace ipxk {
 
-constexpr int kWindow = 2;  // cycles (of 5 iterations) the host may run ahead
+constexpr int kWindow = 2;  // cycles (of 5 iterations) the host may run ahead (driver paced by cycles)
+constexpr int kAhead = 3;   // iterations the host may run ahead (driver paced by the progress word); IPXK_CR_AHEAD
 
 enum CrMode { kModePcrDiag = 0, kModePcrSmw = 1, kModePlain = 2 };
 
@@ -260,11 +272,11 @@ __global__ __launch_bounds__(kBlock) void cr_control_update_kernel(
     }
 }
 
-// one group of the direction kernel's loop, as CtlGroup; lhs is loaded where with_lhs says so
+// one group of the direction kernel's loop, as CtlGroup; lhs is loaded where with_lhs says so, residual for a REFRESH
 struct DirGroup {
-    double p[kCrUnroll], q[kCrUnroll], s[kCrUnroll], cs[kCrUnroll], d[kCrUnroll], l[kCrUnroll];
+    double p[kCrUnroll], q[kCrUnroll], s[kCrUnroll], cs[kCrUnroll], d[kCrUnroll], l[kCrUnroll], r[kCrUnroll];
 };
-template <int MODE, bool INIT>
+template <int MODE, bool INIT, bool REFRESH>
 __device__ __forceinline__ void dir_load(const CrVecs& v, const double* src, bool with_lhs, long long i0, long long stride,
                                          long long last, DirGroup& g) {
 #pragma unroll
@@ -275,11 +287,12 @@ __device__ __forceinline__ void dir_load(const CrVecs& v, const double* src, boo
         if (!INIT) { g.s[u] = v.step[i]; g.cs[u] = v.Cstep[i]; }
         if (MODE == kModePcrDiag) g.d[u] = v.diag[i];
         if (!INIT && with_lhs) g.l[u] = v.lhs[i];
+        if (REFRESH) g.r[u] = v.residual[i];
     }
 }
-template <int MODE, bool INIT>
+template <int MODE, bool INIT, bool REFRESH>
 __device__ __forceinline__ void dir_update(const CrVecs& v, bool owed, double alpha, double beta, long long i0, long long stride,
-                                           long long last, DirGroup& g, double& acc) {
+                                           long long last, DirGroup& g, double& acc, double& rs) {
 #pragma unroll
     for (int u = 0; u < kCrUnroll; u++) {
         const long long i = i0 + u * stride;
@@ -293,6 +306,11 @@ __device__ __forceinline__ void dir_update(const CrVecs& v, bool owed, double al
         v.Cstep[i] = g.q[u];
         if (MODE == kModePcrDiag) acc += (g.q[u] / g.d[u]) * g.q[u];   // pdot of diagonal_precond.cc:152-154
         if (MODE == kModePlain) acc += g.q[u] * g.q[u];                // Dot(Cstep,Cstep), :66
+        if (REFRESH) {                                                 // :187-194, as diag_apply_kernel (precond.hip)
+            const double l = g.r[u] / g.d[u];
+            v.sresidual[i] = l;                                        // (the old value went into step[i] above)
+            rs += l * g.r[u];
+        }
     }
 }
 
@@ -304,9 +322,16 @@ __device__ __forceinline__ void dir_update(const CrVecs& v, bool owed, double al
 // flight before the reduction's barriers, the `done` test after them.  Whether an update is owed is not known when the
 // group is loaded, so lhs is loaded with it and only the store is conditional; in the order run_cr enqueues the
 // kernels every direction kernel of the loop owes one, so nothing is read for nothing there.
-template <int MODE, bool INIT, bool EARLY>
+// REFRESH (PcrDiag, the launches with (k + 1) % 5 == 0): the kernel also makes the refresh sresidual = residual ./ diag
+// with the partials of residual'*sresidual, which is diag_apply_kernel's work on the same thread-to-element map: an
+// element's old sresidual has gone into its new step before it is overwritten, a thread adds its products in ascending
+// element order and block_reduce is the same, so with equal grids the partials are diag_apply_kernel's bit for bit.
+// host_progress (single rank, mapped host memory): the number of finished iterations, for the host's pacing alone.
+template <int MODE, bool INIT, bool EARLY, bool REFRESH>
 __global__ __launch_bounds__(kBlock) void cr_direction_kernel(CrState* st, CrVecs v, PartRef cdot_ref,
-                                                              double* pdot_partial) {
+                                                              double* pdot_partial, double* rsdot_partial,
+                                                              long long* host_progress) {
+    static_assert(!REFRESH || (MODE == kModePcrDiag && !INIT), "the fused refresh is the diagonal preconditioner's");
     __shared__ double red[kBlock / 64 + 1];
     const double* src = MODE == kModePlain ? v.residual : v.sresidual;
     const long long stride = (long long)gridDim.x * kBlock, last = v.m - 1;
@@ -322,7 +347,7 @@ __global__ __launch_bounds__(kBlock) void cr_direction_kernel(CrState* st, CrVec
         alpha = st->alpha_pending;
         double pc[kPartialsPerThread];
         load_partials(cdot_ref, pc);
-        dir_load<MODE, INIT>(v, src, true, first, stride, last, g0);
+        dir_load<MODE, INIT, REFRESH>(v, src, true, first, stride, last, g0);
         cdotnew = block_reduce<SumOp>(fold_partials<SumOp>(cdot_ref, pc), red);
         if (done) return;
         k = INIT ? -1 : k_started - 1;
@@ -337,23 +362,29 @@ __global__ __launch_bounds__(kBlock) void cr_direction_kernel(CrState* st, CrVec
         alpha = st->alpha_pending;
     }
     double acc = 0.0;   // a thread adds its elements in ascending order, unrolled or not: the partials keep their bits
+    double rs = 0.0;    // REFRESH: residual'*sresidual, likewise
     long long i0 = first;
     if (EARLY) {
-        dir_update<MODE, INIT>(v, owed, alpha, beta, i0, stride, last, g0, acc);
+        dir_update<MODE, INIT, REFRESH>(v, owed, alpha, beta, i0, stride, last, g0, acc, rs);
         i0 += kCrUnroll * stride;
     }
     for (; i0 < v.m; i0 += kCrUnroll * stride) {
         DirGroup g{};
-        dir_load<MODE, INIT>(v, src, owed, i0, stride, last, g);
-        dir_update<MODE, INIT>(v, owed, alpha, beta, i0, stride, last, g, acc);
+        dir_load<MODE, INIT, REFRESH>(v, src, owed, i0, stride, last, g);
+        dir_update<MODE, INIT, REFRESH>(v, owed, alpha, beta, i0, stride, last, g, acc, rs);
     }
     if (MODE != kModePcrSmw) {
         acc = block_reduce<SumOp>(acc, red);
         if (threadIdx.x == 0) pdot_partial[blockIdx.x] = acc;
     }
+    if (REFRESH) {
+        rs = block_reduce<SumOp>(rs, red);
+        if (threadIdx.x == 0) rsdot_partial[blockIdx.x] = rs;
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         st->cdot[(k + 1) & 1] = cdotnew;
         st->k_finished = k + 1;
+        if (host_progress) __hip_atomic_store(host_progress, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -395,6 +426,28 @@ __global__ void snapshot_flags_kernel(const double* flags, int* host_done, int* 
 // ---------------------------------------------------------------------------
 constexpr int kDoneRing = kWindow + 2;
 constexpr int kDoneNow = 2 * kDoneRing;   // slot of h_cycle_done the control kernel sets with st->done (single rank)
+// the progress word (64 bits: two slots, 8-byte aligned): the number of finished iterations, stored by the direction kernel
+constexpr int kProgress = kDoneNow + 2;
+static_assert(kProgress % 2 == 0 && kProgress + 2 <= 64, "the progress word lies inside h_cycle_done, aligned");
+
+// IPXK_CR_PACE=cycles: single rank too enqueues cycles of 5 iterations and leaves by the cycles' snapshots (the driver
+// before the progress word; A/B runs and the tests' reference)
+static bool cr_pace_cycles() {
+    static const bool setting = [] { const char* e = getenv("IPXK_CR_PACE"); return e && std::string(e) == "cycles"; }();
+    return setting;
+}
+
+// IPXK_CR_AHEAD=<R>: iterations the host may run ahead of the progress word (A/B runs and tests)
+static long long cr_ahead() {
+    static const long long setting = [] { const char* e = getenv("IPXK_CR_AHEAD"); return e && atoi(e) > 0 ? atoi(e) : kAhead; }();
+    return setting;
+}
+
+// IPXK_CR_REFRESH=0: the refresh of every fifth iteration stays a launch of its own (A/B runs and tests)
+static bool cr_refresh() {
+    static const bool setting = [] { const char* e = getenv("IPXK_CR_REFRESH"); return !e || atoi(e) != 0; }();
+    return setting;
+}
 
 // IPXK_CR_LAZY=0: the control kernel updates lhs itself (the order before the update was deferred; A/B runs and tests)
 static bool cr_lazy() {
@@ -525,6 +578,37 @@ static int applyC_split(Context* c, const double* rhs, double* lhs, const int* d
     return split_apply_dev(c, rhs, lhs, done);
 }
 
+// Single rank, paced by the progress word: waits until `need` iterations have finished or the control kernel has
+// reported `done`.  The first look costs two loads from host memory; a host that is the slower side never gets further.
+// Otherwise the thread yields between looks and asks the stream from time to time: while it holds work the device goes
+// on and one of the two words must move, so the wait ends; an error is thrown; an empty stream that has moved neither
+// word returns false (no iteration that is not `done` finishes without storing its number, so that is a broken queue).
+// hipStreamQuery is not free for the device -- the runtime learns the state of a stream of kernels by putting a marker
+// with a completion signal behind them, the barrier packet this driver exists to avoid -- so the first question comes
+// after kQueryAfter of waiting (ten iterations at C3, where one takes 0.19 ms) and the later ones at doubling intervals.
+static bool wait_for_progress(Context* c, hipStream_t s, long long need) {
+    using clock = std::chrono::steady_clock;
+    constexpr std::chrono::microseconds kQueryAfter(2000), kQueryMax(128000);
+    const volatile int* done_now = c->h_cycle_done + kDoneNow;
+    const volatile long long* progress = reinterpret_cast<const volatile long long*>(c->h_cycle_done + kProgress);
+    if (*done_now || *progress >= need) return true;
+    clock::time_point asked = clock::now();
+    std::chrono::microseconds interval = kQueryAfter;
+    for (unsigned looks = 1;; looks++) {
+        std::this_thread::yield();
+        if (*done_now || *progress >= need) return true;
+        if (looks % 64 == 0 && clock::now() - asked >= interval) {
+            const hipError_t e = hipStreamQuery(s);
+            if (e != hipErrorNotReady) {
+                IPXK_HIP(e);
+                return *done_now || *progress >= need;     // everything enqueued has finished: the words are final
+            }
+            asked = clock::now();
+            interval = std::min(interval * 2, kQueryMax);
+        }
+    }
+}
+
 template <int MODE>
 static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double tol,
                        const double* resscale, ipxint maxiter, double* lhs, bool lhs_is_zero,
@@ -542,16 +626,28 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     int* done = &st->done;
     const int g = cr_grid_cap() > 0 ? std::min(vec_grid(m), cr_grid_cap()) : vec_grid(m);
     const Pub pub(c);
-    for (int i = 0; i <= kDoneNow; i++) c->h_cycle_done[i] = 0;   // previous solve is synchronized
+    for (int i = 0; i < kProgress + 2; i++) c->h_cycle_done[i] = 0;   // previous solve is synchronized
     const bool multi = comm_active(c);
     const int lazy = cr_lazy() ? 1 : 0;
     const bool early = cr_early() && m > 0;   // (the early loads read element 0 of every vector)
     const auto control = early ? cr_control_update_kernel<MODE, true> : cr_control_update_kernel<MODE, false>;
-    const auto direction0 = early ? cr_direction_kernel<MODE, true, true> : cr_direction_kernel<MODE, true, false>;
-    const auto direction = early ? cr_direction_kernel<MODE, false, true> : cr_direction_kernel<MODE, false, false>;
+    const auto direction0 = early ? cr_direction_kernel<MODE, true, true, false> : cr_direction_kernel<MODE, true, false, false>;
+    const auto direction = early ? cr_direction_kernel<MODE, false, true, false> : cr_direction_kernel<MODE, false, false, false>;
+    // the direction kernel that also makes the refresh of every fifth iteration (PcrDiag, single rank)
+    auto direction5 = direction;
+    bool fused_refresh = false;
+    if constexpr (MODE == kModePcrDiag) {
+        fused_refresh = !multi && cr_refresh();
+        direction5 = early ? cr_direction_kernel<MODE, false, true, true> : cr_direction_kernel<MODE, false, false, true>;
+    }
     // partitioned: every rank enqueues the same collectives, so the ranks leave by the agreed snapshots alone
     int* done_now = multi ? nullptr : c->d_cycle_done + kDoneNow;
+    long long* progress = multi ? nullptr : reinterpret_cast<long long*>(c->d_cycle_done + kProgress);
     if (multi) ensure_comm_buffers(c);
+    // what this run enqueues (ipxk_cr_loop_stats): iterations, launches of this file's kernels and of the diagonal
+    // preconditioner's (the operator's and the dense-column preconditioner's are their own routines'), snapshots, events
+    long long* stats = c->cr_loop_stats;
+    stats[0] = stats[1] = stats[2] = stats[3] = 0;
 
     CrVecs v;
     v.m = m; v.lhs = lhs; v.residual = c->v_residual.get(); v.sresidual = c->v_sresidual.get();
@@ -569,8 +665,12 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
         hipLaunchKernelGGL(residual_init_kernel, dim3(g), dim3(kBlock), 0, s, m, rhs,
                            (const double*)v.Cres, resscale, v.residual, c->part(kPartRes0));
     }
+    stats[1]++;
+    // the preconditioner's partials follow the grid of this loop (IPXK_CR_GRID), so that the refresh inside the
+    // direction kernel and the one in a launch of its own give the same partials under every cap
     int nrsdot = 0;
-    if (MODE != kModePlain) nrsdot = diag_apply_dev(c, v.residual, v.sresidual, kPartRsdot, nullptr);
+    if (MODE != kModePlain) nrsdot = diag_apply_dev(c, v.residual, v.sresidual, kPartRsdot, nullptr, g);
+    if (MODE == kModePcrDiag) stats[1]++;
     if (MODE != kModePlain) pub.publish(kPartRes0, g, 1, kPartRsdot, nrsdot, 0);
     else pub.publish(kPartRes0, g, 1);
     const PartRef res0 = pub.ref(kPartRes0, g), res1 = pub.ref(kPartRes1, g);
@@ -581,69 +681,100 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     int ncdot = ops.applyC(c, csrc, v.Cres, nullptr);
     pub.publish(kPartCdot, ncdot, 0);
     hipLaunchKernelGGL(direction0, dim3(g), dim3(kBlock), 0, s, st, v,
-                       pub.ref(kPartCdot, ncdot), c->part(kPartPdot));
+                       pub.ref(kPartCdot, ncdot), c->part(kPartPdot), (double*)nullptr, progress);
+    stats[1] += 2;
     int npdot = g;
-    if (MODE == kModePcrSmw) npdot = diag_apply_dev(c, v.Cstep, v.pCstep, kPartPdot, nullptr);
+    if (MODE == kModePcrSmw) npdot = diag_apply_dev(c, v.Cstep, v.pCstep, kPartPdot, nullptr, g);
     pub.publish(kPartPdot, npdot, 0);
     const PartRef pdot_ref = pub.ref(kPartPdot, npdot);
 
-    // ---- main loop: cycles of 5 iterations ----
-    // Control::InterruptCheck (:209 / :84) is polled once per cycle of 5 iterations, not before the first
-    // cycle (a system that needs no iteration returns its result whatever the callback says).  Single rank:
-    // a nonzero flag ends the loop at once.  Partitioned: the flag travels with the cycle's `done` snapshot
-    // through one all-reduce (max), so every rank leaves in the same cycle, kWindow cycles later.
-    // Single rank: once the control kernel has reported `done` (kDoneNow) everything enqueued from then on would
-    // return at once, so the iterations are no longer enqueued; the cycles' snapshots and events still are, and
-    // the loop is left as before, through the snapshot of the cycle kWindow back.
+    // iteration k, for both drivers
+    const auto enqueue_iteration = [&](long long k) {
+        const bool refresh = MODE != kModePlain && (k + 1) % 5 == 0;   // :187-194
+        hipLaunchKernelGGL(control, dim3(g), dim3(kBlock), 0, s, st, v,
+                           res0, res1, pdot_ref, rsdot, c->part(kPartRes0), c->part(kPartRes1),
+                           c->hist.get(), lazy, done_now);
+        ncdot = ops.applyC(c, csrc, v.Cres, done);
+        // the control kernel of iteration k wrote the residual-norm partials of parity (k+1)&1
+        pub.publish(kPartCdot, ncdot, 0, ((k + 1) & 1) ? kPartRes1 : kPartRes0, g, 1);
+        hipLaunchKernelGGL(refresh && fused_refresh ? direction5 : direction, dim3(g), dim3(kBlock), 0, s, st, v,
+                           pub.ref(kPartCdot, ncdot), c->part(kPartPdot), c->part(kPartRsdot), progress);
+        stats[0]++;
+        stats[1] += 2;
+        if (MODE == kModePcrSmw) diag_apply_dev(c, v.Cstep, v.pCstep, kPartPdot, done, g);
+        if (refresh && !fused_refresh) {
+            diag_apply_dev(c, v.residual, v.sresidual, kPartRsdot, done, g);
+            if (MODE == kModePcrDiag) stats[1]++;
+        }
+        if (refresh) pub.publish(kPartPdot, npdot, 0, kPartRsdot, nrsdot, 0);
+        else pub.publish(kPartPdot, npdot, 0);
+    };
+
+    // ---- main loop ----
+    // Control::InterruptCheck (:209 / :84) is polled once per 5 iterations, not before the first five (a system
+    // that needs no iteration returns its result whatever the callback says).  Single rank: a nonzero flag ends the
+    // loop at once.  Partitioned: the flag travels with the cycle's `done` snapshot through one all-reduce (max), so
+    // every rank leaves in the same cycle, kWindow cycles later.
     ipxint interrupt_flag = 0, my_interrupt = 0;
-    bool agreed_done = false, tail = false;
-    for (long long cycle = 0;; cycle++) {
-        const long long k0 = cycle * 5;
-        if (k0 > maxiter) break;
-        if (cycle >= kWindow) {
-            const long long cw = cycle - kWindow;
-            IPXK_HIP(hipEventSynchronize(c->ev_window[cw % (kWindow + 1)]));
-            if (*(volatile int*)(c->h_cycle_done + cw % kDoneRing)) { agreed_done = true; break; }
+    bool agreed_done = false, tail = false, stalled = false;
+    if (!multi && !cr_pace_cycles()) {
+        // paced by the progress word: iteration k is enqueued once iteration k - R has finished, and never after the
+        // control kernel has reported `done` -- at most iterations 0 .. K + R when iteration K is the final one
+        const long long R = cr_ahead();
+        for (long long k = 0; k <= maxiter; k++) {
+            if (!wait_for_progress(c, s, k - R)) { stalled = true; break; }
+            if (*(volatile int*)(c->h_cycle_done + kDoneNow)) break;
+            if (interrupt && k > 0 && k % 5 == 0) {
+                my_interrupt = interrupt(user);
+                if (my_interrupt != 0) { interrupt_flag = my_interrupt; break; }
+            }
+            enqueue_iteration(k);
+        }
+    } else {
+        // cycles of 5 iterations.  Single rank (IPXK_CR_PACE=cycles): once the control kernel has reported `done`
+        // (kDoneNow) everything enqueued from then on would return at once, so the iterations are no longer enqueued;
+        // the cycles' snapshots and events still are, and the loop is left through the snapshot of the cycle kWindow back.
+        for (long long cycle = 0;; cycle++) {
+            const long long k0 = cycle * 5;
+            if (k0 > maxiter) break;
+            if (cycle >= kWindow) {
+                const long long cw = cycle - kWindow;
+                IPXK_HIP(hipEventSynchronize(c->ev_window[cw % (kWindow + 1)]));
+                if (*(volatile int*)(c->h_cycle_done + cw % kDoneRing)) { agreed_done = true; break; }
+                if (multi) {
+                    const int agreed = *(volatile int*)(c->h_cycle_done + kDoneRing + cw % kDoneRing);
+                    if (agreed != 0) { interrupt_flag = agreed; break; }
+                }
+            }
+            if (interrupt && cycle > 0) {
+                my_interrupt = interrupt(user);
+                if (!multi && my_interrupt != 0) { interrupt_flag = my_interrupt; break; }
+            }
+            for (long long k = k0; k < k0 + 5 && k <= maxiter; k++) {
+                if (done_now && *(volatile int*)(c->h_cycle_done + kDoneNow)) tail = true;
+                if (tail) break;
+                enqueue_iteration(k);
+            }
             if (multi) {
-                const int agreed = *(volatile int*)(c->h_cycle_done + kDoneRing + cw % kDoneRing);
-                if (agreed != 0) { interrupt_flag = agreed; break; }
-            }
-        }
-        if (interrupt && cycle > 0) {
-            my_interrupt = interrupt(user);
-            if (!multi && my_interrupt != 0) { interrupt_flag = my_interrupt; break; }
-        }
-        for (long long k = k0; k < k0 + 5 && k <= maxiter; k++) {
-            if (done_now && *(volatile int*)(c->h_cycle_done + kDoneNow)) tail = true;
-            if (tail) break;
-            hipLaunchKernelGGL(control, dim3(g), dim3(kBlock), 0, s, st, v,
-                               res0, res1, pdot_ref, rsdot, c->part(kPartRes0), c->part(kPartRes1),
-                               c->hist.get(), lazy, done_now);
-            ncdot = ops.applyC(c, csrc, v.Cres, done);
-            // the control kernel of iteration k wrote the residual-norm partials of parity (k+1)&1
-            pub.publish(kPartCdot, ncdot, 0, ((k + 1) & 1) ? kPartRes1 : kPartRes0, g, 1);
-            hipLaunchKernelGGL(direction, dim3(g), dim3(kBlock), 0, s, st, v,
-                               pub.ref(kPartCdot, ncdot), c->part(kPartPdot));
-            if (MODE == kModePcrSmw) diag_apply_dev(c, v.Cstep, v.pCstep, kPartPdot, done);
-            if (MODE != kModePlain && (k + 1) % 5 == 0) {
-                diag_apply_dev(c, v.residual, v.sresidual, kPartRsdot, done);   // :187-194
-                pub.publish(kPartPdot, npdot, 0, kPartRsdot, nrsdot, 0);
+                double* flags = c->comm_scalars.get() + 56;
+                hipLaunchKernelGGL(cycle_flags_kernel, dim3(1), dim3(1), 0, s, st, (double)my_interrupt, flags);
+                comm_allreduce_max(c, flags, 2);
+                hipLaunchKernelGGL(snapshot_flags_kernel, dim3(1), dim3(1), 0, s, flags, c->d_cycle_done + cycle % kDoneRing,
+                                   c->d_cycle_done + kDoneRing + cycle % kDoneRing);
+                stats[1] += 2;
             } else {
-                pub.publish(kPartPdot, npdot, 0);
+                hipLaunchKernelGGL(snapshot_done_kernel, dim3(1), dim3(1), 0, s, st, c->d_cycle_done + cycle % kDoneRing);
+                stats[1]++;
             }
+            stats[2]++;
+            IPXK_HIP(hipEventRecord(c->ev_window[cycle % (kWindow + 1)], s));
+            stats[3]++;
         }
-        if (multi) {
-            double* flags = c->comm_scalars.get() + 56;
-            hipLaunchKernelGGL(cycle_flags_kernel, dim3(1), dim3(1), 0, s, st, (double)my_interrupt, flags);
-            comm_allreduce_max(c, flags, 2);
-            hipLaunchKernelGGL(snapshot_flags_kernel, dim3(1), dim3(1), 0, s, flags, c->d_cycle_done + cycle % kDoneRing,
-                               c->d_cycle_done + kDoneRing + cycle % kDoneRing);
-        } else {
-            hipLaunchKernelGGL(snapshot_done_kernel, dim3(1), dim3(1), 0, s, st, c->d_cycle_done + cycle % kDoneRing);
-        }
-        IPXK_HIP(hipEventRecord(c->ev_window[cycle % (kWindow + 1)], s));
     }
-    if (lazy) hipLaunchKernelGGL(cr_flush_update_kernel, dim3(g), dim3(kBlock), 0, s, st, v);
+    if (lazy) {
+        hipLaunchKernelGGL(cr_flush_update_kernel, dim3(g), dim3(kBlock), 0, s, st, v);
+        stats[1]++;
+    }
     IPXK_HIP(hipEventRecord(c->ev_b, s));
     IPXK_HIP(hipMemcpyAsync(c->h_state, st, sizeof(CrState), hipMemcpyDeviceToHost, s));
     IPXK_HIP(hipStreamSynchronize(s));
@@ -654,6 +785,8 @@ static CrResult run_cr(Context* c, const CrOps& ops, const double* rhs, double t
     // others finish without finishing itself, the replicas have diverged
     if (multi && agreed_done && !c->h_state->done)
         throw Error(IPXK_E_HIP, "ranks of a partitioned solve diverged (another rank finished the CR loop, this one did not)");
+    if (stalled && !c->h_state->done)
+        throw Error(IPXK_E_HIP, "the CR loop's queue ran empty with iterations outstanding and the run not finished");
     CrResult res;
     if (c->h_state->done) {
         res.iter = c->h_state->iter;
@@ -712,6 +845,10 @@ void cr_diagnostics_dev(Context* c, ipxk_cr_diag* out) {
         out->infnorm_residual = norm(c->v_residual.get());
         if (st.mode != kModePlain) out->infnorm_sresidual = norm(c->v_sresidual.get());
     }
+}
+
+void cr_loop_stats_dev(const Context* c, ipxint out[4]) {
+    for (int i = 0; i < 4; i++) out[i] = (ipxint)c->cr_loop_stats[i];
 }
 
 CrResult pcr_solve_dev(Context* c, const double* rhs, double tol, const double* resscale,

@@ -27,7 +27,7 @@ EXPORTS = [
     "ipxk_last_error", "ipxk_device_count", "ipxk_create", "ipxk_destroy", "ipxk_set_pointer_mode",
     "ipxk_set_stream", "ipxk_synchronize", "ipxk_set_profiling", "ipxk_set_interrupt", "ipxk_reset_solver_state", "ipxk_get_reorder_info", "ipxk_get_reordering", "ipxk_num_dense_cols", "ipxk_get_rowwise",
     "ipxk_normal_prepare", "ipxk_normal_apply", "ipxk_diag_factorize", "ipxk_diag_apply",
-    "ipxk_diag_get", "ipxk_pcr_solve", "ipxk_cr_diagnostics", "ipxk_kkt_diag_factorize", "ipxk_kkt_diag_solve",
+    "ipxk_diag_get", "ipxk_pcr_solve", "ipxk_cr_diagnostics", "ipxk_cr_loop_stats", "ipxk_kkt_diag_factorize", "ipxk_kkt_diag_solve",
     "ipxk_kkt_diag_get", "ipxk_split_prepare", "ipxk_split_rescale", "ipxk_split_apply", "ipxk_forward_solve",
     "ipxk_backward_solve", "ipxk_solve_dense", "ipxk_split_levels", "ipxk_cr_solve",
     "ipxk_kkt_basis_solve", "ipxk_newton_solve", "ipxk_iterate_set", "ipxk_iterate_get", "ipxk_iterate_update",
@@ -435,6 +435,12 @@ class KktContext:
         d = CrDiag()
         self._check(self.lib.ipxk_cr_diagnostics(self.h, C.byref(d)))
         return {k: getattr(d, k) for k, _ in CrDiag._fields_}
+
+    def cr_loop_stats(self):
+        """What the last CR run enqueued: iterations, launches of the loop's own kernels, snapshots, loop events."""
+        out = np.zeros(4, i64)
+        self._check(self.lib.ipxk_cr_loop_stats(self.h, _ip(out)))
+        return {"iterations": int(out[0]), "launches": int(out[1]), "snapshots": int(out[2]), "events": int(out[3])}
 
     def cr_solve(self, rhs, tol, resscale, maxiter, lhs0=None, hist_cap=0, interrupt=None):
         return self._cr(self.lib.ipxk_cr_solve, rhs, tol, resscale, maxiter, lhs0, hist_cap, interrupt)
