@@ -13,6 +13,8 @@
 // With 2 as the fourth argument the program makes ONE call instead, ipxk_ipm_solve (LpSolver::InteriorPointSolve: starting
 // point, initial iterations, starting basis, main phase, postprocessing), and prints the evaluation of the postprocessed
 // iterate -- the reference's interior solution -- and the dropping residuals crossover would start from.
+// A sixth argument t > 0 sets both drop tolerances (ipxk_ipm_set_drop_tolerances; the reference's default is 1e-9): the main
+// phase then takes nearly degenerate variables out of the barrier problem before every Maxvolume, and the counts are printed.
 //
 //   g++ -std=c++14 -O2 -Iinclude examples/ipm_loop.cc -Lipx_amd/lib -lipx_kkt_hip -Wl,-rpath,$PWD/ipx_amd/lib -o ipm_loop
 #include <algorithm>
@@ -34,6 +36,7 @@ int main(int argc, char** argv) {
     const ipxint m = argc > 1 ? std::atol(argv[1]) : 2000, n = argc > 2 ? std::atol(argv[2]) : 5000;
     const int iterations = argc > 3 ? std::atoi(argv[3]) : 6;
     const int eq_percent = argc > 5 ? std::atoi(argv[5]) : 0;
+    const double drop_tol = argc > 6 ? std::atof(argv[6]) : 0.0;
     std::mt19937_64 rng(7);
     std::uniform_real_distribution<double> mag(0.5, 4.0), unit(0.0, 1.0);
     // A: 8 entries per column, sorted rows
@@ -66,6 +69,12 @@ int main(int argc, char** argv) {
 
     ipxk_context* ctx = nullptr;
     CHECK(ipxk_create(m, n, Ap.data(), Ai.data(), Ax.data(), 0, &ctx));
+    CHECK(ipxk_ipm_set_drop_tolerances(ctx, drop_tol, drop_tol));
+    auto print_drops = [&]() {
+        ipxint primal = 0, dual = 0, updates = 0;
+        if (ipxk_ipm_drop_counts(ctx, &primal, &dual, &updates) == IPXK_OK)
+            std::printf("drops (tolerance %.1e): %ld primal, %ld dual, %ld exchanges\n", drop_tol, (long)primal, (long)dual, (long)updates);
+    };
     if (argc > 4 && std::atoi(argv[4]) == 2) {           // the whole interior point solve in one call
         ipxk_solve_params prm{};
         prm.kkt_tol = 0.3; prm.feasibility_tol = 1e-6; prm.optimality_tol = 1e-8; prm.crossover_start = 0.0;
@@ -79,6 +88,7 @@ int main(int argc, char** argv) {
         std::printf("interior solution: pobjective %.10e dobjective %.10e rel_objgap %.2e rel_presidual %.2e rel_dresidual %.2e; "
                     "dropping residuals %.2e %.2e\n", info.pobjective, info.dobjective, info.rel_objgap, info.rel_presidual,
                     info.rel_dresidual, info.pres_dropping, info.dres_dropping);
+        print_drops();
         ipxk_destroy(ctx);
         return info.status_ipm == 1 ? 0 : 1;
     }
@@ -121,6 +131,7 @@ int main(int argc, char** argv) {
         std::printf("main IPM: status %ld after %ld iterations, %ld CR iterations, %ld basis updates; pobjective %.10e dobjective %.10e "
                     "presidual %.2e dresidual %.2e\n", (long)info.status_ipm, (long)info.iter, (long)info.kktiter, (long)info.basis_updates,
                     info.pobjective, info.dobjective, info.presidual, info.dresidual);
+        print_drops();
     }
     ipxk_destroy(ctx);
     return 0;

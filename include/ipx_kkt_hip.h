@@ -54,10 +54,14 @@ typedef struct ipxk_context ipxk_context;
 /* variable states, one byte per variable: Iterate::StateOf with the barrier state
  * split by Iterate::has_barrier_lb / has_barrier_ub (src/iterate.h:99-108,295-318) */
 #define IPXK_STATE_FIXED 0
-#define IPXK_STATE_FREE 1          /* FREE and the IMPLIED_* states */
+#define IPXK_STATE_FREE 1          /* FREE and IMPLIED_EQ (finite lb == ub) */
 #define IPXK_STATE_BARRIER_LB 2
 #define IPXK_STATE_BARRIER_UB 3
 #define IPXK_STATE_BARRIER_BOXED 4
+/* Iterate::make_implied_lb / make_implied_ub (src/iterate.cc:160-172), the result of DropPrimal: xl = xu = inf, zl and
+ * zu keep their values, the IPM treats the variable as free; Postprocess puts it on its bound (:294-308) */
+#define IPXK_STATE_IMPLIED_LB 5
+#define IPXK_STATE_IMPLIED_UB 6
 
 /* Wall-clock seconds accumulated by the last solve, measured with HIP events on
  * the context's stream; they feed ipx_info::time_cr1* / time_cr2*
@@ -490,13 +494,20 @@ int ipxk_newton_solve(ipxk_context* ctx, int use_basis, const double* rb,
  * ipxk_iterate_set is collective there: one all-reduce carries each rank's
  * verdict and a fingerprint of y and the slack parts of x, xl, xu, zl, zu and
  * state; if any rank's arguments are wrong or they differ, every rank fails
- * with IPXK_E_ARGUMENT. */
+ * with IPXK_E_ARGUMENT.
+ * A variable in IPXK_STATE_IMPLIED_LB / IMPLIED_UB must meet what Iterate::assert_consistency
+ * (src/iterate.cc:500-513) asks of the iterate's own vectors: xl = xu = inf and zl, zu >= 0 (the bound it
+ * is implied at must be finite; the call does not see the bounds).  Otherwise IPXK_E_ARGUMENT, the first
+ * offending index in the message.  An iterate without those states is copied unchecked, as before. */
 int ipxk_iterate_set(ipxk_context* ctx, const double* x, const double* xl,
                      const double* xu, const double* y, const double* zl,
                      const double* zu, const unsigned char* state);
 /* copies out; NULL pointers are skipped */
 int ipxk_iterate_get(ipxk_context* ctx, double* x, double* xl, double* xu,
                      double* y, double* zl, double* zu);
+/* the IPXK_STATE_* byte of every variable, state[n+m] (host memory): what ipxk_iterate_set was given, as
+ * ipxk_ipm_starting_basis and the drop procedures (ipxk_ipm_drop_degenerate) have changed it */
+int ipxk_iterate_get_state(ipxk_context* ctx, unsigned char* state);
 /* Iterate::Update (src/iterate.cc:94-139): x += sp*dx on non-fixed variables,
  * xl/xu += sp*d, zl/zu += sd*d on variables with that barrier term, truncated
  * at kBarrierMin = 1e-30; y += sd*dy.  NULL step components are skipped. */
@@ -565,8 +576,8 @@ int ipxk_iterate_factorize_diag(ipxk_context* ctx, int precond_dense_cols,
 /* Iterate::ComputeObjectives (src/iterate.cc:590-640) of the resident iterate for
  * the model vectors: out3 = {pobjective, dobjective, offset}; pobjective + offset
  * and dobjective + offset are the objectives after postprocessing (:203-211).
- * Variable states as in ipxk_iterate_set (the implied states of the basis solver's
- * drop procedures do not exist on the device).  On a postprocessed iterate
+ * Variable states as in ipxk_iterate_set; a variable in IPXK_STATE_IMPLIED_LB / IMPLIED_UB
+ * moves (zl - zu) x from pobjective to offset (:621-626).  On a postprocessed iterate
  * (ipxk_iterate_postprocess) it is the other branch (:599-609): pobjective = c'x,
  * dobjective = b'y + sum lb zl - sum ub zu over the finite bounds, offset = 0.
  * Column partition: global, one
@@ -666,14 +677,17 @@ int ipxk_ipm_load_starting_point(ipxk_context* ctx, const double* x,
 
 /* The main IPM phase (LpSolver::RunMainIPM, src/lp_solver.cc:456-462): IPM::Driver around KKTSolverBasis.
  * Every iteration's KKTSolverBasis::_Factorize (src/kkt_solver_basis.cc:20-63) runs on the device: scaling
- * factors from the resident iterate (Iterate::ScalingFactor, src/iterate.cc:183-198), Maxvolume
- * (ipxk_maxvolume), fresh factorization, Prepare; then the predictor-corrector step with the basis-
- * preconditioned solves.  The starting basis is the slack basis (ConstructBasisFromWeights with
- * crash_basis = 0, src/basis.cc:353-385); DropPrimal / DropDual (:36-43) are not taken.  Models whose
- * iterate holds free or fixed variables are refused (IPXK_E_UNSUPPORTED) -- unless the context holds a live
+ * factors from the resident iterate (Iterate::ScalingFactor, src/iterate.cc:183-198),
+ * DropPrimal / DropDual when a drop tolerance is positive (ipxk_ipm_set_drop_tolerances below; :36-43, off by
+ * default), Maxvolume (ipxk_maxvolume), fresh factorization, Prepare; then the predictor-corrector step with the
+ * basis-preconditioned solves.  The starting basis is the slack basis (ConstructBasisFromWeights with
+ * crash_basis = 0, src/basis.cc:353-385).  Models whose
+ * iterate holds free or fixed variables are refused (IPXK_E_UNSUPPORTED) when the phase has to build the slack
+ * basis -- not when the context holds a live
  * starting basis (ipxk_ipm_starting_basis below): then the phase starts from that basis and its four-valued
  * statuses instead, BASIC_FREE and NONBASIC_FIXED persist through Maxvolume and Prepare, and the scaling
- * factors 0 / inf of fixed / free variables are taken as they are.  basis_out[m] / status_out[n+m]
+ * factors 0 / inf of fixed / free variables are taken as they are; nor in a later iteration, whose basis may
+ * hold the variables the drop procedures have fixed or implied.  basis_out[m] / status_out[n+m]
  * (either may be NULL) return the final basis.  params->kkt_maxiter is ignored (KKTSolverBasis runs CR with
  * maxiter = -1).  The termination test is ipxk_ipm_driver's, crossover_start included; a postprocessed iterate is
  * refused by both drivers.  Limits of the refactorizations: see ipxk_lu_factorize (dense bump).  Refused on any partitioned
@@ -736,14 +750,70 @@ int ipxk_ipm_starting_basis(ipxk_context* ctx, const double* b, const double* c,
                             ipxint* status_out, ipxint* exchange_log, ipxint log_cap,
                             ipxk_interrupt_fn interrupt, void* interrupt_user);
 
+/* ---- KKTSolverBasis::DropPrimal / DropDual (src/kkt_solver_basis.cc:36-43, 196-387) --------------------------
+ * Control::ipm_drop_primal / ipm_drop_dual for ipxk_ipm_driver_basis, ipxk_ipm_solve and ipxk_lp_solve: with a
+ * positive tolerance every Factorize of the main phase first takes nearly degenerate variables out of the barrier
+ * problem (below).  0, 0 (the default, restored by ipxk_reset_solver_state): off, the phase runs as it did without
+ * them.  Negative or non-finite values: IPXK_E_ARGUMENT.  (The reference's default is 1e-9 for both.) */
+int ipxk_ipm_set_drop_tolerances(ipxk_context* ctx, double drop_primal, double drop_dual);
+/* One DropPrimal + DropDual pass on the resident iterate and the context's live basis, with the tolerances set
+ * above: what KKTSolverBasis::_Factorize does between the scaling factors and Maxvolume.
+ *   Gate (:36): nothing happens unless pobjective >= dobjective (without the offset, as ipxk_iterate_objectives
+ *     returns them); the model vectors b[m], c, lb, ub [n+m] are read for it alone.
+ *   DropPrimal: the candidates are the BASIC variables whose distance xj to the nearer bound and its dual zj have
+ *     xj < 0.01 zj and xj <= drop_primal, taken from the back of the list in position order.  Per candidate jb at
+ *     position p: the tableau row r = AI' inverse(B') e_p over the NONBASIC columns and the arg max of
+ *     |r_j| colscale_j / colscale_jb among |r_j| > 1e-7 (kPivotZeroTol) with a value > 2.0 (volume_tol), both strict,
+ *     ties to the lowest j -- one fused pass over the matrix, the row is never stored.  A winner jmax is exchanged for
+ *     jb (Basis::ExchangeIfStable with the pivot from the FTRAN of jmax; a refused exchange refactorizes and tries
+ *     the candidate again); without one jb becomes implied at lb (zl/xl > zu/xu) or at ub (IPXK_STATE_IMPLIED_*,
+ *     xl = xu = inf, zl, zu kept), BASIC_FREE, scaling factor inf.
+ *   DropDual: the candidates are the NONBASIC variables whose larger dual zj and its xj have zj < 0.01 xj and
+ *     zj <= drop_dual, from the back of the ascending list.  Per candidate jn: the tableau column and the arg max of
+ *     |lhs_p| colscale_jn / colscale_basis[p] under the same two thresholds (a BASIC_FREE position never wins).  A
+ *     winner is exchanged (pivot from the BTRAN against the one from the column); without one jn is fixed at its
+ *     value (IPXK_STATE_FIXED, xl = xu = zl = zu = 0), NONBASIC_FIXED, scaling factor 0.
+ * When a screening kernel finds no candidate, only its count reaches the host and nothing else is launched.  Every
+ * reduction is a fixed-order tree with ties to the lowest index: two calls from the same state give the same bits.
+ * Requires a live starting basis (ipxk_ipm_starting_basis) or the basis ipxk_ipm_driver_basis ended with, whose
+ * factors are still the context's; otherwise IPXK_E_ARGUMENT.  Afterwards that basis is the one returned here, with
+ * fresh factors and its operator.  basis_out[m], status_out[n+m] may be NULL; so may colscale_out[n+m] (host memory), which
+ * receives the scaling factors Maxvolume would go on with: Iterate::ScalingFactor of every variable, read back from the device
+ * after the pass, with the inf of the implied and the 0 of the fixed variables as the deciding kernels wrote them.  log receives triples {variable, action, partner} of
+ * the first log_cap decisions (3 log_cap entries): action 0 exchanged (partner: the variable it was exchanged with), 1 implied at lb, 2 implied at ub,
+ * 3 fixed (partner -1).  info->errflag: 301 / 306 from a refactorization, 999 (or the callback's value) from the
+ * interrupt, polled once per candidate; variables already dropped stay dropped, as in the reference, and after an interrupt
+ * the context holds the factors and the operator of the basis returned.  A call that ends with an errflag leaves no live
+ * basis (the next one is refused until ipxk_ipm_starting_basis or ipxk_ipm_driver_basis has run again); so does an
+ * ipxk_ipm_driver_basis that ends inside a Factorize.
+ * Refused on any partitioned context and on a postprocessed iterate. */
+typedef struct ipxk_drop_info {
+    ipxint errflag;
+    ipxint primal_candidates, dual_candidates;   /* of the two screenings */
+    ipxint primal_dropped, dual_dropped;         /* Info::primal_dropped / dual_dropped of this pass */
+    ipxint updates;                              /* exchanges (they count into Info::updates_ipm) */
+    ipxint refused;                              /* exchanges refused as unstable */
+    ipxint factorizations;
+    double seconds;
+} ipxk_drop_info;
+int ipxk_ipm_drop_degenerate(ipxk_context* ctx, const double* b, const double* c, const double* lb, const double* ub,
+                             ipxk_drop_info* info, ipxint* basis_out, ipxint* status_out, double* colscale_out,
+                             ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* interrupt_user);
+/* Sums over the Factorizes since the last ipxk_ipm_driver_basis / ipxk_ipm_solve / ipxk_lp_solve began
+ * (Info::primal_dropped, Info::dual_dropped and the exchanges of the drop procedures, which ipxk_ipm_info::basis_updates
+ * includes as Info::updates_ipm does).  Any pointer may be NULL. */
+int ipxk_ipm_drop_counts(const ipxk_context* ctx, ipxint* primal_dropped, ipxint* dual_dropped, ipxint* drop_updates);
+
 /* ---- the end of the solve (src/lp_solver.cc:305-332, src/iterate.cc:237-448) -------------------------------
  * Iterate::Postprocess (src/iterate.cc:250-313) on the resident iterate for the model vectors c, lb, ub [n+m].
- * The reference's StateDetail is derived from the five device states and the bounds: IPXK_STATE_FIXED is FIXED;
+ * The reference's StateDetail is derived from the device states and the bounds: IPXK_STATE_FIXED is FIXED;
  * IPXK_STATE_FREE with finite lb == ub is IMPLIED_EQ (the slacks of dependent equality rows after
- * ipxk_ipm_starting_basis); IPXK_STATE_FREE otherwise is FREE.  IMPLIED_LB / IMPLIED_UB do not occur.
+ * ipxk_ipm_starting_basis); IPXK_STATE_FREE otherwise is FREE; IPXK_STATE_IMPLIED_LB / IMPLIED_UB are themselves.
  *   fixed:      xl = x - lb, xu = ub - x (inf at an infinite bound); if lb == ub, z = c_j - a_j'y goes to zl
  *               (z >= 0) or to zu as -z.
  *   implied eq: z goes to zl or zu by sign, the other one is 0; x = lb, xl = xu = 0.
+ *   implied lb: zl = z, zu = 0, x = lb;  implied ub: zl = 0, zu = -z, x = ub;  then xl = x - lb, xu = ub - x
+ *               (:294-308).
  * Only those variables are written; when a count on the device finds none, nothing else is launched and the
  * iterate keeps its bits.  The products a_j'y come from one pass over the column gather matrix.
  * Afterwards the iterate is "postprocessed" until ipxk_iterate_set, ipxk_ipm_starting_point,

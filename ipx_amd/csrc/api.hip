@@ -269,9 +269,11 @@ int ipxk_reset_solver_state(ipxk_context* c, double lu_pivottol) {
         // factors, N, the tightened pivot tolerance.  The buffers stay (grow-only workspaces); nothing of their content is used again.
         c->W = nullptr;
         c->normal_prepared = c->diag_factorized = c->kkt_diag_factorized = c->it_set = false;
-        c->sb_live = false;
+        c->sb_live = c->drv_live = false;
         c->postprocessed = false;
         c->crossover_start = 0.0;
+        c->drop_primal = c->drop_dual = 0.0;
+        c->sum_primal_dropped = c->sum_dual_dropped = c->sum_drop_updates = 0;
         c->kdense = 0;
         if (c->split) {
             if (c->split_spare) destroy_split(c->split_spare);
@@ -596,7 +598,7 @@ int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const d
         bind_device(c);
         c->it_set = false;
         c->postprocessed = false;
-        c->sb_live = false;                 // a starting basis belongs to the iterate it was built from
+        c->sb_live = c->drv_live = false;                 // a starting basis belongs to the iterate it was built from
         const size_t m = (size_t)c->m, n = (size_t)c->n, N = (size_t)(c->n + c->m);
         DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
         const double* src[6] = {x, xl, xu, y, zl, zu};
@@ -610,6 +612,18 @@ int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const d
             copy_in(c, c->it_state.get(), state, N);
         }
         IPXK_HIP(hipStreamSynchronize(c->stream));
+        // the implied states under the conditions of Iterate::assert_consistency (src/iterate.cc:500-513)
+        std::string err = args ? std::string() : std::string("NULL argument");
+        // (host pointers: the kernel runs only when a state byte says there is something to check)
+        bool any_implied = args;
+        if (args && c->pointer_mode == IPXK_POINTER_HOST)
+            any_implied = std::any_of(state, state + N, [](unsigned char st) { return st == IPXK_STATE_IMPLIED_LB || st == IPXK_STATE_IMPLIED_UB; });
+        if (any_implied) {
+            const int64_t bad = iterate_check_implied_dev(c);
+            if (bad >= 0)
+                err = "variable " + std::to_string(bad) + " is in an implied state but does not have xl = xu = inf and zl, zu >= 0";
+        }
+        if (!comm_cols(c)) IPXK_REQUIRE(err.empty(), err);
         if (comm_cols(c)) {
             uint64_t fp = 0;
             if (args) {
@@ -622,7 +636,7 @@ int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const d
                 F.add(hs.data(), hs.size());
                 fp = F.h;
             }
-            agree_on_arguments(c, args ? std::string() : std::string("NULL argument"), fp, "ipxk_iterate_set",
+            agree_on_arguments(c, err, fp, "ipxk_iterate_set",
                                "y and the slack parts of x, xl, xu, zl, zu and state");
         }
         c->it_set = true;
@@ -776,7 +790,7 @@ int ipxk_ipm_starting_point(ipxk_context* c, const double* b, const double* cc, 
         const double* dc = stage_in(c, cc, N, c->nw_in[1]);
         const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
         const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        c->sb_live = false;
+        c->sb_live = c->drv_live = false;
         c->postprocessed = false;
         ipm_starting_point_dev(c, db, dc, dlb, dub, params, info, interrupt, interrupt_user);
         IPXK_HIP(hipStreamSynchronize(c->stream));
@@ -813,7 +827,7 @@ int ipxk_ipm_load_starting_point(ipxk_context* c, const double* x, const double*
         bind_device(c);
         c->it_set = false;
         c->postprocessed = false;
-        c->sb_live = false;                 // a starting basis belongs to the iterate it was built from
+        c->sb_live = c->drv_live = false;                 // a starting basis belongs to the iterate it was built from
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         std::string err = args ? std::string() : std::string("NULL argument");
         if (!args) {
@@ -864,6 +878,55 @@ int ipxk_ipm_set_crossover_start(ipxk_context* c, double value) {
         IPXK_REQUIRE(c != nullptr, "ctx is NULL");
         IPXK_REQUIRE(value >= 0.0, "crossover_start must not be negative (0: off)");    // false for a NaN
         c->crossover_start = value;
+    });
+}
+
+// ---- DropPrimal / DropDual (drop.hip) ------------------------------------------------------------------------------
+int ipxk_ipm_set_drop_tolerances(ipxk_context* c, double drop_primal, double drop_dual) {
+    return guarded([&] {
+        IPXK_REQUIRE(c != nullptr, "ctx is NULL");
+        IPXK_REQUIRE(drop_primal >= 0.0 && std::isfinite(drop_primal) && drop_dual >= 0.0 && std::isfinite(drop_dual),
+                     "the drop tolerances must be finite and not negative (0: off)");
+        c->drop_primal = drop_primal;
+        c->drop_dual = drop_dual;
+    });
+}
+
+int ipxk_ipm_drop_degenerate(ipxk_context* c, const double* b, const double* cc, const double* lb, const double* ub,
+                             ipxk_drop_info* info, ipxint* basis_out, ipxint* status_out, double* colscale_out, ipxint* log,
+                             ipxint log_cap, ipxk_interrupt_fn interrupt, void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && b && cc && lb && ub && info, "NULL argument");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // it runs the device LU
+        IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
+        IPXK_REQUIRE(log_cap >= 0 && (log || log_cap == 0), "log is NULL");
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* db = stage_in(c, b, m, c->nw_in[0]);
+        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        ipm_drop_degenerate_dev(c, db, dc, dlb, dub, info, basis_out, status_out, colscale_out, log, log_cap, interrupt, interrupt_user);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_ipm_drop_counts(const ipxk_context* c, ipxint* primal_dropped, ipxint* dual_dropped, ipxint* drop_updates) {
+    return guarded([&] {
+        IPXK_REQUIRE(c != nullptr, "ctx is NULL");
+        if (primal_dropped) *primal_dropped = c->sum_primal_dropped;
+        if (dual_dropped) *dual_dropped = c->sum_dual_dropped;
+        if (drop_updates) *drop_updates = c->sum_drop_updates;
+    });
+}
+
+int ipxk_iterate_get_state(ipxk_context* c, unsigned char* state) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && c->it_set, "no iterate on the device (ipxk_iterate_set)");
+        IPXK_REQUIRE(state != nullptr, "NULL argument");
+        bind_device(c);
+        staged_d2h(state, c->it_state.get(), (size_t)(c->n + c->m), c->stream);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
     });
 }
 

@@ -161,6 +161,14 @@ struct Context {
     bool sb_live = false;
     long sb_lu_generation = -1;            // of those factors: another factorization in the context ends the state
     std::vector<ipxint> sb_basis, sb_status;
+    // DropPrimal / DropDual (drop.hip): Control::ipm_drop_primal / ipm_drop_dual (0, 0: off), the basis ipm_driver_dev ended with
+    // when it did not start from a starting basis (what ipxk_ipm_drop_degenerate then works on), and Info::primal_dropped /
+    // dual_dropped / the drop exchanges since the last driver began
+    double drop_primal = 0.0, drop_dual = 0.0;
+    bool drv_live = false;
+    long drv_lu_generation = -1;
+    std::vector<ipxint> drv_basis, drv_status;
+    ipxint sum_primal_dropped = 0, sum_dual_dropped = 0, sum_drop_updates = 0;
 
     // ---- multi-GPU ----
     ncclComm* comm = nullptr;
@@ -342,6 +350,19 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
                             ipxint* status_out, ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* user);
 // Iterate::ScalingFactor of every variable into d[n+m] (device); *nonbarrier (device) is set when a variable is fixed or free
 void iterate_scaling_factors_dev(Context* c, double* d, int* nonbarrier);
+
+// ---- drop.hip ----
+// One DropPrimal + DropDual pass (src/kkt_solver_basis.cc:196-387) on the resident iterate and the basis (basis[m], status[n+m],
+// colscale[n+m], host; updated in place) whose factors and operator the context holds -- fresh, or with Maxvolume's kept etas
+// behind them.  The caller has taken the gate (:36).  On return the context holds the operator of the basis returned.
+void ipm_drop_dev(Context* c, std::vector<ipxint>& basis, std::vector<ipxint>& status, std::vector<double>& colscale,
+                  ipxk_drop_info* info, ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* user);
+// ipxk_ipm_drop_degenerate: the gate, the scaling factors and the pass on the context's live basis
+void ipm_drop_degenerate_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, ipxk_drop_info* info,
+                             ipxint* basis_out, ipxint* status_out, double* colscale_out, ipxint* log, ipxint log_cap,
+                             ipxk_interrupt_fn interrupt, void* user);
+// the first variable in IPXK_STATE_IMPLIED_* whose xl, xu, zl, zu break Iterate::assert_consistency, -1: none (ipxk_iterate_set)
+int64_t iterate_check_implied_dev(Context* c);
 
 // ---- start.hip ----
 // IPM::ComputeStartingPoint (the model vectors on the device; b, c, lb, ub checked) and IPM::LoadStartingPoint (the

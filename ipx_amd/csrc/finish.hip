@@ -4,7 +4,7 @@
 //   Iterate::ResidualsFromDropping  iterate.cc:393-448  what term_crit_reached asks with crossover_start > 0 (:237-248)
 //   LpSolver::InteriorPointSolve    lp_solver.cc:305-462 starting point, initial iterations, starting basis, main phase,
 //                                                       postprocessing, evaluation, the "imprecise" verdict
-// The device keeps five states (IPXK_STATE_*); the reference's StateDetail is derived from the state and the bounds
+// The device keeps seven states (IPXK_STATE_*); the reference's StateDetail is derived from the state and the bounds
 // (detail_of).  Every rule is local to a column, so on a column partition each rank treats [its structural slice; all m
 // slack entries] and only the two dropping residuals are combined (max, slack terms on rank 0).  The products a_j'y of
 // the structural columns are one pass of the column gather matrix with EpiPostprocess; a dense column of A is a long row
@@ -26,7 +26,9 @@ enum Detail { kOther, kFixed, kImpliedEq, kImpliedLb, kImpliedUb };
 __device__ __forceinline__ Detail detail_of(unsigned char st, double l, double u) {
     if (st == IPXK_STATE_FIXED) return kFixed;
     if (st == IPXK_STATE_FREE && l == u && isfinite(l)) return kImpliedEq;     // the slack of a dependent equality row
-    return kOther;                              // kImpliedLb / kImpliedUb are not stored states yet (DropPrimal / DropDual)
+    if (st == IPXK_STATE_IMPLIED_LB) return kImpliedLb;                        // DropPrimal (drop.hip)
+    if (st == IPXK_STATE_IMPLIED_UB) return kImpliedUb;
+    return kOther;
 }
 
 struct IterateVectors { double *x, *xl, *xu, *zl, *zu; };
@@ -93,12 +95,17 @@ __global__ __launch_bounds__(kBlock) void postprocess_count_kernel(int n, int m,
                                                                    const double* __restrict__ lb,
                                                                    const double* __restrict__ ub, double* out) {
     __shared__ double red[kBlock / 64 + 1];
-    double ns = 0.0, nk = 0.0;
-    for (int j = blockIdx.x * kBlock + threadIdx.x; j < n + m; j += gridDim.x * kBlock)
-        if (detail_of(state[j], lb[j], ub[j]) != kOther) { if (j < n) ns += 1.0; else nk += 1.0; }
+    double ns = 0.0, nk = 0.0, bad = MinOp::identity();
+    for (int j = blockIdx.x * kBlock + threadIdx.x; j < n + m; j += gridDim.x * kBlock) {
+        const Detail d = detail_of(state[j], lb[j], ub[j]);
+        if (d != kOther) { if (j < n) ns += 1.0; else nk += 1.0; }
+        // Iterate::assert_consistency (:500-513): the bound a variable is implied at is finite
+        if ((d == kImpliedLb && !isfinite(lb[j])) || (d == kImpliedUb && !isfinite(ub[j]))) bad = fmin(bad, (double)j);
+    }
     ns = block_reduce<SumOp>(ns, red);
     nk = block_reduce<SumOp>(nk, red);
-    if (threadIdx.x == 0) { out[blockIdx.x] = ns; out[gridDim.x + blockIdx.x] = nk; }
+    bad = block_reduce<MinOp>(bad, red);
+    if (threadIdx.x == 0) { out[blockIdx.x] = ns; out[gridDim.x + blockIdx.x] = nk; out[2 * gridDim.x + blockIdx.x] = bad; }
 }
 
 // max |a_ij| of every structural column, 8 lanes per column
@@ -195,11 +202,12 @@ void iterate_postprocess_dev(Context* c, const double* cc, const double* lb, con
     const int g = vec_grid(N);
     c->it_partials.resize((size_t)4 * 1024);
     hipLaunchKernelGGL(postprocess_count_kernel, dim3(g), dim3(kBlock), 0, s, n, m, c->it_state.get(), lb, ub, c->it_partials.get());
-    std::vector<double> h((size_t)2 * g);
+    std::vector<double> h((size_t)3 * g);
     c->it_partials.download(h.data(), h.size(), s);
     IPXK_HIP(hipGetLastError());
-    double nstruct = 0.0, nslack = 0.0;
-    for (int i = 0; i < g; i++) { nstruct += h[i]; nslack += h[(size_t)g + i]; }
+    double nstruct = 0.0, nslack = 0.0, bad = INFINITY;
+    for (int i = 0; i < g; i++) { nstruct += h[i]; nslack += h[(size_t)g + i]; bad = std::min(bad, h[(size_t)2 * g + i]); }
+    IPXK_REQUIRE(std::isinf(bad), "variable " + std::to_string((long long)bad) + " is implied at an infinite bound");
     const IterateVectors V{c->it_x.get(), c->it_xl.get(), c->it_xu.get(), c->it_zl.get(), c->it_zu.get()};
     if (nstruct > 0.0) {
         EpiPostprocess ep{{}, c->it_state.get(), cc, lb, ub, V};
@@ -210,7 +218,7 @@ void iterate_postprocess_dev(Context* c, const double* cc, const double* lb, con
                            c->it_y.get(), V);
     IPXK_HIP(hipGetLastError());
     c->postprocessed = true;
-    c->sb_live = false;                         // the main phase does not go on from a postprocessed iterate
+    c->sb_live = c->drv_live = false;                         // the main phase does not go on from a postprocessed iterate
 }
 
 void iterate_dropping_residuals_dev(Context* c, const double* lb, const double* ub, double out2[2]) {
@@ -249,6 +257,7 @@ void ipm_solve_dev(Context* c, const double* b, const double* cc, const double* 
     constexpr ipxint kNotRun = 0, kOptimal = 1, kImprecise = 2, kPrimalInfeas = 3, kDualInfeas = 4, kTimeLimit = 5, kIterLimit = 6,
                      kNoProgress = 7, kFailed = 8;
     *info = ipxk_solve_info{};
+    c->sum_primal_dropped = c->sum_dual_dropped = c->sum_drop_updates = 0;
     struct Restore {                            // crossover_start holds for this call
         Context* c; double saved;
         ~Restore() { c->crossover_start = saved; }
@@ -268,7 +277,7 @@ void ipm_solve_dev(Context* c, const double* b, const double* cc, const double* 
     };
     auto run = [&] {                            // RunIPM, :334-359
         if (!prm->use_resident_point) {
-            c->sb_live = false;
+            c->sb_live = c->drv_live = false;
             c->postprocessed = false;
             ipm_starting_point_dev(c, b, cc, lb, ub, &ip, &gi, interrupt, user);
             info->status_ipm = gi.status_ipm;

@@ -518,6 +518,14 @@ struct MaxvolState {
     DevBuf<MvScalars> scalars;
     DevBuf<unsigned char> tmp;
     MvScalars* h = nullptr;    // pinned
+    // the drop procedures (drop.hip): device copies of basis, status and scaling factors, the candidate list (+ its count), the
+    // scalars of a candidate and their pinned mirror; grow-only like the rest
+    DevBuf<ipxint> drop_basis, drop_status;
+    DevBuf<double> drop_colscale;
+    DevBuf<int> drop_list;
+    DevBuf<unsigned char> drop_scalars;
+    void* drop_h = nullptr;    // pinned
+    size_t drop_h_bytes = 0;
     // the eta file kept BEHIND the resident factors between two calls (Context::etas_live): what EtaFile needs to go on, and the basis
     // the factors + etas represent (by basis position; the device copy is `basis`)
     struct Saved {
@@ -529,7 +537,7 @@ struct MaxvolState {
         int Kd = 0;                    // > 0: etaF / etaG hold the matrices of the two triangular systems (Kd etas are the first at their position)
     } saved;
     std::vector<ipxint> basis_h;
-    ~MaxvolState() { if (h) (void)hipHostFree(h); }
+    ~MaxvolState() { if (h) (void)hipHostFree(h); if (drop_h) (void)hipHostFree(drop_h); }
 };
 
 struct Context;

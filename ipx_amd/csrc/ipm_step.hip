@@ -182,7 +182,7 @@ __global__ void scaling_factor_kernel(int N, const unsigned char* __restrict__ s
         const unsigned char st = state[j];
         double d;
         if (st == IPXK_STATE_FIXED) { d = 0.0; *nonbarrier = 1; }
-        else if (st == IPXK_STATE_FREE) { d = __builtin_huge_val(); *nonbarrier = 1; }
+        else if (st == IPXK_STATE_FREE || st == IPXK_STATE_IMPLIED_LB || st == IPXK_STATE_IMPLIED_UB) { d = __builtin_huge_val(); *nonbarrier = 1; }
         else d = 1.0 / sqrt(zl[j] / xl[j] + zu[j] / xu[j]);
         colscale[j] = d;
     }
@@ -195,14 +195,15 @@ void iterate_scaling_factors_dev(Context* c, double* d, int* nonbarrier) {
 }
 
 // KKTSolverBasis::_Factorize (src/kkt_solver_basis.cc:20-63) on the device: scaling factors from the iterate,
-// Maxvolume, fresh factorization, Prepare.  DropPrimal / DropDual (:36-43) are not taken (they move nearly
-// degenerate variables out of the barrier problem; leaving them in is a valid, if slower, interior point step).
+// DropPrimal / DropDual (:36-43, drop.hip) when a drop tolerance is positive and the gate pobjective >= dobjective holds,
+// Maxvolume, fresh factorization, Prepare.  With both tolerances 0 (the default) the drops are not taken: leaving nearly
+// degenerate variables in the barrier problem is a valid, if slower, interior point step.
 // The first call builds the slack basis (Basis::SetToSlackBasis; ConstructBasisFromWeights with crash_basis = 0,
 // src/basis.cc:353-385, for a model without free or fixed variables).  With a live starting basis
 // (ipxk_ipm_starting_basis) there is no first call: basis and status are its result, fixed and free variables
 // keep their scaling factors 0 and inf, and Maxvolume and Prepare carry BASIC_FREE / NONBASIC_FIXED along.
 static void basis_factorize_dev(Context* c, std::vector<ipxint>& basis, std::vector<ipxint>& status, std::vector<double>& colscale,
-                                bool first, ipxk_ipm_info* info) {
+                                bool first, bool drop_gate, ipxk_interrupt_fn interrupt, void* user, ipxk_ipm_info* info) {
     const int m = (int)c->m, n = (int)c->n, N = n + m;
     hipStream_t s = c->stream;
     DevBuf<double> d((size_t)N);
@@ -213,13 +214,23 @@ static void basis_factorize_dev(Context* c, std::vector<ipxint>& basis, std::vec
     flag.download(&nonbarrier, 1, s);
     d.download(colscale.data(), (size_t)N, s);
     IPXK_HIP(hipStreamSynchronize(s));
-    if (nonbarrier && !c->sb_live) throw Error(IPXK_E_UNSUPPORTED, "the basis phase of ipxk_ipm_driver handles barrier variables only (no free or fixed ones)");
+    // (a basis the driver has carried may hold variables the drop procedures have fixed or implied, as a live starting basis may)
+    if (nonbarrier && first) throw Error(IPXK_E_UNSUPPORTED, "the basis phase of ipxk_ipm_driver handles barrier variables only (no free or fixed ones)");
     if (first) {
         for (int j = 0; j < n; j++) status[j] = IPXK_NONBASIC;
         for (int i = 0; i < m; i++) { status[n + i] = IPXK_BASIC; basis[i] = n + i; }
         ipxk_lu_info li{};
         lu_factorize_basis(c, basis.data(), 0.1, false, &li);
         split_prepare_lu(c, status.data(), colscale.data());
+    }
+    if (drop_gate && (c->drop_primal > 0.0 || c->drop_dual > 0.0)) {                        // :36-43
+        ipxk_drop_info di{};
+        ipm_drop_dev(c, basis, status, colscale, &di, nullptr, 0, interrupt, user);
+        c->sum_primal_dropped += di.primal_dropped;
+        c->sum_dual_dropped += di.dual_dropped;
+        c->sum_drop_updates += di.updates;
+        info->basis_updates += di.updates;
+        if (di.errflag) { info->errflag = di.errflag; return; }
     }
     ipxk_maxvolume_info mi{};
     std::vector<ipxint> nb(basis.size()), ns(status.size());
@@ -280,7 +291,11 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
     std::vector<ipxint> basis, status;
     std::vector<double> colscale;
-    if (use_basis) { basis.resize((size_t)c->m); status.resize((size_t)(c->n + c->m)); colscale.resize((size_t)(c->n + c->m)); }
+    if (use_basis) {
+        basis.resize((size_t)c->m); status.resize((size_t)(c->n + c->m)); colscale.resize((size_t)(c->n + c->m));
+        c->sum_primal_dropped = c->sum_dual_dropped = c->sum_drop_updates = 0;
+        c->drv_live = false;
+    }
     bool first_factorize = true;
     if (use_basis && c->sb_live && c->sb_lu_generation != lu_generation(c)) c->sb_live = false;    // the factors are no longer its
     const bool from_starting_basis = use_basis && c->sb_live;
@@ -295,6 +310,9 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     iterate_complementarity_dev(c, comp);
     double best_complementarity = comp[0];               // :315
     ipxint num_bad_iter = 0, errflag = 0;
+    // a Factorize that ends with an errflag -- since the drop procedures poll the interrupt, also 999, which is reported as a time
+    // limit without an errflag -- leaves basis, status and factors as they stood when it gave up: nothing goes on from them
+    bool ended_in_factorize = false;
     while (true) {
         IterScalars S;                                   // residuals, complementarity and objectives: one table
         iterate_scalars_dev(c, kIterResiduals | kIterComplementarity | kIterObjectives, b, cc, lb, ub, c->ipm[0].get(),
@@ -330,9 +348,10 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
         if (info->iter >= prm->ipm_maxiter) { info->status_ipm = 6; break; }       // iter_limit
         if ((errflag = agree_interrupt(c, interrupt ? interrupt(user) : 0)) != 0) break;
         if (use_basis) {
-            basis_factorize_dev(c, basis, status, colscale, first_factorize, info);
+            basis_factorize_dev(c, basis, status, colscale, first_factorize, S.obj[0] >= S.obj[1], interrupt, user, info);
             first_factorize = false;
             errflag = info->errflag;
+            ended_in_factorize = errflag != 0;
         } else {
             kkt_diag_factorize_dev(c, c->it_xl.get(), c->it_xu.get(), c->it_zl.get(), c->it_zu.get(), comp[1],
                                    prm->precond_dense_cols != 0, &errflag);
@@ -356,8 +375,13 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     }
     if (from_starting_basis) {
         // a later call goes on from the basis this one ended with -- unless it ended inside a Factorize
-        c->sb_live = info->errflag == 0 && info->status_ipm != 8;
+        c->sb_live = info->errflag == 0 && info->status_ipm != 8 && !ended_in_factorize;
         if (c->sb_live) { c->sb_basis = basis; c->sb_status = status; c->sb_lu_generation = lu_generation(c); }
+    }
+    if (use_basis && !from_starting_basis && !first_factorize) {
+        // the basis ipxk_ipm_drop_degenerate works on after a phase that built its own -- unless it ended inside a Factorize
+        c->drv_live = info->errflag == 0 && info->status_ipm != 8 && !ended_in_factorize;
+        if (c->drv_live) { c->drv_basis = basis; c->drv_status = status; c->drv_lu_generation = lu_generation(c); }
     }
     if (use_basis && !first_factorize) {
         if (basis_out) std::copy(basis.begin(), basis.end(), basis_out);

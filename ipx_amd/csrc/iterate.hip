@@ -149,6 +149,11 @@ __global__ __launch_bounds__(kBlock) void iterate_objectives_kernel(int n, int m
     for (int j = blockIdx.x * kBlock + threadIdx.x; j < N; j += gridDim.x * kBlock) {
         const unsigned char st = state[j];
         if (st != IPXK_STATE_FIXED) pobj += c[j] * x[j]; else offset += c[j] * x[j];
+        if (st == IPXK_STATE_IMPLIED_LB || st == IPXK_STATE_IMPLIED_UB) {       // :621-626: the cost of j is decreased by zl - zu
+            const double shift = (zl[j] - zu[j]) * x[j];
+            pobj -= shift;
+            offset += shift;
+        }
         if (has_lb(st)) dobj += lb[j] * zl[j];
         if (has_ub(st)) dobj -= ub[j] * zu[j];
         if (j < m) dobj += b[j] * y[j];

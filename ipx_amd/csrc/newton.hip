@@ -15,7 +15,8 @@ namespace {
 
 __device__ __forceinline__ bool has_lb(unsigned char st) { return st == IPXK_STATE_BARRIER_LB || st == IPXK_STATE_BARRIER_BOXED; }
 __device__ __forceinline__ bool has_ub(unsigned char st) { return st == IPXK_STATE_BARRIER_UB || st == IPXK_STATE_BARRIER_BOXED; }
-__device__ __forceinline__ bool is_barrier(unsigned char st) { return st >= IPXK_STATE_BARRIER_LB; }
+// (the implied states of DropPrimal are treated as free)
+__device__ __forceinline__ bool is_barrier(unsigned char st) { return st >= IPXK_STATE_BARRIER_LB && st <= IPXK_STATE_BARRIER_BOXED; }
 
 // :551-566
 __global__ void newton_rhs_kernel(int N, const double* __restrict__ rc, const double* __restrict__ rl,

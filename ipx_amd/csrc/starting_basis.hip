@@ -273,7 +273,7 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
     const double dependency_tol = std::max(0.0, prm ? prm->dependency_tol : 1e-6);
     const ipxint max_etas = prm ? prm->max_etas : 0;
     ipxk_starting_basis_info I{};
-    c->sb_live = false;
+    c->sb_live = c->drv_live = false;
     maxvol_drop_etas(c);                       // an eta file of an earlier Maxvolume: history, the slack basis is factorized below
     if (!c->maxvol) c->maxvol = new MaxvolState;
     MaxvolState& M = *c->maxvol;

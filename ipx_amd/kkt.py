@@ -22,6 +22,8 @@ INTERRUPT_FN = C.CFUNCTYPE(c_i64, C.c_void_p)
 
 POINTER_HOST, POINTER_DEVICE = 0, 1
 NONBASIC_FIXED, NONBASIC, BASIC, BASIC_FREE = -2, -1, 0, 1
+STATE_FIXED, STATE_FREE, STATE_BARRIER_LB, STATE_BARRIER_UB, STATE_BARRIER_BOXED, STATE_IMPLIED_LB, STATE_IMPLIED_UB = range(7)
+DROP_EXCHANGED, DROP_IMPLIED_LB, DROP_IMPLIED_UB, DROP_FIXED = range(4)
 
 EXPORTS = [
     "ipxk_last_error", "ipxk_device_count", "ipxk_create", "ipxk_destroy", "ipxk_set_pointer_mode",
@@ -40,6 +42,7 @@ EXPORTS = [
     "ipxk_dev_download",
     "ipxk_lp_create", "ipxk_lp_destroy", "ipxk_lp_context", "ipxk_lp_get_model", "ipxk_lp_solve", "ipxk_lp_postsolve", "ipxk_lp_evaluate",
     "ipxk_lp_get_residuals",
+    "ipxk_ipm_set_drop_tolerances", "ipxk_ipm_drop_degenerate", "ipxk_ipm_drop_counts", "ipxk_iterate_get_state",
 ]
 
 
@@ -94,6 +97,12 @@ class StartingBasisInfo(C.Structure):
     _fields_ = [("errflag", c_i64), ("dependent_rows", c_i64), ("dependent_cols", c_i64), ("rows_inconsistent", c_i64),
                 ("cols_inconsistent", c_i64), ("updates_start", c_i64), ("stability_pivots", c_i64),
                 ("factorizations", c_i64), ("seconds", c_f64)]
+
+
+class DropInfo(C.Structure):
+    _fields_ = [("errflag", c_i64), ("primal_candidates", c_i64), ("dual_candidates", c_i64), ("primal_dropped", c_i64),
+                ("dual_dropped", c_i64), ("updates", c_i64), ("refused", c_i64), ("factorizations", c_i64),
+                ("seconds", c_f64)]
 
 
 class SolveParams(C.Structure):
@@ -652,6 +661,36 @@ class KktContext:
 
     def ipm_set_crossover_start(self, value):
         self._check(self.lib.ipxk_ipm_set_crossover_start(self.h, c_f64(value)))
+
+    def ipm_set_drop_tolerances(self, drop_primal, drop_dual):
+        """Control::ipm_drop_primal / ipm_drop_dual for the main phase (0, 0: off)"""
+        self._check(self.lib.ipxk_ipm_set_drop_tolerances(self.h, c_f64(drop_primal), c_f64(drop_dual)))
+
+    def ipm_drop_degenerate(self, b, c, lb, ub, log_cap=100000, interrupt=None):
+        """One DropPrimal + DropDual pass on the resident iterate and the context's live basis.  Returns the info fields
+        plus the basis, the statuses, the scaling factors read back from the device and the decision log (variable, action, partner)."""
+        info = DropInfo()
+        basis, status = np.zeros(self.m, i64), np.zeros(self.n + self.m, i64)
+        log = np.zeros(3 * max(log_cap, 1), i64)
+        colscale = np.zeros(self.n + self.m, f64)
+        cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
+        self._check(self.lib.ipxk_ipm_drop_degenerate(self.h, _fp(_F(b)), _fp(_F(c)), _fp(_F(lb)), _fp(_F(ub)), C.byref(info),
+                                                      _ip(basis), _ip(status), _fp(colscale), _ip(log), c_i64(log_cap), cb, None))
+        out = {name: getattr(info, name) for name, _ in DropInfo._fields_}
+        decisions = info.updates + info.primal_dropped + info.dual_dropped
+        out.update(basis=basis, status=status, colscale=colscale, log=log[: 3 * min(decisions, log_cap)].reshape(-1, 3))
+        return out
+
+    def ipm_drop_counts(self):
+        """(primal_dropped, dual_dropped, drop_updates) since the last ipm_driver_basis / ipm_solve began"""
+        p, d, u = c_i64(0), c_i64(0), c_i64(0)
+        self._check(self.lib.ipxk_ipm_drop_counts(self.h, C.byref(p), C.byref(d), C.byref(u)))
+        return int(p.value), int(d.value), int(u.value)
+
+    def iterate_get_state(self):
+        st = np.zeros(self.n + self.m, np.uint8)
+        self._check(self.lib.ipxk_iterate_get_state(self.h, st.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return st
 
     def iterate_drop_to_complementarity(self, lb, ub):
         """Iterate::DropToComplementarity of the postprocessed iterate: (x, y, z), host vectors"""
