@@ -12,7 +12,8 @@
 // the fixed slacks out of the slack basis, which is where the main phase goes on.
 // With 2 as the fourth argument the program makes ONE call instead, ipxk_ipm_solve (LpSolver::InteriorPointSolve: starting
 // point, initial iterations, starting basis, main phase, postprocessing), and prints the evaluation of the postprocessed
-// iterate -- the reference's interior solution -- and the dropping residuals crossover would start from.
+// iterate -- the reference's interior solution -- and the dropping residuals crossover starts from (crossover_start = 1e-8);
+// then ipxk_crossover_run turns it into a vertex in solver form and the pushes, pivots, status and infeasibilities are printed.
 // A sixth argument t > 0 sets both drop tolerances (ipxk_ipm_set_drop_tolerances; the reference's default is 1e-9): the main
 // phase then takes nearly degenerate variables out of the barrier problem before every Maxvolume, and the counts are printed.
 //
@@ -77,10 +78,11 @@ int main(int argc, char** argv) {
     };
     if (argc > 4 && std::atoi(argv[4]) == 2) {           // the whole interior point solve in one call
         ipxk_solve_params prm{};
-        prm.kkt_tol = 0.3; prm.feasibility_tol = 1e-6; prm.optimality_tol = 1e-8; prm.crossover_start = 0.0;
+        prm.kkt_tol = 0.3; prm.feasibility_tol = 1e-6; prm.optimality_tol = 1e-8; prm.crossover_start = 1e-8;
         prm.dependency_tol = 1e-6; prm.ipm_maxiter = 300; prm.switchiter = -1; prm.max_etas = 100; prm.precond_dense_cols = 1;
         ipxk_solve_info info;
-        CHECK(ipxk_ipm_solve(ctx, b.data(), c.data(), lb.data(), ub.data(), &prm, &info, nullptr, nullptr, nullptr, nullptr));
+        std::vector<ipxint> basis(m), status(N);
+        CHECK(ipxk_ipm_solve(ctx, b.data(), c.data(), lb.data(), ub.data(), &prm, &info, basis.data(), status.data(), nullptr, nullptr));
         std::printf("solve: status %ld after %ld iterations (%ld initial, ended by status %ld), %ld CR iterations, %ld exchanges for the "
                     "starting basis, %ld basis updates, %ld dependent rows, %ld dependent columns\n", (long)info.status_ipm, (long)info.iter,
                     (long)info.iter_initial, (long)info.status_initial, (long)info.kktiter, (long)info.updates_start, (long)info.basis_updates,
@@ -89,8 +91,21 @@ int main(int argc, char** argv) {
                     "dropping residuals %.2e %.2e\n", info.pobjective, info.dobjective, info.rel_objgap, info.rel_presidual,
                     info.rel_dresidual, info.pres_dropping, info.dres_dropping);
         print_drops();
+        if (info.status_ipm != 1) { ipxk_destroy(ctx); return 1; }
+        // crossover in solver form from the postprocessed iterate and the last basis: push phases, then the basic solution
+        ipxk_crossover_info cross;
+        std::vector<double> xv(N), yv(m), zv(N);
+        std::vector<ipxint> basic_statuses(N);
+        CHECK(ipxk_crossover_run(ctx, b.data(), c.data(), lb.data(), ub.data(), nullptr, basis.data(), nullptr, &cross, xv.data(), yv.data(),
+                                 zv.data(), basic_statuses.data(), nullptr, 0, nullptr, nullptr));
+        double objective = 0.0;
+        for (ipxint j = 0; j < N; j++) objective += c[j] * xv[j];
+        std::printf("crossover: status %ld, %ld dual pushes (%ld pivots, %.3f s), %ld primal pushes (%ld pivots, %.3f s); vertex objective "
+                    "%.10e, primal infeasibility %.2e, dual infeasibility %.2e\n", (long)cross.status_crossover, (long)cross.dual_pushes,
+                    (long)cross.dual_pivots, cross.seconds_dual, (long)cross.primal_pushes, (long)cross.primal_pivots, cross.seconds_primal,
+                    objective, cross.primal_infeas, cross.dual_infeas);
         ipxk_destroy(ctx);
-        return info.status_ipm == 1 ? 0 : 1;
+        return cross.status_crossover == 1 ? 0 : 1;
     }
     // interior start away from the solution: x = xl = 1, y = 0, zl = 1 (all variables have a lower bound only)
     std::vector<double> x(N, 1.0), xl(N, 1.0), xu(N, INFINITY), y(m, 0.0), zl(N, 1.0), zu(N, 0.0);

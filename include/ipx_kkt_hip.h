@@ -843,7 +843,81 @@ int ipxk_ipm_set_crossover_start(ipxk_context* ctx, double value);
 int ipxk_iterate_drop_to_complementarity(ipxk_context* ctx, const double* lb, const double* ub,
                                          double* x_out, double* y_out, double* z_out);
 
-/* LpSolver::InteriorPointSolve (src/lp_solver.cc:305-462) without presolve, postsolve and crossover, in one call:
+/* ---- crossover in solver form (src/crossover.cc, src/basis.cc:324-351, src/lp_solver.cc:464-537) ---------------
+ * The two push phases, Basis::ComputeBasicSolution and the call that strings them together, on the device basis
+ * (FTRAN, BTRAN, the eta file, Basis::ExchangeIfStable with the pivot-tolerance ladder).  Out of scope:
+ * Presolver::PostsolveBasicSolution / PostsolveBasis, UserModel::EvaluateBasicPoint (the vertex stays in solver form),
+ * the ipxk_lp_* calls and partitioned contexts: all four calls are refused on any partitioned context.
+ * Conventions of all four:
+ *   basis[m] (host) is given; crossover only distinguishes basic from nonbasic, so NONBASIC_FIXED counts as nonbasic
+ *     and the tableau row is taken without ignore_fixed.  Each call factorizes the given basis at entry (unit scaling
+ *     factors) and depends on no live basis.  On return basis holds the final basis and the context fresh factors of
+ *     it (ipxk_solve_dense solves with it).
+ *   x, z [n+m], y [m] are in/out and follow the pointer mode; lb, ub, b, c are in the forms of ipxk_ipm_driver.
+ *     variables (host) lists the candidates in the order they are pushed; fixed_at_bound (host bytes, may be NULL).
+ *   Per candidate one block of scalars reaches the host.  An exchange refused as unstable (refactorization, tighter
+ *     pivot tolerance) tries the same candidate again, as crossover.cc:165-166, :291-292.
+ *   The interrupt is polled once per candidate: 999 gives status_crossover 5 (time_limit) with errflag 0; 301 / 306
+ *     from the basis give 8 (failed); otherwise 1.  What has been pushed stays pushed.
+ *   The reference's logic_error checks are IPXK_E_ARGUMENT, counted on the device before any push: a listed variable of
+ *     the wrong kind, x outside [lb, ub], a fixed-at-bound variable off its bounds, a z that violates its sign restriction
+ *     (bit 1: x != ub, z >= 0; bit 2: x != lb, z <= 0).
+ *   The ratio tests are order free.  The reference's first pass shrinks the step entry by entry; in exact arithmetic
+ *     its result is the candidate ratio of least magnitude among the entries with |pivot| > 1e-5 (kPivotZeroTol,
+ *     strict) that violate their bound by more than feastol at the FULL step: (z_j +- feastol) / row_j for the dual
+ *     test, (lbbasic_p - xbasic_p - feastol) / pivot and (ubbasic_p - xbasic_p + feastol) / pivot for the primal one.
+ *     That ratio is computed (lowest index among equal magnitudes), then the reference's second pass: the largest |pivot|
+ *     among the entries that block within that step, lowest index among equals.  This equals the reference's loop
+ *     wherever no two candidate ratios lie within rounding of each other, and exactly at exact ties.  Every reduction is a
+ *     fixed-order tree: two calls from the same state give the same bits.
+ * ipxk_crossover_push_dual (:229-357): per candidate jb with z[jb] != 0 the tableau row is formed in one gather pass
+ *   with the first pass of the ratio test fused in and stored; blocked: jn enters, step = z[jn] / row[jn]; then
+ *   y += step btran, z -= step row with the clamps, z[jb] -= step, z[jn] = 0.  x is read only.
+ * ipxk_crossover_push_primal (:73-227): per candidate jn not at a bound (nor free at 0) move_to is the nearer finite
+ *   bound (ties to lb), 0 for a free variable; blocked: the variable at pblock leaves, step from lbbasic / ubbasic (0
+ *   when a fixed-at-bound variable blocks); x[jb] takes exactly its bound, an unblocked x[jn] exactly move_to.
+ * ipxk_crossover_basic_solution (basis.cc:324-351): x_B = inverse(B)(b - N x_N), y = inverse(B')(c_B - z_B),
+ *   z_j = c_j - a_j'y on the nonbasic j; x_N and z_B stay as given.
+ * ipxk_crossover_run (lp_solver.cc:464-537) on the resident POSTPROCESSED iterate: DropToComplementarity; the order
+ *   Sortperm(weights) -- weights[n+m] follows the pointer mode, NULL: Iterate::ScalingFactor of the resident iterate --
+ *   ascending by (weight, index), a stable sort on the device; the dual superbasics (basic, z != 0) in ascending, the
+ *   primal superbasics (nonbasic, off both bounds, not free at 0; screened after the dual phase) in descending order;
+ *   the basic solution; basic_statuses[n+m] (host, may be NULL): IPX_basic 0, IPX_nonbasic_lb -1, IPX_nonbasic_ub -2,
+ *   IPX_superbasic -3 by the rule at :499-512; primal_infeas / dual_infeas of the vertex (src/model.cc:69-97); status 2
+ *   (imprecise) when the first exceeds primal_feastol or the second dual_feastol.  A push phase that does not end optimal
+ *   ends the run there; x_out, y_out, z_out then hold no solution.
+ * log receives the pairs {jb, jn} of the first log_cap pivots (2 log_cap entries). */
+typedef struct ipxk_crossover_params {
+    double primal_feastol;     /* 1e-7; for a dualized model the caller swaps the two (crossover.cc:83-84, :237-238) */
+    double dual_feastol;       /* 1e-7 */
+    ipxint max_etas;           /* 100 */
+} ipxk_crossover_params;       /* NULL: the defaults */
+typedef struct ipxk_crossover_info {
+    ipxint errflag, status_crossover;
+    ipxint dual_superbasics, primal_superbasics;    /* candidates listed */
+    ipxint dual_pushes, dual_pivots, primal_pushes, primal_pivots;   /* Info::updates_crossover = the two pivot counts */
+    ipxint refused;                                 /* exchanges refused as unstable */
+    ipxint factorizations;
+    double primal_infeas, dual_infeas;              /* ipxk_crossover_run: of the vertex */
+    double seconds_dual, seconds_primal;
+} ipxk_crossover_info;
+int ipxk_crossover_push_dual(ipxk_context* ctx, const double* lb, const double* ub, const double* x, double* y, double* z,
+                             const ipxint* variables, ipxint num_variables, ipxint* basis,
+                             const ipxk_crossover_params* params, ipxk_crossover_info* info, ipxint* log, ipxint log_cap,
+                             ipxk_interrupt_fn interrupt, void* interrupt_user);
+int ipxk_crossover_push_primal(ipxk_context* ctx, const double* lb, const double* ub, double* x, const ipxint* variables,
+                               ipxint num_variables, const unsigned char* fixed_at_bound, ipxint* basis,
+                               const ipxk_crossover_params* params, ipxk_crossover_info* info, ipxint* log, ipxint log_cap,
+                               ipxk_interrupt_fn interrupt, void* interrupt_user);
+int ipxk_crossover_basic_solution(ipxk_context* ctx, const double* b, const double* c, const ipxint* basis, double* x,
+                                  double* y, double* z);
+int ipxk_crossover_run(ipxk_context* ctx, const double* b, const double* c, const double* lb, const double* ub,
+                       const double* weights, ipxint* basis, const ipxk_crossover_params* params,
+                       ipxk_crossover_info* info, double* x_out, double* y_out, double* z_out, ipxint* basic_statuses,
+                       ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* interrupt_user);
+
+/* LpSolver::InteriorPointSolve (src/lp_solver.cc:305-462) without presolve, postsolve and crossover (the crossover of
+ * the solver-form result: ipxk_crossover_run), in one call:
  *   1. ipxk_ipm_starting_point (skipped with use_resident_point: the caller has called
  *      ipxk_ipm_load_starting_point, :337-343); a status other than not_run ends the run.
  *   2. RunInitialIPM (:384-420): ipxk_ipm_driver; switchiter < 0: CR cap min(500, 10 + m/20) and limit
@@ -912,8 +986,9 @@ int ipxk_ipm_solve(ipxk_context* ctx, const double* b, const double* c, const do
  * column counts and, below 2^16 entries, the entries for the host layout builders.  The context (ipxk_lp_context)
  * is owned by the lp and unpartitioned; every ipxk_* call works on it.
  * Out of scope: Presolver::PresolveIPMStartingPoint (a caller who has a starting point loads it in solver form with
- * ipxk_ipm_load_starting_point on the lp's context and sets use_resident_point), basic solutions, PostsolveBasis and
- * crossover, and partitioned contexts (after ipxk_comm_init* on the lp's context ipxk_lp_solve returns what
+ * ipxk_ipm_load_starting_point on the lp's context and sets use_resident_point), user-form basic solutions
+ * (PostsolveBasicSolution, PostsolveBasis; crossover exists in solver form only: ipxk_crossover_run on the lp's
+ * context), and partitioned contexts (after ipxk_comm_init* on the lp's context ipxk_lp_solve returns what
  * ipxk_ipm_solve returns on a partitioned context). */
 typedef struct ipxk_lp ipxk_lp;
 typedef struct ipxk_lp_params {

@@ -949,6 +949,101 @@ int ipxk_iterate_drop_to_complementarity(ipxk_context* c, const double* lb, cons
     });
 }
 
+// ---- crossover in solver form (crossover.hip) ------------------------------------------------------------------------
+// an in/out vector: the caller's device memory, or the staging buffer with the host vector in it
+static double* stage_inout(Context* c, double* p, size_t len, DevBuf<double>& buf) {
+    double* d = stage_out(c, p, len, buf);
+    if (d != p) staged_h2d(d, p, len * sizeof(double), c->stream);
+    return d;
+}
+
+int ipxk_crossover_push_dual(ipxk_context* c, const double* lb, const double* ub, const double* x, double* y, double* z,
+                             const ipxint* variables, ipxint num_variables, ipxint* basis, const ipxk_crossover_params* params,
+                             ipxk_crossover_info* info, ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && lb && ub && x && y && z && basis && info && (variables || num_variables == 0), "NULL argument");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
+        IPXK_REQUIRE(num_variables >= 0 && log_cap >= 0 && (log || log_cap == 0), "log is NULL or a negative count");
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        const double* dx = stage_in(c, x, N, c->nw_out[0]);
+        double* dy = stage_inout(c, y, m, c->nw_out[3]);
+        double* dz = stage_inout(c, z, N, c->nw_out[1]);
+        crossover_push_dual_dev(c, dlb, dub, dx, dy, dz, variables, num_variables, basis, params, info, log, log_cap, interrupt, interrupt_user);
+        finish_out(c, y, dy, m);
+        finish_out(c, z, dz, N);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_crossover_push_primal(ipxk_context* c, const double* lb, const double* ub, double* x, const ipxint* variables,
+                               ipxint num_variables, const unsigned char* fixed_at_bound, ipxint* basis,
+                               const ipxk_crossover_params* params, ipxk_crossover_info* info, ipxint* log, ipxint log_cap,
+                               ipxk_interrupt_fn interrupt, void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && lb && ub && x && basis && info && (variables || num_variables == 0), "NULL argument");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
+        IPXK_REQUIRE(num_variables >= 0 && log_cap >= 0 && (log || log_cap == 0), "log is NULL or a negative count");
+        bind_device(c);
+        const size_t N = (size_t)(c->n + c->m);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        double* dx = stage_inout(c, x, N, c->nw_out[0]);
+        crossover_push_primal_dev(c, dlb, dub, dx, variables, num_variables, fixed_at_bound, basis, params, info, log, log_cap, interrupt,
+                                  interrupt_user);
+        finish_out(c, x, dx, N);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_crossover_basic_solution(ipxk_context* c, const double* b, const double* cc, const ipxint* basis, double* x, double* y,
+                                  double* z) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && b && cc && basis && x && y && z, "NULL argument");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* db = stage_in(c, b, m, c->nw_in[0]);
+        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
+        double* dx = stage_inout(c, x, N, c->nw_out[0]);
+        double* dy = stage_out(c, y, m, c->nw_out[3]);
+        double* dz = stage_inout(c, z, N, c->nw_out[1]);
+        crossover_basic_solution_dev(c, db, dc, basis, dx, dy, dz);
+        finish_out(c, x, dx, N);
+        finish_out(c, y, dy, m);
+        finish_out(c, z, dz, N);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_crossover_run(ipxk_context* c, const double* b, const double* cc, const double* lb, const double* ub, const double* weights,
+                       ipxint* basis, const ipxk_crossover_params* params, ipxk_crossover_info* info, double* x_out, double* y_out,
+                       double* z_out, ipxint* basic_statuses, ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt,
+                       void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(c && b && cc && lb && ub && basis && info && x_out && y_out && z_out, "NULL argument");
+        IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
+        IPXK_REQUIRE(log_cap >= 0 && (log || log_cap == 0), "log is NULL");
+        bind_device(c);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        const double* db = stage_in(c, b, m, c->nw_in[0]);
+        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
+        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
+        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        const double* dw = stage_in(c, weights, N, c->nw_in[4]);
+        double* dx = stage_out(c, x_out, N, c->nw_out[0]);
+        double* dy = stage_out(c, y_out, m, c->nw_out[3]);
+        double* dz = stage_out(c, z_out, N, c->nw_out[1]);
+        crossover_run_dev(c, db, dc, dlb, dub, dw, basis, params, info, dx, dy, dz, basic_statuses, log, log_cap, interrupt, interrupt_user);
+        finish_out(c, x_out, dx, N);
+        finish_out(c, y_out, dy, m);
+        finish_out(c, z_out, dz, N);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
 int ipxk_ipm_solve(ipxk_context* c, const double* b, const double* cc, const double* lb, const double* ub,
                    const ipxk_solve_params* params, ipxk_solve_info* info, ipxint* basis_out, ipxint* status_out,
                    ipxk_interrupt_fn interrupt, void* interrupt_user) {

@@ -364,6 +364,21 @@ void ipm_drop_degenerate_dev(Context* c, const double* b, const double* cc, cons
 // the first variable in IPXK_STATE_IMPLIED_* whose xl, xu, zl, zu break Iterate::assert_consistency, -1: none (ipxk_iterate_set)
 int64_t iterate_check_implied_dev(Context* c);
 
+// ---- crossover.hip ----
+// Crossover::PushDual / PushPrimal, Basis::ComputeBasicSolution and LpSolver::RunCrossover in solver form.  Vectors on the device;
+// basis (in/out), variables, fixed_at_bound, statuses_out and log on the host.  Each factorizes the given basis at entry and leaves
+// fresh factors of the basis returned.
+void crossover_push_dual_dev(Context* c, const double* lb, const double* ub, const double* x, double* y, double* z, const ipxint* variables,
+                             ipxint num_variables, ipxint* basis, const ipxk_crossover_params* prm, ipxk_crossover_info* info, ipxint* log,
+                             ipxint log_cap, ipxk_interrupt_fn interrupt, void* user);
+void crossover_push_primal_dev(Context* c, const double* lb, const double* ub, double* x, const ipxint* variables, ipxint num_variables,
+                               const unsigned char* fixed_at_bound, ipxint* basis, const ipxk_crossover_params* prm, ipxk_crossover_info* info,
+                               ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* user);
+void crossover_basic_solution_dev(Context* c, const double* b, const double* cc, const ipxint* basis, double* x, double* y, double* z);
+void crossover_run_dev(Context* c, const double* b, const double* cc, const double* lb, const double* ub, const double* weights, ipxint* basis,
+                       const ipxk_crossover_params* prm, ipxk_crossover_info* info, double* x, double* y, double* z, ipxint* statuses_out,
+                       ipxint* log, ipxint log_cap, ipxk_interrupt_fn interrupt, void* user);
+
 // ---- start.hip ----
 // IPM::ComputeStartingPoint (the model vectors on the device; b, c, lb, ub checked) and IPM::LoadStartingPoint (the
 // six iterate vectors already copied into it_*; lb, ub on the device)

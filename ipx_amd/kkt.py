@@ -38,6 +38,7 @@ EXPORTS = [
     "ipxk_lu_get_factors", "ipxk_lu_generation", "ipxk_split_prepare_lu", "ipxk_maxvolume", "ipxk_ipm_driver_basis",
     "ipxk_ipm_starting_point", "ipxk_ipm_load_starting_point", "ipxk_ipm_starting_basis", "ipxk_iterate_postprocess",
     "ipxk_iterate_dropping_residuals", "ipxk_ipm_set_crossover_start", "ipxk_iterate_drop_to_complementarity", "ipxk_ipm_solve",
+    "ipxk_crossover_push_dual", "ipxk_crossover_push_primal", "ipxk_crossover_basic_solution", "ipxk_crossover_run",
     "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
     "ipxk_dev_download",
     "ipxk_lp_create", "ipxk_lp_destroy", "ipxk_lp_context", "ipxk_lp_get_model", "ipxk_lp_solve", "ipxk_lp_postsolve", "ipxk_lp_evaluate",
@@ -103,6 +104,17 @@ class DropInfo(C.Structure):
     _fields_ = [("errflag", c_i64), ("primal_candidates", c_i64), ("dual_candidates", c_i64), ("primal_dropped", c_i64),
                 ("dual_dropped", c_i64), ("updates", c_i64), ("refused", c_i64), ("factorizations", c_i64),
                 ("seconds", c_f64)]
+
+
+class CrossoverParams(C.Structure):
+    _fields_ = [("primal_feastol", c_f64), ("dual_feastol", c_f64), ("max_etas", c_i64)]
+
+
+class CrossoverInfo(C.Structure):
+    _fields_ = [("errflag", c_i64), ("status_crossover", c_i64), ("dual_superbasics", c_i64), ("primal_superbasics", c_i64),
+                ("dual_pushes", c_i64), ("dual_pivots", c_i64), ("primal_pushes", c_i64), ("primal_pivots", c_i64),
+                ("refused", c_i64), ("factorizations", c_i64), ("primal_infeas", c_f64), ("dual_infeas", c_f64),
+                ("seconds_dual", c_f64), ("seconds_primal", c_f64)]
 
 
 class SolveParams(C.Structure):
@@ -698,6 +710,60 @@ class KktContext:
         x, y, z = np.zeros(N, f64), np.zeros(self.m, f64), np.zeros(N, f64)
         self._check(self.lib.ipxk_iterate_drop_to_complementarity(self.h, _fp(_F(lb)), _fp(_F(ub)), _fp(x), _fp(y), _fp(z)))
         return x, y, z
+
+    # -- crossover in solver form ---------------------------------------------------------------
+    def _crossover_call(self, fn, head, basis, tail, feastol, max_etas, log_cap, interrupt):
+        """the arguments the three crossover calls share; returns the info fields, the basis and the pivot log (jb, jn)"""
+        prm = CrossoverParams(feastol[0], feastol[1], max_etas)
+        info = CrossoverInfo()
+        basis = _I(basis).copy()
+        log = np.zeros(2 * max(log_cap, 1), i64)
+        cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
+        self._check(fn(self.h, *head, _ip(basis), C.byref(prm), C.byref(info), *tail, _ip(log), c_i64(log_cap), cb, None))
+        out = {name: getattr(info, name) for name, _ in CrossoverInfo._fields_}
+        out.update(basis=basis, log=log[: 2 * min(info.dual_pivots + info.primal_pivots, log_cap)].reshape(-1, 2))
+        return out
+
+    def crossover_push_dual(self, lb, ub, x, y, z, variables, basis, feastol=(1e-7, 1e-7), max_etas=100, log_cap=100000,
+                            interrupt=None):
+        """Crossover::PushDual on host vectors: the basic `variables` in the order given.  Returns the info fields plus y, z,
+        the basis and the pivot log."""
+        y, z, var = _F(y).copy(), _F(z).copy(), _I(variables)
+        out = self._crossover_call(self.lib.ipxk_crossover_push_dual,
+                                   [_fp(_F(lb)), _fp(_F(ub)), _fp(_F(x)), _fp(y), _fp(z), _ip(var), c_i64(len(var))], basis, [],
+                                   feastol, max_etas, log_cap, interrupt)
+        out.update(y=y, z=z)
+        return out
+
+    def crossover_push_primal(self, lb, ub, x, variables, basis, fixed_at_bound=None, feastol=(1e-7, 1e-7), max_etas=100,
+                              log_cap=100000, interrupt=None):
+        """Crossover::PushPrimal on host vectors: the nonbasic `variables` in the order given; fixed_at_bound: a flag per
+        variable or None.  Returns the info fields plus x, the basis and the pivot log."""
+        x, var = _F(x).copy(), _I(variables)
+        fixed = None if fixed_at_bound is None else np.ascontiguousarray(fixed_at_bound, dtype=np.uint8)
+        fp = None if fixed is None else fixed.ctypes.data_as(C.POINTER(C.c_ubyte))
+        out = self._crossover_call(self.lib.ipxk_crossover_push_primal,
+                                   [_fp(_F(lb)), _fp(_F(ub)), _fp(x), _ip(var), c_i64(len(var)), fp], basis, [], feastol, max_etas,
+                                   log_cap, interrupt)
+        out.update(x=x)
+        return out
+
+    def crossover_basic_solution(self, b, c, basis, x, y, z):
+        """Basis::ComputeBasicSolution: (x, y, z) with x_B, y, z_N recomputed, x_N and z_B as given"""
+        x, y, z = _F(x).copy(), _F(y).copy(), _F(z).copy()
+        self._check(self.lib.ipxk_crossover_basic_solution(self.h, _fp(_F(b)), _fp(_F(c)), _ip(_I(basis)), _fp(x), _fp(y), _fp(z)))
+        return x, y, z
+
+    def crossover_run(self, b, c, lb, ub, basis, weights=None, feastol=(1e-7, 1e-7), max_etas=100, log_cap=100000, interrupt=None):
+        """LpSolver::RunCrossover in solver form on the resident postprocessed iterate.  Returns the info fields plus the
+        vertex x, y, z, the basis, the basic statuses and the pivot log."""
+        N = self.n + self.m
+        x, y, z = np.zeros(N, f64), np.zeros(self.m, f64), np.zeros(N, f64)
+        statuses = np.zeros(N, i64)
+        out = self._crossover_call(self.lib.ipxk_crossover_run, [_fp(_F(b)), _fp(_F(c)), _fp(_F(lb)), _fp(_F(ub)), _fp(_F(weights))],
+                                   basis, [_fp(x), _fp(y), _fp(z), _ip(statuses)], feastol, max_etas, log_cap, interrupt)
+        out.update(x=x, y=y, z=z, basic_statuses=statuses)
+        return out
 
     def ipm_solve(self, b, c, lb, ub, kkt_tol=0.3, feasibility_tol=1e-6, optimality_tol=1e-8, ipm_maxiter=300, switchiter=-1,
                   precond_dense_cols=True, crossover_start=0.0, dependency_tol=1e-6, max_etas=100, use_resident_point=False,
