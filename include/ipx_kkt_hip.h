@@ -845,9 +845,9 @@ int ipxk_iterate_drop_to_complementarity(ipxk_context* ctx, const double* lb, co
 
 /* ---- crossover in solver form (src/crossover.cc, src/basis.cc:324-351, src/lp_solver.cc:464-537) ---------------
  * The two push phases, Basis::ComputeBasicSolution and the call that strings them together, on the device basis
- * (FTRAN, BTRAN, the eta file, Basis::ExchangeIfStable with the pivot-tolerance ladder).  Out of scope:
- * Presolver::PostsolveBasicSolution / PostsolveBasis, UserModel::EvaluateBasicPoint (the vertex stays in solver form),
- * the ipxk_lp_* calls and partitioned contexts: all four calls are refused on any partitioned context.
+ * (FTRAN, BTRAN, the eta file, Basis::ExchangeIfStable with the pivot-tolerance ladder).  The vertex stays in
+ * solver form here; ipxk_lp_crossover below returns it in the user's terms (Presolver::PostsolveBasicSolution /
+ * PostsolveBasis, UserModel::EvaluateBasicPoint).  Out of scope: partitioned contexts, on which all four calls are refused.
  * Conventions of all four:
  *   basis[m] (host) is given; crossover only distinguishes basic from nonbasic, so NONBASIC_FIXED counts as nonbasic
  *     and the tableau row is taken without ignore_fixed.  Each call factorizes the given basis at entry (unit scaling
@@ -986,10 +986,9 @@ int ipxk_ipm_solve(ipxk_context* ctx, const double* b, const double* c, const do
  * column counts and, below 2^16 entries, the entries for the host layout builders.  The context (ipxk_lp_context)
  * is owned by the lp and unpartitioned; every ipxk_* call works on it.
  * Out of scope: Presolver::PresolveIPMStartingPoint (a caller who has a starting point loads it in solver form with
- * ipxk_ipm_load_starting_point on the lp's context and sets use_resident_point), user-form basic solutions
- * (PostsolveBasicSolution, PostsolveBasis; crossover exists in solver form only: ipxk_crossover_run on the lp's
- * context), and partitioned contexts (after ipxk_comm_init* on the lp's context ipxk_lp_solve returns what
- * ipxk_ipm_solve returns on a partitioned context). */
+ * ipxk_ipm_load_starting_point on the lp's context and sets use_resident_point), Presolver::PresolveStartingPoint (a
+ * user-form basic starting point), and partitioned contexts (after ipxk_comm_init* on the lp's context ipxk_lp_solve
+ * and ipxk_lp_crossover return what ipxk_ipm_solve and ipxk_crossover_run return on a partitioned context). */
 typedef struct ipxk_lp ipxk_lp;
 typedef struct ipxk_lp_params {
     ipxint dualize;            /* -1: num_constr > 2 * num_var, 0: never, 1: always (ipx_parameters::dualize) */
@@ -1013,7 +1012,9 @@ ipxk_context* ipxk_lp_context(ipxk_lp* lp);
  * colscale[n], rowscale[m] (1.0 where the reference's scaling vectors are empty).  Any may be NULL. */
 int ipxk_lp_get_model(ipxk_lp* lp, ipxint* Ap, ipxint* Ai, double* Ax, double* b, double* c,
                       double* lb, double* ub, double* colscale, double* rowscale);
-/* ipxk_ipm_solve on the lp's context with the resident b, c, lb, ub (no basis is returned). */
+/* ipxk_ipm_solve on the lp's context with the resident b, c, lb, ub.  The last basis, if the solve built one, stays
+ * with the lp (ipxk_lp_get_basis, ipxk_lp_crossover); a basic solution stored by an earlier ipxk_lp_crossover is
+ * cleared. */
 int ipxk_lp_solve(ipxk_lp* lp, const ipxk_solve_params* params, ipxk_solve_info* info,
                   ipxk_interrupt_fn interrupt, void* interrupt_user);
 /* Presolver::PostsolveInteriorPoint (src/presolver.cc:618-793) of the context's resident iterate, postprocessed or
@@ -1035,6 +1036,52 @@ typedef struct ipxk_lp_eval {
 } ipxk_lp_eval;
 int ipxk_lp_evaluate(ipxk_lp* lp, ipxk_lp_eval* out);
 int ipxk_lp_get_residuals(ipxk_lp* lp, double* rb, double* rc);
+/* ---- basic solutions in user form (src/presolver.cc:92-116, 566-616, 795-867; src/user_model.cc:173-211) ----
+ * ipxk_lp_postsolve_basic is Presolver::PostsolveBasicSolution of ANY solver-form point: PostsolveGeneralPoint,
+ * PostsolveBasis and CorrectBasicSolution as one map from x_solver, z_solver [n+m], y_solver [m] and
+ * basic_statuses[n+m] (IPX_basic 0, IPX_nonbasic_lb -1, IPX_nonbasic_ub -2, IPX_superbasic -3) to x, z [num_var],
+ * slack, y [num_constr], vbasis[num_var] (the same four values) and cbasis[num_constr] (IPX_basic 0, IPX_nonbasic -1).
+ * The double arrays follow the context's pointer mode, the status arrays are host memory; any output may be NULL.
+ * Every entry is the reference's operation on the reference's operands; the correction writes exactly lb[j], ub[j]
+ * of the user model or 0.0.  Statuses that violate the reference's asserts are refused with IPXK_E_ARGUMENT, found on
+ * the device before anything is written (ipxk_last_error() names the first offending index): a slack variable that is
+ * superbasic, and for a dualized model a boxed variable whose added column is basic while the variable's own slack
+ * is basic too (:822: the variable would be nonbasic twice).  num_constr == 0 is served.
+ *
+ * ipxk_lp_crossover is the tail of LpSolver::Solve after the interior solve (src/lp_solver.cc:64-67, :464-537).  It
+ * needs a preceding ipxk_lp_solve on this lp (IPXK_E_ARGUMENT otherwise).  If that solve did not end with status_ipm
+ * 1 or 2 it returns 0 with status_crossover 0 and nothing else happens.  Otherwise ipxk_crossover_run's body runs on the
+ * resident b, c, lb, ub from the basis the solve left, with the scaling factors of the resident iterate as weights.
+ * params are in the USER's terms: for a dualized model the call swaps primal_feastol and dual_feastol itself
+ * (src/crossover.cc:83-84, :237-238).  With status_crossover 1 the vertex is postsolved, kept in the lp and
+ * evaluated (UserModel::EvaluateBasicPoint: primal_infeas, dual_infeas, objval = obj'x, fixed-order trees over block
+ * partials: the same bits from the same vertex); status_crossover becomes 2 when primal_infeas exceeds the user's
+ * primal_feastol or dual_infeas the dual one (:534-536).  crossover_info->primal_infeas / dual_infeas stay those of
+ * the solver-form vertex.  A push phase that does not end optimal, or an interrupt (status_crossover 5, errflag 0),
+ * leaves no basic solution; basic_eval (may be NULL) is zero then.  An lp with num_constr == 0 is refused with
+ * IPXK_E_ARGUMENT (there is no basis to push on); so is a partitioned context.
+ *
+ * ipxk_lp_evaluate_basic is UserModel::EvaluateBasicPoint on its own, of any user-form point: x, z [num_var], slack, y
+ * [num_constr] follow the pointer mode, vbasis[num_var] is host memory; none may be NULL (slack and y may with num_constr
+ * == 0).  Two calls on the same point give the same bits.
+ *
+ * ipxk_lp_get_basic_solution copies out the stored vertex (IPXK_E_ARGUMENT when there is none, where
+ * LpSolver::GetBasicSolution returns -1); ipxk_lp_get_basis is LpSolver::GetBasis: the vertex's statuses if one is
+ * stored, else BuildBasicStatuses (:212-231) of the last solve's basis through PostsolveBasis, else IPXK_E_ARGUMENT.
+ * Doubles follow the pointer mode, statuses are host arrays, any may be NULL. */
+typedef struct ipxk_lp_basic_eval {
+    double primal_infeas, dual_infeas, objval;
+} ipxk_lp_basic_eval;
+int ipxk_lp_postsolve_basic(ipxk_lp* lp, const double* x_solver, const double* y_solver, const double* z_solver,
+                            const ipxint* basic_statuses, double* x, double* slack, double* y, double* z,
+                            ipxint* cbasis, ipxint* vbasis);
+int ipxk_lp_crossover(ipxk_lp* lp, const ipxk_crossover_params* params, ipxk_crossover_info* crossover_info,
+                      ipxk_lp_basic_eval* basic_eval, ipxk_interrupt_fn interrupt, void* interrupt_user);
+int ipxk_lp_evaluate_basic(ipxk_lp* lp, const double* x, const double* slack, const double* y, const double* z,
+                           const ipxint* vbasis, ipxk_lp_basic_eval* out);
+int ipxk_lp_get_basic_solution(ipxk_lp* lp, double* x, double* slack, double* y, double* z, ipxint* cbasis,
+                               ipxint* vbasis);
+int ipxk_lp_get_basis(ipxk_lp* lp, ipxint* cbasis, ipxint* vbasis);
 
 /* ---- multi-GPU: rows of AI partitioned over ranks, one RCCL all-reduce per
  *      NormalMatrix apply ---------------------------- */

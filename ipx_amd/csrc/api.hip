@@ -1173,6 +1173,85 @@ int ipxk_lp_get_residuals(ipxk_lp* lp, double* rb, double* rc) {
     });
 }
 
+int ipxk_lp_postsolve_basic(ipxk_lp* lp, const double* x_solver, const double* y_solver, const double* z_solver, const ipxint* basic_statuses,
+                            double* x, double* slack, double* y, double* z, ipxint* cbasis, ipxint* vbasis) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp && x_solver && z_solver && basic_statuses, "NULL argument");
+        Context* c = lp_context(lp->p);
+        IPXK_REQUIRE(y_solver || c->m == 0, "NULL argument");
+        bind_device(c);
+        int64_t num_constr = 0, num_var = 0;
+        lp_dims(lp->p, &num_constr, &num_var);
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m), nc = (size_t)num_constr, nv = (size_t)num_var;
+        const double* dxs = stage_in(c, x_solver, N, c->nw_in[0]);
+        const double* dys = stage_in(c, y_solver, m, c->nw_in[1]);
+        const double* dzs = stage_in(c, z_solver, N, c->nw_in[2]);
+        const LpBasicPoint out{stage_out(c, x, nv, c->nw_out[0]), stage_out(c, slack, nc, c->nw_out[1]), stage_out(c, y, nc, c->nw_out[2]),
+                               stage_out(c, z, nv, c->nw_out[3]), cbasis, vbasis};
+        lp_postsolve_basic(lp->p, dxs, dys, dzs, basic_statuses, out);
+        finish_out(c, x, out.x, nv);
+        finish_out(c, slack, out.slack, nc);
+        finish_out(c, y, out.y, nc);
+        finish_out(c, z, out.z, nv);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_lp_crossover(ipxk_lp* lp, const ipxk_crossover_params* params, ipxk_crossover_info* crossover_info, ipxk_lp_basic_eval* basic_eval,
+                      ipxk_interrupt_fn interrupt, void* interrupt_user) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp && crossover_info, "NULL argument");
+        bind_device(lp_context(lp->p));
+        lp_crossover(lp->p, params, crossover_info, basic_eval, interrupt, interrupt_user);
+    });
+}
+
+int ipxk_lp_evaluate_basic(ipxk_lp* lp, const double* x, const double* slack, const double* y, const double* z, const ipxint* vbasis,
+                           ipxk_lp_basic_eval* out) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp && x && z && vbasis && out, "NULL argument");
+        Context* c = lp_context(lp->p);
+        bind_device(c);
+        int64_t num_constr = 0, num_var = 0;
+        lp_dims(lp->p, &num_constr, &num_var);
+        IPXK_REQUIRE((slack && y) || num_constr == 0, "NULL argument");
+        const size_t nc = (size_t)num_constr, nv = (size_t)num_var;
+        const double* dx = stage_in(c, x, nv, c->nw_in[0]);
+        const double* ds = stage_in(c, slack, nc, c->nw_in[1]);
+        const double* dy = stage_in(c, y, nc, c->nw_in[2]);
+        const double* dz = stage_in(c, z, nv, c->nw_in[3]);
+        lp_evaluate_basic(lp->p, dx, ds, dy, dz, vbasis, out);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_lp_get_basic_solution(ipxk_lp* lp, double* x, double* slack, double* y, double* z, ipxint* cbasis, ipxint* vbasis) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp, "NULL argument");
+        Context* c = lp_context(lp->p);
+        bind_device(c);
+        const double* src[4];
+        const ipxint *cb = nullptr, *vb = nullptr;
+        lp_basic_solution(lp->p, src, &cb, &vb);
+        int64_t num_constr = 0, num_var = 0;
+        lp_dims(lp->p, &num_constr, &num_var);
+        double* dst[4] = {x, slack, y, z};
+        for (int k = 0; k < 4; k++)
+            if (dst[k]) copy_out(c, dst[k], src[k], (size_t)(k == 1 || k == 2 ? num_constr : num_var) * sizeof(double));
+        if (cbasis) std::copy(cb, cb + num_constr, cbasis);
+        if (vbasis) std::copy(vb, vb + num_var, vbasis);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
+int ipxk_lp_get_basis(ipxk_lp* lp, ipxint* cbasis, ipxint* vbasis) {
+    return guarded([&] {
+        IPXK_REQUIRE(lp, "NULL argument");
+        bind_device(lp_context(lp->p));
+        lp_get_basis(lp->p, cbasis, vbasis);
+    });
+}
+
 int ipxk_lu_factorize(ipxk_context* c, ipxint dim, const ipxint* Bbegin, const ipxint* Bend, const ipxint* Bi,
                       const double* Bx, double pivottol, int strict_abs_pivottol, ipxk_lu_info* info) {
     return guarded([&] {

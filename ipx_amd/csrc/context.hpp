@@ -476,6 +476,18 @@ void lp_postsolve_dev(Lp* lp, const double* out[7]);
 void lp_dims(const Lp* lp, int64_t* num_constr, int64_t* num_var);
 void lp_evaluate(Lp* lp, ipxk_lp_eval* out);
 void lp_get_residuals(Lp* lp, double* rb, double* rc);
+// Presolver::PostsolveBasicSolution of a solver-form point: doubles on the device, statuses on the host; outputs may be null
+struct LpBasicPoint { double *x, *slack, *y, *z; ipxint *cbasis, *vbasis; };
+void lp_postsolve_basic(Lp* lp, const double* x_solver, const double* y_solver, const double* z_solver, const ipxint* statuses,
+                        const LpBasicPoint& out);
+void lp_crossover(Lp* lp, const ipxk_crossover_params* prm, ipxk_crossover_info* info, ipxk_lp_basic_eval* eval,
+                  ipxk_interrupt_fn interrupt, void* user);
+// UserModel::EvaluateBasicPoint of a user-form point: doubles on the device, vbasis on the host
+void lp_evaluate_basic(Lp* lp, const double* x, const double* slack, const double* y, const double* z, const ipxint* vbasis,
+                       ipxk_lp_basic_eval* out);
+// the stored vertex, on the device (x, slack, y, z) and on the host (cbasis, vbasis); throws when there is none
+void lp_basic_solution(Lp* lp, const double* out[4], const ipxint** cbasis, const ipxint** vbasis);
+void lp_get_basis(Lp* lp, ipxint* cbasis, ipxint* vbasis);
 
 // ---- comm.hip ----
 void comm_allreduce_sum(Context* c, double* buf, size_t count);

@@ -5,6 +5,9 @@
 //   Presolver::LoadPrimal / LoadDual / ScaleModel         :135-180, :182-264, :266-292
 //   Presolver::PostsolveInteriorPoint                     :618-793
 //   UserModel::EvaluateInteriorPoint / ComputeNorms       src/user_model.cc:99-171, :306-316
+//   Presolver::PostsolveBasicSolution / PostsolveBasis    src/presolver.cc:92-116, :566-616, :795-867
+//   UserModel::EvaluateBasicPoint                         src/user_model.cc:173-211
+//   LpSolver::RunCrossover's tail, GetBasis               src/lp_solver.cc:64-67, :212-244, :524-536
 // The caller's arrays are uploaded once; validation, the attributes, the solver form, its scaling and the context's matrix
 // are built from the resident copies, and only scalars, counts and the flag / result blocks come back to the host.  The
 // solver form is sign flips, copies and powers of two, so it equals the reference's bit for bit; the postsolve applies
@@ -33,6 +36,17 @@ struct Lp {
     // the postsolved point (x, xl, xu, zl, zu [num_var]; slack, y [num_constr]) and the evaluation's residuals and partials
     DevBuf<double> px, pxl, pxu, pslack, py, pzl, pzu, rb, rc, part, result;
     bool evaluated = false;
+    // the last ipxk_lp_solve: whether there was one, its status, and the basis it left (empty: none was built)
+    bool solved = false;
+    ipxint status_ipm = 0;
+    std::vector<ipxint> basis;
+    // the basic solution of the last ipxk_lp_crossover: x, z [num_var], slack, y [num_constr]; its statuses on the host
+    DevBuf<double> vx, vslack, vy, vz;
+    std::vector<ipxint> cbasis, vbasis;
+    bool has_vertex = false;
+    // work space of the basic postsolve: the solver-form statuses and the user-form ones, the first violations of the asserts
+    DevBuf<ipxint> st_solver, st_cbasis, st_vbasis;
+    DevBuf<long long> st_part, st_first;
     ~Lp() { if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); delete ctx; } }
 };
 
@@ -369,6 +383,130 @@ __global__ __launch_bounds__(kBlock) void evaluate_finish_kernel(int grid_rows, 
     }
 }
 
+// ---- PostsolveBasicSolution (:92-101) = PostsolveGeneralPoint (:566-616) + PostsolveBasis (:795-845) + CorrectBasicSolution
+// (:847-867) ----
+constexpr ipxint kBasic = 0, kNonbasic = -1, kNonbasicLb = -1, kNonbasicUb = -2, kSuperbasic = -3;      // include/ipx_status.h
+struct SolverPoint { const double *x, *y, *z; const ipxint* st; };      // x, z, st [n + m], y [m]
+struct BasicPoint { double *x, *slack, *y, *z; ipxint *cbasis, *vbasis; };       // any of the four doubles may be null
+
+// The asserts of PostsolveBasis, by first index.  Slot 0: a slack variable that is superbasic (:812, :836).  Slot 1 (dualized):
+// a boxed variable, by its place in the list, whose added column is basic although its own slack is basic too, which has made
+// it nonbasic already (:822).  (:826 cannot fail: a flipped variable is not boxed.)
+__global__ __launch_bounds__(kBlock) void check_statuses_kernel(int64_t n, int64_t m, int64_t nc, int64_t nb, const ipxint* __restrict__ st,
+                                                                const int* __restrict__ boxed, long long* part) {
+    long long f0 = kNoIndex, f1 = kNoIndex;
+    IPXK_GRID_STRIDE(i, m) if (st[n + i] == kSuperbasic) note(f0, i);
+    IPXK_GRID_STRIDE(k, nb) if (st[nc + k] == kBasic && st[n + boxed[k]] == kBasic) note(f1, k);
+    put_first(part, 0, f0); put_first(part, 1, f1);
+}
+// primal form: n = nv, m = nc; the three steps of an entry in one pass (the correction owns x where vbasis is -1 / -2, z where it
+// is basic, slack where cbasis is nonbasic and y where it is basic)
+__global__ void postsolve_basic_primal_kernel(int64_t nc, int64_t nv, SolverPoint s, const double* __restrict__ cs, const double* __restrict__ rs,
+                                              const double* __restrict__ lbu, const double* __restrict__ ubu, BasicPoint u) {
+    IPXK_GRID_STRIDE(j, nv) {
+        const ipxint vb = s.st[j];
+        if (u.x) u.x[j] = vb == kNonbasicLb ? lbu[j] : vb == kNonbasicUb ? ubu[j] : s.x[j] * cs[j];
+        if (u.z) u.z[j] = vb == kBasic ? 0.0 : s.z[j] / cs[j];
+        u.vbasis[j] = vb;
+    }
+    IPXK_GRID_STRIDE(i, nc) {
+        const ipxint cb = s.st[nv + i] == kBasic ? kBasic : kNonbasic;
+        if (u.slack) u.slack[i] = cb == kNonbasic ? 0.0 : s.x[nv + i] / rs[i];
+        if (u.y) u.y[i] = cb == kBasic ? 0.0 : s.y[i] * rs[i];
+        u.cbasis[i] = cb;
+    }
+}
+// dualized form without the boxed and flipped variables: n = nc + nb, m = nv.  The rows are final here (cbasis depends on
+// nothing else); x, z and vbasis of the variables wait for the two lists and are corrected after them.
+__global__ void postsolve_basic_dual_kernel(int64_t nc, int64_t nb, int64_t nv, SolverPoint s, const double* __restrict__ lb,
+                                            const double* __restrict__ ub, const double* __restrict__ cs, const double* __restrict__ rs,
+                                            BasicPoint u) {
+    const int64_t n = nc + nb;
+    IPXK_GRID_STRIDE(j, nv) {
+        if (u.x) u.x[j] = -s.y[j] * rs[j];
+        if (u.z) u.z[j] = s.x[n + j] / rs[j];
+        u.vbasis[j] = s.st[n + j] != kBasic ? kBasic : lb[n + j] != ub[n + j] ? kNonbasicLb : kSuperbasic;
+    }
+    IPXK_GRID_STRIDE(i, nc) {
+        const ipxint cb = s.st[i] == kBasic ? kNonbasic : kBasic;
+        if (u.slack) u.slack[i] = cb == kNonbasic ? 0.0 : -s.z[i] / cs[i];
+        if (u.y) u.y[i] = cb == kBasic ? 0.0 : s.x[i] * cs[i];
+        u.cbasis[i] = cb;
+    }
+}
+// :587-591, :819-824.  colscale is a power of two, so the product is exact and a fused multiply-add, were this file built with
+// contraction, would give the bits of the reference's multiply and subtract.
+__global__ void postsolve_basic_boxed_kernel(int64_t nc, int64_t nb, SolverPoint s, const int* __restrict__ boxed, const double* __restrict__ cs,
+                                             BasicPoint u) {
+    IPXK_GRID_STRIDE(k, nb) {
+        const int j = boxed[k];
+        if (u.z) u.z[j] -= s.x[nc + k] * cs[nc + k];
+        if (s.st[nc + k] == kBasic) u.vbasis[j] = kNonbasicUb;
+    }
+}
+// :593-596, :825-829
+__global__ void postsolve_basic_flipped_kernel(int64_t nf, const int* __restrict__ flipped, BasicPoint u) {
+    IPXK_GRID_STRIDE(f, nf) {
+        const int j = flipped[f];
+        if (u.x) u.x[j] *= -1.0;
+        if (u.z) u.z[j] *= -1.0;
+        if (u.vbasis[j] == kNonbasicLb) u.vbasis[j] = kNonbasicUb;
+    }
+}
+// CorrectBasicSolution's loop over the variables, once vbasis is final
+__global__ void correct_basic_kernel(int64_t nv, const double* __restrict__ lbu, const double* __restrict__ ubu, BasicPoint u) {
+    IPXK_GRID_STRIDE(j, nv) {
+        const ipxint vb = u.vbasis[j];
+        if (u.x && vb == kNonbasicLb) u.x[j] = lbu[j];
+        if (u.x && vb == kNonbasicUb) u.x[j] = ubu[j];
+        if (u.z && vb == kBasic) u.z[j] = 0.0;
+    }
+}
+// BuildBasicStatuses (src/lp_solver.cc:212-231): the nonbasic statuses from the solver form's bounds, then the basis over them
+__global__ void nonbasic_statuses_kernel(int64_t N, const double* __restrict__ lb, const double* __restrict__ ub, ipxint* __restrict__ st) {
+    IPXK_GRID_STRIDE(k, N) st[k] = isfinite(lb[k]) ? kNonbasicLb : isfinite(ub[k]) ? kNonbasicUb : kSuperbasic;
+}
+__global__ void basic_statuses_kernel(int64_t m, const ipxint* __restrict__ basis, ipxint* __restrict__ st) {
+    IPXK_GRID_STRIDE(p, m) st[basis[p]] = kBasic;
+}
+
+// ---- EvaluateBasicPoint (src/user_model.cc:173-211) ----
+enum BasicSlot { kBasicPrimal, kBasicDual, kBasicObjX, kNumBasicSlots };
+__device__ __forceinline__ double std_max(double a, double b) { return a < b ? b : a; }      // std::max: a NaN on the right is dropped
+__global__ __launch_bounds__(kBlock) void evaluate_basic_kernel(int64_t nc, int64_t nv, const double* __restrict__ lbu, const double* __restrict__ ubu,
+                                                                const double* __restrict__ obj, const unsigned char* __restrict__ ctype,
+                                                                const double* __restrict__ x, const double* __restrict__ slack,
+                                                                const double* __restrict__ y, const double* __restrict__ z,
+                                                                const ipxint* __restrict__ vbasis, double* part) {
+    __shared__ double scratch[kBlock / 64 + 1];
+    double pinf = 0.0, dinf = 0.0, obj_x = 0.0;
+    IPXK_GRID_STRIDE(j, nv) {
+        pinf = std_max(pinf, lbu[j] - x[j]);
+        pinf = std_max(pinf, x[j] - ubu[j]);
+        if (vbasis[j] != kNonbasicLb) dinf = std_max(dinf, z[j]);
+        if (vbasis[j] != kNonbasicUb) dinf = std_max(dinf, -z[j]);
+        obj_x += obj[j] * x[j];
+    }
+    IPXK_GRID_STRIDE(i, nc) {
+        const unsigned char t = ctype[i];
+        if (t == '<') { pinf = std_max(pinf, -slack[i]); dinf = std_max(dinf, y[i]); }
+        else if (t == '>') { pinf = std_max(pinf, slack[i]); dinf = std_max(dinf, -y[i]); }
+        else pinf = std_max(pinf, fabs(slack[i]));
+    }
+    put_partial(part, kBasicPrimal, pinf, true, scratch);
+    put_partial(part, kBasicDual, dinf, true, scratch);
+    put_partial(part, kBasicObjX, obj_x, false, scratch);
+}
+// one workgroup: the three slots' partials in fixed order
+__global__ __launch_bounds__(kBlock) void evaluate_basic_finish_kernel(int grid, const double* __restrict__ part, double* result) {
+    __shared__ double scratch[kBlock / 64 + 1];
+    for (int slot = 0; slot < kNumBasicSlots; slot++) {
+        const PartRef ref{part + slot * kEvalGrid, grid, 1};
+        const double v = slot == kBasicObjX ? reduce_partials<SumOp>(ref, scratch) : reduce_partials<MaxOp>(ref, scratch);
+        if (threadIdx.x == 0) result[slot] = v;
+    }
+}
+
 // exclusive prefix sums of a 0/1 mask, the number of ones into *count (device) and their indices, ascending, into list
 void list_of_mask(Tmp& T, int64_t len, const int* mask, int* pos, int* count, int* list, hipStream_t s) {
     if (len > 0) scan_int(T, mask, pos, (size_t)len, s);
@@ -593,8 +731,14 @@ void lp_solve(Lp* lp, const ipxk_solve_params* prm, ipxk_solve_info* info, ipxk_
     Context* c = lp->ctx;
     IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
     lp->evaluated = false;
-    ipm_solve_dev(c, lp->b.get(), lp->c.get(), lp->lb.get(), lp->ub.get(), prm, info, nullptr, nullptr, interrupt, user);
+    lp->solved = lp->has_vertex = false;           // ClearSolution (src/lp_solver.cc:54)
+    lp->basis.clear();
+    std::vector<ipxint> basis((size_t)c->m, -1);   // (stays -1 when the solve ends before it has a basis)
+    ipm_solve_dev(c, lp->b.get(), lp->c.get(), lp->lb.get(), lp->ub.get(), prm, info, basis.data(), nullptr, interrupt, user);
     IPXK_HIP(hipStreamSynchronize(c->stream));
+    lp->solved = true;
+    lp->status_ipm = info->status_ipm;
+    if (!basis.empty() && basis[0] >= 0) lp->basis = std::move(basis);
 }
 
 void lp_postsolve_dev(Lp* lp, const double* out[7]) {
@@ -663,6 +807,163 @@ void lp_get_residuals(Lp* lp, double* rb, double* rc) {
     if (rb) lp->rb.download(rb, (size_t)lp->num_constr, s);
     if (rc) lp->rc.download(rc, (size_t)lp->num_var, s);
     IPXK_HIP(hipStreamSynchronize(s));
+}
+
+namespace {
+
+// the map on device statuses (lp->st_solver) into u, whose cbasis and vbasis are device arrays; refuses before it writes
+void postsolve_basic_dev(Lp* lp, const double* x, const double* y, const double* z, const BasicPoint& u) {
+    Context* c = lp->ctx;
+    hipStream_t s = c->stream;
+    const int64_t nc = lp->num_constr, nv = lp->num_var, nb = lp->dualized ? lp->num_boxed : 0, nf = lp->num_flipped, m = c->m, n = c->n;
+    const SolverPoint pt{x, y, z, lp->st_solver.get()};
+    lp->st_part.ensure((size_t)2 * kFlagGrid); lp->st_first.ensure(2);
+    hipLaunchKernelGGL(fill_kernel<long long>, dim3(gridn(2 * kFlagGrid)), dim3(kBlock), 0, s, (int64_t)2 * kFlagGrid, kNoIndex, lp->st_part.get());
+    hipLaunchKernelGGL(check_statuses_kernel, dim3(grid_for(std::max(m, nb), kFlagGrid)), dim3(kBlock), 0, s, n, m, nc, nb, pt.st,
+                       lp->boxed.get(), lp->st_part.get());
+    hipLaunchKernelGGL(first_index_kernel, dim3(2), dim3(kBlock), 0, s, lp->st_part.get(), lp->st_first.get());
+    long long first[2];
+    lp->st_first.download(first, 2, s);
+    IPXK_HIP(hipGetLastError());
+    char buf[256];
+    if (first[0] != kNoIndex) {
+        snprintf(buf, sizeof buf, "basic_statuses: a slack variable cannot be superbasic, first at slack %lld", first[0]);
+        throw Error(IPXK_E_ARGUMENT, buf);
+    }
+    if (first[1] != kNoIndex) {
+        snprintf(buf, sizeof buf, "basic_statuses: the added column of a boxed variable is basic and so is the variable's slack, "
+                 "first at boxed variable number %lld", first[1]);
+        throw Error(IPXK_E_ARGUMENT, buf);
+    }
+    const int grid = gridn(std::max(nc, nv));
+    if (!lp->dualized) {
+        hipLaunchKernelGGL(postsolve_basic_primal_kernel, dim3(grid), dim3(kBlock), 0, s, nc, nv, pt, lp->colscale.get(), lp->rowscale.get(),
+                           lp->lbu.get(), lp->ubu.get(), u);
+    } else {
+        hipLaunchKernelGGL(postsolve_basic_dual_kernel, dim3(grid), dim3(kBlock), 0, s, nc, nb, nv, pt, lp->lb.get(), lp->ub.get(),
+                           lp->colscale.get(), lp->rowscale.get(), u);
+        if (nb > 0) hipLaunchKernelGGL(postsolve_basic_boxed_kernel, dim3(gridn(nb)), dim3(kBlock), 0, s, nc, nb, pt, lp->boxed.get(), lp->colscale.get(), u);
+        if (nf > 0) hipLaunchKernelGGL(postsolve_basic_flipped_kernel, dim3(gridn(nf)), dim3(kBlock), 0, s, nf, lp->flipped.get(), u);
+        hipLaunchKernelGGL(correct_basic_kernel, dim3(gridn(nv)), dim3(kBlock), 0, s, nv, lp->lbu.get(), lp->ubu.get(), u);
+    }
+    IPXK_HIP(hipGetLastError());
+}
+
+void ensure_status_buffers(Lp* lp) {
+    lp->st_solver.ensure((size_t)(lp->ctx->n + lp->ctx->m));
+    lp->st_cbasis.ensure(atleast1(lp->num_constr));
+    lp->st_vbasis.ensure((size_t)lp->num_var);
+}
+
+// EvaluateBasicPoint of a user-form point on the device
+void evaluate_basic_dev(Lp* lp, const BasicPoint& u, ipxk_lp_basic_eval* out) {
+    hipStream_t s = lp->ctx->stream;
+    const int64_t nc = lp->num_constr, nv = lp->num_var;
+    lp->part.ensure((size_t)kNumEvalSlots * kEvalGrid); lp->result.ensure(kNumEvalSlots);
+    const int grid = grid_for(std::max(nc, nv), kEvalGrid);
+    hipLaunchKernelGGL(evaluate_basic_kernel, dim3(grid), dim3(kBlock), 0, s, nc, nv, lp->lbu.get(), lp->ubu.get(), lp->obj.get(), lp->ctype.get(),
+                       u.x, u.slack, u.y, u.z, u.vbasis, lp->part.get());
+    hipLaunchKernelGGL(evaluate_basic_finish_kernel, dim3(1), dim3(kBlock), 0, s, grid, lp->part.get(), lp->result.get());
+    double r[kNumBasicSlots];
+    lp->result.download(r, kNumBasicSlots, s);
+    IPXK_HIP(hipGetLastError());
+    out->primal_infeas = r[kBasicPrimal];
+    out->dual_infeas = r[kBasicDual];
+    out->objval = r[kBasicObjX];
+}
+
+}  // namespace
+
+void lp_postsolve_basic(Lp* lp, const double* x_solver, const double* y_solver, const double* z_solver, const ipxint* statuses,
+                        const LpBasicPoint& out) {
+    hipStream_t s = lp->ctx->stream;
+    ensure_status_buffers(lp);
+    lp->st_solver.upload(statuses, (size_t)(lp->ctx->n + lp->ctx->m), s);
+    postsolve_basic_dev(lp, x_solver, y_solver, z_solver, BasicPoint{out.x, out.slack, out.y, out.z, lp->st_cbasis.get(), lp->st_vbasis.get()});
+    if (out.cbasis) lp->st_cbasis.download(out.cbasis, (size_t)lp->num_constr, s);
+    if (out.vbasis) lp->st_vbasis.download(out.vbasis, (size_t)lp->num_var, s);
+    IPXK_HIP(hipStreamSynchronize(s));
+    IPXK_HIP(hipGetLastError());
+}
+
+// LpSolver::RunCrossover (src/lp_solver.cc:464-537) behind the gate of LpSolver::Solve (:64-67)
+void lp_crossover(Lp* lp, const ipxk_crossover_params* prm, ipxk_crossover_info* info, ipxk_lp_basic_eval* eval, ipxk_interrupt_fn interrupt,
+                  void* user) {
+    Context* c = lp->ctx;
+    IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
+    IPXK_REQUIRE(lp->num_constr > 0, "ipxk_lp_crossover: the lp has no constraints, so there is no basis to push on");
+    IPXK_REQUIRE(lp->solved, "ipxk_lp_crossover: no solve on this lp yet (ipxk_lp_solve)");
+    hipStream_t s = c->stream;
+    *info = ipxk_crossover_info{};
+    ipxk_lp_basic_eval ev{};
+    if (eval) *eval = ev;
+    lp->has_vertex = false;
+    if (lp->status_ipm != 1 && lp->status_ipm != 2) return;             // (:64-66: optimal or imprecise)
+    IPXK_REQUIRE(!lp->basis.empty(), "ipxk_lp_crossover: the solve left no basis");
+    ipxk_crossover_params p = prm ? *prm : ipxk_crossover_params{1e-7, 1e-7, 100};
+    const double user_primal_tol = p.primal_feastol, user_dual_tol = p.dual_feastol;
+    if (lp->dualized) std::swap(p.primal_feastol, p.dual_feastol);      // src/crossover.cc:83-84, :237-238
+    const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+    DevBuf<double> sx(N), sy(m), sz(N);                                 // the solver-form vertex
+    std::vector<ipxint> statuses(N);
+    crossover_run_dev(c, lp->b.get(), lp->c.get(), lp->lb.get(), lp->ub.get(), nullptr, lp->basis.data(), &p, info, sx.get(), sy.get(), sz.get(),
+                      statuses.data(), nullptr, 0, interrupt, user);
+    // the run reports 2 when the SOLVER-form vertex misses the tolerances; the reference decides on the user-form one (:534-536)
+    if (info->status_crossover != 1 && info->status_crossover != 2) { IPXK_HIP(hipStreamSynchronize(s)); return; }
+    ensure_status_buffers(lp);
+    lp->st_solver.upload(statuses.data(), N, s);
+    lp->vx.ensure((size_t)lp->num_var); lp->vz.ensure((size_t)lp->num_var);
+    lp->vslack.ensure((size_t)lp->num_constr); lp->vy.ensure((size_t)lp->num_constr);
+    const BasicPoint u{lp->vx.get(), lp->vslack.get(), lp->vy.get(), lp->vz.get(), lp->st_cbasis.get(), lp->st_vbasis.get()};
+    postsolve_basic_dev(lp, sx.get(), sy.get(), sz.get(), u);
+    lp->cbasis.resize((size_t)lp->num_constr); lp->vbasis.resize((size_t)lp->num_var);
+    lp->st_cbasis.download(lp->cbasis.data(), lp->cbasis.size(), s);
+    lp->st_vbasis.download(lp->vbasis.data(), lp->vbasis.size(), s);
+    evaluate_basic_dev(lp, u, &ev);
+    IPXK_HIP(hipStreamSynchronize(s));               // (sx, sy, sz go out of scope)
+    lp->has_vertex = true;
+    info->status_crossover = ev.primal_infeas > user_primal_tol || ev.dual_infeas > user_dual_tol ? 2 : 1;
+    if (eval) *eval = ev;
+}
+
+void lp_evaluate_basic(Lp* lp, const double* x, const double* slack, const double* y, const double* z, const ipxint* vbasis,
+                       ipxk_lp_basic_eval* out) {
+    ensure_status_buffers(lp);
+    lp->st_vbasis.upload(vbasis, (size_t)lp->num_var, lp->ctx->stream);
+    // (the kernel only reads: the point is passed as the writable record the postsolve fills)
+    evaluate_basic_dev(lp, BasicPoint{const_cast<double*>(x), const_cast<double*>(slack), const_cast<double*>(y), const_cast<double*>(z), nullptr,
+                                      lp->st_vbasis.get()}, out);
+}
+
+void lp_basic_solution(Lp* lp, const double* out[4], const ipxint** cbasis, const ipxint** vbasis) {
+    IPXK_REQUIRE(lp->has_vertex, "no basic solution (ipxk_lp_crossover with status_crossover 1 or 2)");
+    out[0] = lp->vx.get(); out[1] = lp->vslack.get(); out[2] = lp->vy.get(); out[3] = lp->vz.get();
+    *cbasis = lp->cbasis.data();
+    *vbasis = lp->vbasis.data();
+}
+
+// LpSolver::GetBasis (src/lp_solver.cc:233-244)
+void lp_get_basis(Lp* lp, ipxint* cbasis, ipxint* vbasis) {
+    Context* c = lp->ctx;
+    IPXK_REQUIRE(!lp->basis.empty(), "no basis (ipxk_lp_solve has not built one)");
+    if (lp->has_vertex) {
+        if (cbasis) std::copy(lp->cbasis.begin(), lp->cbasis.end(), cbasis);
+        if (vbasis) std::copy(lp->vbasis.begin(), lp->vbasis.end(), vbasis);
+        return;
+    }
+    hipStream_t s = c->stream;
+    const int64_t m = c->m, N = c->n + c->m;
+    for (ipxint j : lp->basis) IPXK_REQUIRE(j >= 0 && j < N, "the stored basis holds an index out of range");
+    ensure_status_buffers(lp);
+    DevBuf<ipxint> basis_dev;
+    basis_dev.upload(lp->basis, s);
+    hipLaunchKernelGGL(nonbasic_statuses_kernel, dim3(gridn(N)), dim3(kBlock), 0, s, N, lp->lb.get(), lp->ub.get(), lp->st_solver.get());
+    hipLaunchKernelGGL(basic_statuses_kernel, dim3(gridn(m)), dim3(kBlock), 0, s, m, basis_dev.get(), lp->st_solver.get());
+    postsolve_basic_dev(lp, nullptr, nullptr, nullptr, BasicPoint{nullptr, nullptr, nullptr, nullptr, lp->st_cbasis.get(), lp->st_vbasis.get()});
+    if (cbasis) lp->st_cbasis.download(cbasis, (size_t)lp->num_constr, s);
+    if (vbasis) lp->st_vbasis.download(vbasis, (size_t)lp->num_var, s);
+    IPXK_HIP(hipStreamSynchronize(s));               // (basis_dev goes out of scope)
+    IPXK_HIP(hipGetLastError());
 }
 
 }  // namespace ipxk

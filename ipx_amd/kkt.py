@@ -42,7 +42,7 @@ EXPORTS = [
     "ipxk_normal_apply_bytes", "ipxk_spmv_layout", "ipxk_layout_info", "ipxk_layout_array", "ipxk_split_inverse_stats", "ipxk_split_inverse_refined", "ipxk_dev_alloc", "ipxk_dev_free", "ipxk_dev_upload",
     "ipxk_dev_download",
     "ipxk_lp_create", "ipxk_lp_destroy", "ipxk_lp_context", "ipxk_lp_get_model", "ipxk_lp_solve", "ipxk_lp_postsolve", "ipxk_lp_evaluate",
-    "ipxk_lp_get_residuals",
+    "ipxk_lp_get_residuals", "ipxk_lp_postsolve_basic", "ipxk_lp_crossover", "ipxk_lp_evaluate_basic", "ipxk_lp_get_basic_solution", "ipxk_lp_get_basis",
     "ipxk_ipm_set_drop_tolerances", "ipxk_ipm_drop_degenerate", "ipxk_ipm_drop_counts", "ipxk_iterate_get_state",
 ]
 
@@ -145,6 +145,10 @@ class LpEval(C.Structure):
     _fields_ = [("abs_presidual", c_f64), ("abs_dresidual", c_f64), ("rel_presidual", c_f64), ("rel_dresidual", c_f64),
                 ("pobjval", c_f64), ("dobjval", c_f64), ("rel_objgap", c_f64), ("complementarity", c_f64), ("normx", c_f64),
                 ("normy", c_f64), ("normz", c_f64), ("norm_obj", c_f64), ("norm_rhs", c_f64), ("norm_bounds", c_f64)]
+
+
+class LpBasicEval(C.Structure):
+    _fields_ = [("primal_infeas", c_f64), ("dual_infeas", c_f64), ("objval", c_f64)]
 
 
 class Times(C.Structure):
@@ -956,6 +960,7 @@ class Lp:
     dualize: -1 (when num_constr > 2 * num_var), 0 or 1; scale: 0 or 1.  info: the fields of ipxk_lp_info."""
 
     PT_KEYS = ("x", "xl", "xu", "slack", "y", "zl", "zu")
+    BASIC_KEYS = ("x", "slack", "y", "z", "cbasis", "vbasis")
 
     def __init__(self, A, rhs, constr_type, obj, lb, ub, dualize=-1, scale=1, device=0):
         self.lib = load_library()
@@ -1002,14 +1007,76 @@ class Lp:
 
     def solve(self, kkt_tol=0.3, feasibility_tol=1e-6, optimality_tol=1e-8, ipm_maxiter=300, switchiter=-1,
               precond_dense_cols=True, crossover_start=0.0, dependency_tol=1e-6, max_etas=100, use_resident_point=False,
-              interrupt=None):
-        """ipxk_ipm_solve on the presolved model; returns the fields of ipxk_solve_info."""
+              interrupt=None, crossover=False):
+        """ipxk_ipm_solve on the presolved model; returns the fields of ipxk_solve_info.  crossover: crossover_start becomes
+        1e-8 (the reference's default with crossover on) when it is 0, crossover() runs after the solve with its defaults,
+        and the result also holds its two records under "crossover" and "basic_eval"."""
+        if crossover and crossover_start == 0.0:
+            crossover_start = 1e-8
         prm = SolveParams(kkt_tol, feasibility_tol, optimality_tol, crossover_start, dependency_tol, ipm_maxiter, switchiter,
                           max_etas, 1 if precond_dense_cols else 0, 1 if use_resident_point else 0)
         info = SolveInfo()
         cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
         self._check(self.lib.ipxk_lp_solve(self.h, C.byref(prm), C.byref(info), cb, None))
-        return {name: getattr(info, name) for name, _ in SolveInfo._fields_}
+        out = {name: getattr(info, name) for name, _ in SolveInfo._fields_}
+        if crossover:
+            out["crossover"], out["basic_eval"] = self.crossover(interrupt=interrupt)
+        return out
+
+    def crossover(self, feastol=(1e-7, 1e-7), max_etas=100, interrupt=None):
+        """LpSolver::RunCrossover after solve(): (the fields of ipxk_crossover_info, the fields of ipxk_lp_basic_eval).
+        feastol = (primal, dual) in the user's terms."""
+        prm, info, ev = CrossoverParams(feastol[0], feastol[1], max_etas), CrossoverInfo(), LpBasicEval()
+        cb = INTERRUPT_FN(lambda _u: int(interrupt())) if interrupt else C.cast(None, INTERRUPT_FN)
+        self._check(self.lib.ipxk_lp_crossover(self.h, C.byref(prm), C.byref(info), C.byref(ev), cb, None))
+        return ({name: getattr(info, name) for name, _ in CrossoverInfo._fields_},
+                {name: getattr(ev, name) for name, _ in LpBasicEval._fields_})
+
+    def evaluate_basic(self, u):
+        """UserModel::EvaluateBasicPoint of a user-form point u = dict(x, slack, y, z, vbasis), host vectors: the fields of
+        ipxk_lp_basic_eval."""
+        ev = LpBasicEval()
+        self._check(self.lib.ipxk_lp_evaluate_basic(self.h, _fp(_F(u["x"])), _fp(_F(u["slack"])), _fp(_F(u["y"])), _fp(_F(u["z"])),
+                                                    _ip(_I(u["vbasis"])), C.byref(ev)))
+        return {name: getattr(ev, name) for name, _ in LpBasicEval._fields_}
+
+    def _basic_arrays(self, want):
+        out = {k: np.zeros(self.num_constr if k in ("slack", "y", "cbasis") else self.num_var, i64 if k.endswith("basis") else f64)
+               for k in self.BASIC_KEYS if k in want}
+        return out, [(_ip if k.endswith("basis") else _fp)(out.get(k)) for k in self.BASIC_KEYS]
+
+    def basic_solution(self):
+        """LpSolver::GetBasicSolution: dict(x, slack, y, z, cbasis, vbasis) of the vertex crossover() stored."""
+        out, args = self._basic_arrays(self.BASIC_KEYS)
+        self._check(self.lib.ipxk_lp_get_basic_solution(self.h, *args))
+        return out
+
+    def basis(self):
+        """LpSolver::GetBasis: (cbasis, vbasis) of the stored vertex, else of the basis the last solve() left."""
+        cbasis, vbasis = np.zeros(self.num_constr, i64), np.zeros(self.num_var, i64)
+        self._check(self.lib.ipxk_lp_get_basis(self.h, _ip(cbasis), _ip(vbasis)))
+        return cbasis, vbasis
+
+    def postsolve_basic(self, x, y, z, basic_statuses, want=BASIC_KEYS):
+        """Presolver::PostsolveBasicSolution of a solver-form point (host vectors x, z [n+m], y [m], basic_statuses [n+m]):
+        dict of the outputs named in `want` (the others are passed as NULL)."""
+        out, args = self._basic_arrays(want)
+        if not self.context.device_mode:
+            self._check(self.lib.ipxk_lp_postsolve_basic(self.h, _fp(_F(x)), _fp(_F(y)), _fp(_F(z)), _ip(_I(basic_statuses)), *args))
+            return out
+        # device-pointer mode: the doubles through resident vectors (a vector of at least one entry, so that none is NULL)
+        vin = [self.context.vector(max(len(v), 1), np.resize(_F(v), max(len(v), 1)) if len(v) else np.zeros(1)) for v in (x, y, z)]
+        vout = {k: self.context.vector(max(out[k].size, 1)) for k in out if not k.endswith("basis")}
+        for j, k in enumerate(self.BASIC_KEYS[:4]):
+            args[j] = vout[k].as_arg() if k in vout else None
+        try:
+            self._check(self.lib.ipxk_lp_postsolve_basic(self.h, *[v.as_arg() for v in vin], _ip(_I(basic_statuses)), *args))
+            for k, v in vout.items():
+                out[k] = v.download()[: out[k].size]
+        finally:
+            for v in vin + list(vout.values()):
+                v.free()
+        return out
 
     def interior_solution(self):
         """Presolver::PostsolveInteriorPoint of the resident iterate: dict(x, xl, xu, slack, y, zl, zu)."""
