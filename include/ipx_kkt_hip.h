@@ -1183,7 +1183,8 @@ ipxint ipxk_split_inverse_refined(const ipxk_context* ctx);
  * slice_elems, # batches, # entries that waited for a later batch, use_acc_fused,
  * accf.built, nrb, RB, # batches, use_plain, # steps of the accumulated tiles (runs
  * of batches the persistent kernel takes as one pipeline step), # 16-byte units of
- * their wide stream (0: not built, IPXK_ACC_WIDE=0); the rest of the 48 is 0}.
+ * their wide stream (0: not built, IPXK_ACC_WIDE=0), the launch grid their head
+ * tables are built for (0: not built, the default; IPXK_ACC_HEAD=1 builds them); the rest of the 48 is 0}.
  * `sorted`: the sorted fused tiles.  The retired slots [1], [12], [13], [18], [19]
  * described the sorted sub-tiles (use_sorted, their slice and sub-slice counts, their
  * slice width, the fused flag) and are always 0.  use_sorted_fused, use_acc,
@@ -1207,7 +1208,14 @@ int ipxk_layout_info(const ipxk_context* ctx, int which, ipxint info[48],
  * last two}, as bit patterns; positions >= ne are zero), 24 the first unit of each
  * step in it (u32, one per step record; the last is the total).  23 and 24 are empty
  * with IPXK_ACC_WIDE=0, which makes the persistent tile kernel read arrays 13 and 14
- * as it did before there was a wide stream.  Copies min(cap, size) bytes into out;
+ * as it did before there was a wide stream.  25 the head of the accumulated tiles
+ * (u32, 64 words per workgroup of the launch grid: the records {first entry, end,
+ * three cuts, first unit of the wide stream, tile, 0} of the first six steps of the
+ * workgroup's walk, tile = -1 past its last tile, then the walker's state {tile,
+ * step in it, first step record of the tile, its steps}, then zeros), 26 the head of
+ * the wide stream (u32; per workgroup, step 0-2 and plane 0-2 the 512 units of 16
+ * bytes that threads 0-511 load for it); both empty unless IPXK_ACC_HEAD=1, 26 also
+ * with IPXK_ACC_WIDE=0.  Copies min(cap, size) bytes into out;
  * *nbytes = the array's size. */
 int ipxk_layout_array(ipxk_context* ctx, int which, int array, void* out,
                       ipxint cap, ipxint* nbytes);

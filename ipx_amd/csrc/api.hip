@@ -1511,7 +1511,7 @@ int ipxk_layout_info(const ipxk_context* c, int which, ipxint info[48], double c
         info[29] = M.acc.nrows_pad; info[30] = M.acc.slice_elems; info[31] = M.acc.nbatches; info[32] = M.acc.deferred;
         info[33] = L == SpmvLayout::accfused; info[34] = M.accf.built; info[35] = M.accf.nrb; info[36] = M.accf.RB; info[37] = M.accf.nbatches;
         info[38] = L == SpmvLayout::plain; info[39] = M.acc.nsteps;
-        info[40] = M.acc.wide_units;
+        info[40] = M.acc.wide_units; info[41] = M.acc.head_grid;
         if (create_ms) for (int i = 0; i < 4; i++) create_ms[i] = c->create_ms[i];
     });
 }
@@ -1554,6 +1554,8 @@ int ipxk_layout_array(ipxk_context* c, int which, int array, void* out, ipxint c
             case 22: src = M.acc.steps.get(); bytes = M.acc.built ? ((size_t)M.acc.nsteps + 1) * 16 : 0; break;
             case 23: src = M.acc.wide.get(); bytes = M.acc.built ? (size_t)M.acc.wide_units * 16 : 0; break;
             case 24: src = M.acc.wide_start.get(); bytes = M.acc.built && M.acc.wide_units > 0 ? ((size_t)M.acc.nsteps + 1) * 4 : 0; break;
+            case 25: src = M.acc.head.get(); bytes = M.acc.built ? (size_t)M.acc.head_grid * kAccHeadWords * 4 : 0; break;
+            case 26: src = M.acc.head_wide.get(); bytes = M.acc.built && M.acc.wide_units > 0 ? (size_t)M.acc.head_grid * kAccHeadStreams * 3 * kAccThreads * 16 : 0; break;
             default: IPXK_REQUIRE(false, "unknown array");
         }
         if (M.nlong > 0 && (array < 8 || array > 10)) bytes = 0;       // long rows: the tiles hold fewer entries than nnz; not inspected

@@ -295,6 +295,22 @@ constexpr int kAccStepBatches = 4;                         // batches a step of 
 //     wide_start has one entry per step record (the sentinel's: the total).  Only a tile's last step is short: at C3
 //     0.4 % more bytes than pack + val, and as much device memory again as those two (C3: 193 MB per gather matrix).
 __host__ __device__ inline int acc_wide_threads(int ne) { return ne >= kAccBatch ? kAccThreads : ((ne + 3) / 4 + 63) & ~63; }
+//   * the HEAD tables (built only with IPXK_ACC_HEAD=1 -- they gain nothing measurable, profiles/acc_cold_start.txt; the sliced form only): what a workgroup of the persistent kernel needs before
+//     its first add, at addresses it can form from its arguments, blockIdx.x and threadIdx.x alone -- one round trip through the
+//     caches that the kernel boundary has emptied instead of three dependent ones (tile_step -> steps / wide_start -> wide).
+//     Derived by acc_build_steps for the launch grid head_grid = min(acc_persist_grid(nslices), # tiles); a launch on any other
+//     grid does not use them.
+//     head: kAccHeadWords (64) words per workgroup w < head_grid.  Words 0-47: the records of the first kAccHeadSteps (6) steps of
+//     the workgroup's walk over tiles w, w + head_grid, ..., 8 words each: {e0, e1, c1, c2, c3, w0, tile, 0}; tile = -1 past
+//     the workgroup's last tile, an empty tile gives its one empty step (all zeros but the tile).  Words 48-51: the walker's
+//     state after those steps {tile, step in the tile, first step record of the tile, its steps}.  The rest is zero.
+//     head_wide (only with the wide stream): for workgroup w, step d = 0, 1, 2 of its walk, plane p = 0, 1, 2 and thread
+//     t < 512 the 16-byte unit ((w 3 + d) 3 + p) 512 + t is the unit thread t loads for that step and plane from the wide
+//     stream, wide[w0 + p Tp + min(t, Tp - 1)] (an empty step: unit 0 in every plane); zeros where the workgroup has no
+//     step d.  72 KB per workgroup (C3: 19 MB per gather matrix).
+constexpr int kAccHeadWords = 64;
+constexpr int kAccHeadSteps = 6;                           // the step records a workgroup holds ahead (the kernel's NE)
+constexpr int kAccHeadStreams = 3;                         // the steps whose stream loads the kernel's prologue issues
 //   * FUSED form (one slice = all of x, for matrices whose gathers have locality; round 4): a tile is a row block of RB rows
 //     (as many as give every CU two tiles), the gathered index is stored relative to the tile's smallest one (`xmin`; the
 //     tile's window of x must span less than 2^18 entries), the row sums start from the epilogue's initial value and the
@@ -303,6 +319,10 @@ __host__ __device__ inline int acc_wide_threads(int ne) { return ne >= kAccBatch
 //     timing at ipxk_create may choose among them).
 struct AccView {
     int nrows, nrows_pad, nslices, nrb, RB, slice_elems;
+    int xlen;                          // elements of the gathered vector (the last slice may be short); 0: not known
+    int head_grid;                     // the launch grid the head tables are for
+    const unsigned* head;              // [head_grid][kAccHeadWords]; nullptr: no head tables
+    const uint4* head_wide;            // [head_grid][3][3][kAccThreads]; nullptr: no wide stream
     const int* xmin;                   // FUSED: [nrb] smallest gathered index of the tile; else nullptr
     const unsigned* tile_batch;        // [nrb*nslices + 1] first batch of each tile
     const unsigned* bptr;              // [# batches + 1] first entry of each batch
@@ -318,12 +338,25 @@ struct AccMatrix {
     bool built = false;
     int nslices = 0, nrb = 0, RB = 0, nrows_pad = 0, slice_elems = 0;
     int64_t nbatches = 0, deferred = 0, nsteps = 0, wide_units = 0;
-    DevBuf<unsigned> tile_batch, bptr, pack, tile_step, wide_start;
-    DevBuf<uint4> steps, wide;
+    int xlen = 0;                      // elements of the gathered vector
+    int head_grid = 0;                 // the grid the head tables are built for; 0: none
+    DevBuf<unsigned> tile_batch, bptr, pack, tile_step, wide_start, head;
+    DevBuf<uint4> steps, wide, head_wide;
+    // the view's fields every accumulated form shares (spmv.hip, nmatrix.hip)
+    void fill_view(AccView& V, int nrows) const;
     DevBuf<double> val, partial;
     bool fused = false;                // the FUSED form
     DevBuf<int> xmin;
 };
+// (the fused form has no partial vectors, step tables' head or wide stream, the sliced one no xmin: their buffers are empty, the pointers null)
+inline void AccMatrix::fill_view(AccView& V, int nrows) const {
+    V.nrows = nrows; V.nrows_pad = nrows_pad; V.nslices = nslices; V.nrb = nrb; V.RB = RB; V.slice_elems = slice_elems;
+    V.xlen = xlen; V.head_grid = head_grid; V.head = head.get(); V.head_wide = head_wide.get();
+    V.xmin = xmin.get();
+    V.tile_batch = tile_batch.get(); V.bptr = bptr.get(); V.pack = pack.get(); V.val = val.get(); V.partial = partial.get();
+    V.tile_step = tile_step.get(); V.steps = steps.get();
+    V.wide_start = wide_start.get(); V.wide = wide.get();
+}
 
 struct LayoutScratch;                 // layout_scratch.hpp
 

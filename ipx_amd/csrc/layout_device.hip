@@ -256,6 +256,49 @@ __global__ __launch_bounds__(kAccThreads) void acc_wide_fill_kernel(int nsteps, 
     }
 }
 
+// The head tables (internal.hpp) of the launch grid P: one thread per workgroup walks its first kAccHeadSteps steps exactly as the
+// persistent kernel's walker does (spmv_kernels.hpp: next()), then one workgroup per (workgroup, step) copies the units its
+// threads load for that step.
+__global__ void acc_head_fill_kernel(int P, int ntiles, const unsigned* __restrict__ tile_step, const uint4* __restrict__ steps,
+                                     const unsigned* __restrict__ wide_start, unsigned* __restrict__ head) {
+    IPXK_GRID_STRIDE(w, P) {
+        unsigned* h = head + (size_t)w * kAccHeadWords;
+        int wt = (int)w, wq = 0, wnb = 0;
+        unsigned wb0 = 0;
+        if (wt < ntiles) { wb0 = tile_step[wt]; wnb = (int)(tile_step[wt + 1] - wb0); }
+        for (int i = 0; i < kAccHeadSteps; i++) {
+            unsigned r[8] = {0u, 0u, 0u, 0u, 0u, 0u, ~0u, 0u};
+            if (wt < ntiles) {
+                r[6] = (unsigned)wt;
+                if (wnb > 0) {
+                    const uint4 a = steps[wb0 + wq];
+                    r[0] = a.x; r[2] = a.y; r[3] = a.z; r[4] = a.w; r[1] = steps[wb0 + wq + 1].x;
+                    if (wide_start) r[5] = wide_start[wb0 + wq];
+                }
+                if (++wq >= max(wnb, 1)) {
+                    wt += P; wq = 0;
+                    if (wt < ntiles) { wb0 = tile_step[wt]; wnb = (int)(tile_step[wt + 1] - wb0); }
+                }
+            }
+            for (int j = 0; j < 8; j++) h[8 * i + j] = r[j];
+        }
+        h[8 * kAccHeadSteps] = (unsigned)wt; h[8 * kAccHeadSteps + 1] = (unsigned)wq; h[8 * kAccHeadSteps + 2] = wb0; h[8 * kAccHeadSteps + 3] = (unsigned)wnb;
+        for (int j = 8 * kAccHeadSteps + 4; j < kAccHeadWords; j++) h[j] = 0u;
+    }
+}
+__global__ __launch_bounds__(kAccThreads) void acc_head_wide_fill_kernel(int P, const unsigned* __restrict__ head, const uint4* __restrict__ wide,
+                                                                         uint4* __restrict__ head_wide) {
+    const int t = threadIdx.x;
+    for (int k = blockIdx.x; k < P * kAccHeadStreams; k += gridDim.x) {
+        const unsigned* r = head + (size_t)(k / kAccHeadStreams) * kAccHeadWords + 8 * (k % kAccHeadStreams);
+        uint4* dst = head_wide + (size_t)k * 3 * kAccThreads;
+        const bool live = (int)r[6] >= 0;
+        const int tp = acc_wide_threads((int)(r[1] - r[0]));
+        const uint4* src = wide + r[5] + min(t, max(tp - 1, 0));
+        for (int p = 0; p < 3; p++) dst[p * kAccThreads + t] = live ? src[p * tp] : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
 // ---- one-slice (FUSED) forms: a tile is a row block, offsets are relative to the tile's smallest gathered index ----
 // smallest / largest gathered index per tile, the rows' count bytes (optional), a flag for rows with descending / repeated indices
 __global__ void tile_window_kernel(int nrows, const int* __restrict__ ptr, const int* __restrict__ idx, int RB, int* __restrict__ lo,
@@ -513,6 +556,24 @@ int acc_rows_per_block(int nrows, int ns) {
 // wide (the sliced form, whose persistent kernel reads it): then the wide stream of those steps from A.pack / A.val, unless
 // IPXK_ACC_WIDE=0 (the kernel then streams pack / val as before; A/B runs and the tests' reference) -- A.wide_start / wide /
 // wide_units.  Not built either when the units could overflow 32 bits (more than 2^21 steps).
+// The sliced form (A.nslices is set) with the persistent kernel also gets the head tables of its launch grid (internal.hpp) --
+// A.head / head_wide / head_grid -- only with IPXK_ACC_HEAD=1 (measured: no gain, profiles/acc_cold_start.txt; A/B runs and the tests): head from the step table, head_wide
+// from the wide stream when that was built.
+static void acc_build_head(AccMatrix& A, int64_t ntiles, hipStream_t s) {
+    static const bool head_on = [] { const char* e = getenv("IPXK_ACC_HEAD"); return e && atoi(e) != 0; }();
+    A.head.release(); A.head_wide.release(); A.head_grid = 0;
+    const int P = (int)std::min<int64_t>(acc_persist_grid(A.nslices), ntiles);
+    if (!head_on || A.fused || P < 1 || A.nsteps == 0) return;
+    A.head.ensure((size_t)P * kAccHeadWords);
+    hipLaunchKernelGGL(acc_head_fill_kernel, dim3(gridn(P)), dim3(kBlock), 0, s, P, (int)ntiles, A.tile_step.get(), A.steps.get(),
+                       A.wide_units > 0 ? A.wide_start.get() : nullptr, A.head.get());
+    if (A.wide_units > 0) {
+        A.head_wide.ensure((size_t)P * kAccHeadStreams * 3 * kAccThreads);
+        hipLaunchKernelGGL(acc_head_wide_fill_kernel, dim3(P * kAccHeadStreams), dim3(kAccThreads), 0, s, P, A.head.get(), A.wide.get(), A.head_wide.get());
+    }
+    IPXK_HIP(hipStreamSynchronize(s));
+    A.head_grid = P;
+}
 void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, bool wide, hipStream_t s) {
     static const bool merge = !(getenv("IPXK_ACC_STEPS") && getenv("IPXK_ACC_STEPS")[0] == '0');
     static const bool wide_on = !(getenv("IPXK_ACC_WIDE") && getenv("IPXK_ACC_WIDE")[0] == '0');
@@ -531,7 +592,9 @@ void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, bool wide, hipSt
     IPXK_HIP(hipStreamSynchronize(s));          // nstep goes out of scope
     A.nsteps = total;
     A.wide_start.release(); A.wide.release(); A.wide_units = 0;
-    if (!wide || !wide_on || total == 0 || total > (1u << 21)) return;
+    A.head.release(); A.head_wide.release(); A.head_grid = 0;
+    if (!wide) return;
+    if (!wide_on || total == 0 || total > (1u << 21)) { acc_build_head(A, ntiles, s); return; }
     DevBuf<unsigned> units((size_t)total + 1);
     hipLaunchKernelGGL(acc_wide_count_kernel, dim3(gridn(total)), dim3(kBlock), 0, s, (int)total, A.steps.get(), units.get());
     A.wide_start.ensure((size_t)total + 1);
@@ -544,6 +607,7 @@ void acc_build_steps(AccMatrix& A, int64_t ntiles, int64_t nnz, bool wide, hipSt
                        A.wide_start.get(), A.pack.get(), A.val.get(), A.wide.get());
     IPXK_HIP(hipStreamSynchronize(s));          // units goes out of scope
     A.wide_units = nunits;
+    acc_build_head(A, ntiles, s);
 }
 
 // The tail both accumulated forms share.  On entry S.q2 / S.v2 hold the entries' keys (tile << 18 | offset) and storage positions
@@ -616,10 +680,11 @@ bool device_build_acc(LayoutScratch& S, AccMatrix& out, const SlicedMatrix& slic
     sort_pairs<u64>(S.T, S.q1.get(), S.q2.get(), S.v1.get(), S.v2.get(), nz, kSortedOffBits + bits_for((u64)std::max<int64_t>(ntiles, 2) - 1), s);
     hipLaunchKernelGGL(lower_bounds_kernel<u64>, dim3(gridn(ntiles + 1)), dim3(kBlock), 0, s, ntiles + 1, nnz, S.q2.get(), (u64)1, kSortedOffBits,
                        T.tile_ptr.get());
+    // (the geometry first: acc_build_steps sizes the head tables by the slice count)
+    out.nslices = ns; out.nrb = nrb; out.RB = RB; out.nrows_pad = nrb * RB; out.slice_elems = (int)slice; out.xlen = ncols;
     acc_batches(S, out, T, ntiles, RB, nnz, dval, true, s);
     IPXK_HIP(hipStreamSynchronize(s));       // the temporaries go out of scope
     IPXK_HIP(hipGetLastError());
-    out.nslices = ns; out.nrb = nrb; out.RB = RB; out.nrows_pad = nrb * RB; out.slice_elems = (int)slice;
     out.partial.resize((size_t)ns * out.nrows_pad);
     out.built = true;
     return true;

@@ -316,7 +316,7 @@ void GatherMatrix::build_acc(const ipxint* hptr, const ipxint* hidx, const doubl
         tb[t] = (unsigned)B.bp.size();
         B.tile(all.data() + tptr[t], (int)(tptr[t + 1] - tptr[t]), tptr[t]);
     }
-    acc.nslices = ns; acc.nrb = nrb; acc.RB = RB; acc.nrows_pad = nrb * RB; acc.slice_elems = (int)slice;
+    acc.nslices = ns; acc.nrb = nrb; acc.RB = RB; acc.nrows_pad = nrb * RB; acc.slice_elems = (int)slice; acc.xlen = ncols;
     B.finish(acc, tb, nnz, s);
     acc.partial.resize((size_t)ns * acc.nrows_pad);
     IPXK_HIP(hipStreamSynchronize(s));

@@ -330,10 +330,7 @@ static void launch_tiles(const SlicedMatrix& P, int nrows, const double* x, cons
 template <class Epi>
 static void launch_acc(const AccMatrix& A, const SlicedMatrix& P, int nrows, const double* x, const Epi& epi, const int* done, hipStream_t s) {
     AccView W;
-    W.nrows = nrows; W.nrows_pad = A.nrows_pad; W.nslices = A.nslices; W.nrb = A.nrb; W.RB = A.RB; W.slice_elems = A.slice_elems;
-    W.tile_batch = A.tile_batch.get(); W.bptr = A.bptr.get(); W.pack = A.pack.get(); W.val = A.val.get(); W.partial = A.partial.get();
-    W.tile_step = A.tile_step.get(); W.steps = A.steps.get();
-    W.wide_start = A.wide_start.get(); W.wide = A.wide.get();
+    A.fill_view(W, nrows);
     launch_acc_tiles<Epi>(W, x, done, s);
     SlicedView V = view_of(P, nrows);
     V.nrows_pad = A.nrows_pad; V.partial = A.partial.get();

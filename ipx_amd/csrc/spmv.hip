@@ -256,14 +256,9 @@ bool GatherMatrix::build_device(LayoutScratch& S, int64_t nrows_, int64_t ncols_
     return true;
 }
 
-// (the fused form has no partial vectors, the sliced one no xmin: their buffers are empty, the pointers null)
 static AccView view_of(const AccMatrix& A, int nrows) {
     AccView V;
-    V.nrows = nrows; V.nrows_pad = A.nrows_pad; V.nslices = A.nslices; V.nrb = A.nrb; V.RB = A.RB; V.slice_elems = A.slice_elems;
-    V.xmin = A.xmin.get();
-    V.tile_batch = A.tile_batch.get(); V.bptr = A.bptr.get(); V.pack = A.pack.get(); V.val = A.val.get(); V.partial = A.partial.get();
-    V.tile_step = A.tile_step.get(); V.steps = A.steps.get();
-    V.wide_start = A.wide_start.get(); V.wide = A.wide.get();
+    A.fill_view(V, nrows);
     return V;
 }
 AccView GatherMatrix::acc_view() const { return view_of(acc, nrows); }

@@ -713,18 +713,31 @@ constexpr int kAccParkPerBatch = 2;
 // the padding positions >= ne are gathered (word 0: the slice's first element) and never added.  Which thread adds an entry
 // cannot change a sum (the rows of a batch are distinct), so every row sum is the same sequence of ds_add_f64 between the same
 // barriers as without.
+// HEAD (only with IPXK_ACC_HEAD=1: measured, it takes 0.4 us off the start of a launch and shows in no trace, profiles/
+// acc_cold_start.txt): the launch starts from the head tables (internal.hpp).  A workgroup's first six step records, the walker's state behind
+// them, *done and (WIDE) the nine stream loads of its first three steps are all issued before anything waits, from addresses
+// formed of the kernel's arguments, blockIdx.x and threadIdx.x alone: one trip through the caches that the kernel boundary has
+// emptied where the form without takes three dependent ones (tile_step -> steps / wide_start -> the wide stream).  Behind the
+// prologue pk, v, q and the walker hold what they hold without HEAD and the loop is the same; `done` is looked at where the
+// records arrive, so a spare launch has loaded what it does not use (from tables that stay valid).  Without the wide stream
+// only the records come from the head; the stream loads of pack / val need them and keep a level of their own.
+// WARM (the default, with or without HEAD; IPXK_ACC_WARM=0: off): as its first load each thread loads one 128-byte line of its workgroup's slice of x, line (blockIdx.x / 8) 512 + tid --
+// where workgroups are placed on the XCDs in turn, the 32 workgroups of an XCD cover a slice of 2 MiB once, so that the first
+// gathers do not find the XCD's L2 empty.  No result reads the value: placement only decides what the loads are worth.
 typedef unsigned acc_u32x4 __attribute__((ext_vector_type(4)));
 typedef double acc_f64x2 __attribute__((ext_vector_type(2)));
-template <class Prod, bool WIDE>
+template <class Prod, bool WIDE, bool HEAD = false, bool WARM = false>
 // (the step tables come as __restrict__ arguments: the partial stores of the loop would otherwise keep the compiler from
 // reading them with scalar loads, and a vector load of a step record waits vmcnt(0) -- for the whole pipeline)
 __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M, const unsigned* __restrict__ tile_step,
                                                                        const uint4* __restrict__ steps, const unsigned* __restrict__ wide_start,
                                                                        const acc_u32x4* __restrict__ wide, const double* __restrict__ x,
-                                                                       const int* done) {
+                                                                       const int* done, const unsigned* __restrict__ head,
+                                                                       const acc_u32x4* __restrict__ head_wide) {
     // *done is fetched together with the first step-table loads and tested when they are there, not in a round trip of its
     // own in front of them (no `done`: a word of the table, which counts for nothing)
-    const int dn = *(done ? done : reinterpret_cast<const int*>(tile_step));
+    int dn = 0;
+    if constexpr (!HEAD) dn = *(done ? done : reinterpret_cast<const int*>(tile_step));
     extern __shared__ double ac_sum[];
     constexpr int U = kAccPerThread, T = kAccThreads, NP = kAccParkPairs, PB = kAccParkPerBatch;
     static_assert(NP % PB == 0, "parked pairs per batch");
@@ -733,6 +746,15 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
     const int s = blockIdx.x % M.nslices;                       // the same for every tile of the workgroup (G % nslices == 0)
     const double* __restrict__ xs = x + (size_t)s * M.slice_elems;
     double* const part = M.partial + (size_t)s * M.nrows_pad;
+    [[maybe_unused]] double warm = 0.0;
+    if constexpr (WARM) {
+        // (clamped to the slice's last element that x has: no predicate; every slice starts inside x, launch_acc_tiles.  The
+        // first vector load of the kernel: loads return in order, so whoever waits for a stream load has this one too)
+        const long long left = (long long)M.xlen - (long long)s * M.slice_elems;
+        const long long e = min((long long)((blockIdx.x >> 3) * T + tid) * 16, min((long long)M.slice_elems, left) - 1);
+        warm = xs[e];
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // walker over the workgroup's steps (wave-uniform: scalar loads; a record and the first word of the next one, the step's
     // end); an empty tile has no record and yields one empty step, so that its partial is written (zeros) like any other.
     // A step (internal.hpp) is entries [e0, e1) of one tile: streamed and gathered as one batch, added as the batches
@@ -741,8 +763,10 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
     struct Step { unsigned e0, e1, c1, c2, c3, w0; int tile; };    // tile -1: past the workgroup's last tile
     int wt = blockIdx.x, wq = 0, wnb = 0;
     unsigned wb0 = 0;
-    if (wt < ntiles) { wb0 = tile_step[wt]; wnb = (int)(tile_step[wt + 1] - wb0); }
-    if (done && dn) return;
+    if constexpr (!HEAD) {
+        if (wt < ntiles) { wb0 = tile_step[wt]; wnb = (int)(tile_step[wt + 1] - wb0); }
+        if (done && dn) return;
+    }
     auto next = [&]() -> Step {
         Step b{0u, 0u, 0u, 0u, 0u, 0u, -1};
         if (wt >= ntiles) return b;
@@ -759,9 +783,19 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
         return b;
     };
     constexpr int NE = 6;
+    static_assert(NE == kAccHeadSteps, "the head holds the records the kernel keeps ahead");
     Step q[NE];                           // q[i] = step k + i for the current step k
+    if constexpr (HEAD) {
+        const unsigned* __restrict__ h = head + (size_t)blockIdx.x * kAccHeadWords;
 #pragma unroll
-    for (int i = 0; i < NE; i++) q[i] = next();
+        for (int i = 0; i < NE; i++) q[i] = Step{h[8 * i], h[8 * i + 1], h[8 * i + 2], h[8 * i + 3], h[8 * i + 4], h[8 * i + 5], (int)h[8 * i + 6]};
+        wt = (int)h[8 * NE]; wq = (int)h[8 * NE + 1]; wb0 = h[8 * NE + 2]; wnb = (int)h[8 * NE + 3];
+        dn = *(done ? done : reinterpret_cast<const int*>(head));
+        __builtin_amdgcn_sched_barrier(0);          // (the scalar loads first, and nothing that waits for one in between)
+    } else {
+#pragma unroll
+        for (int i = 0; i < NE; i++) q[i] = next();
+    }
     unsigned pk[3][U];
     double v[3][U], xg[2][U];
     // The loads of an empty batch are issued too, from entry 0 and x[0] (the product has at least one entry and one column):
@@ -797,14 +831,41 @@ __global__ __launch_bounds__(kAccThreads) void spmv_acc_persist_kernel(AccView M
 #pragma unroll
         for (int u = 0; u < U; u++) xgb[u] = xb[pkb[u] & mask];
     };
+    if constexpr (HEAD && WIDE) {
+        static_assert(kAccHeadStreams == 3, "the prologue streams three steps");
+        const acc_u32x4* hw = head_wide + (size_t)blockIdx.x * (kAccHeadStreams * 3 * T) + tid;
 #pragma unroll
-    for (int d = 0; d < 3; d++) {
-#pragma unroll
-        for (int u = 0; u < U; u++) { pk[d][u] = 0u; v[d][u] = 0.0; }
-        stream(pk[d], v[d], q[d]);
+        for (int d = 0; d < 3; d++) {
+            const acc_u32x4 w = __builtin_nontemporal_load(hw + (3 * d) * T);
+            const acc_f64x2 v01 = __builtin_nontemporal_load(reinterpret_cast<const acc_f64x2*>(hw + (3 * d + 1) * T));
+            const acc_f64x2 v23 = __builtin_nontemporal_load(reinterpret_cast<const acc_f64x2*>(hw + (3 * d + 2) * T));
+            pk[d][0] = w.x; pk[d][1] = w.y; pk[d][2] = w.z; pk[d][3] = w.w;
+            v[d][0] = v01.x; v[d][1] = v01.y; v[d][2] = v23.x; v[d][3] = v23.y;
+        }
     }
-    for (int r = tid; r < M.RB; r += T) ac_sum[r] = 0.0;
+    // `done` set: the workgroup has no steps.  Not a return, and plain arithmetic on the records once they are there: a branch
+    // on *done (a select becomes one) is moved up in front of the prologue's loads, whatever fence stands between -- the
+    // compiler knows that nothing writes a __restrict__ table -- and is a round trip of its own again.  A spare launch has
+    // loaded what it does not use, from tables that stay valid.
+    [[maybe_unused]] int stopmask = 0;
+    if constexpr (HEAD) {
+        __builtin_amdgcn_sched_barrier(0);
+        stopmask = -(int)(done != nullptr && dn != 0);
+#pragma unroll
+        for (int i = 0; i < NE; i++) q[i].tile |= stopmask;
+    }
+    if constexpr (!(HEAD && WIDE)) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+#pragma unroll
+            for (int u = 0; u < U; u++) { pk[d][u] = 0u; v[d][u] = 0.0; }
+            stream(pk[d], v[d], q[d]);
+        }
+    }
+    for (int r = tid; r < (M.RB & ~stopmask); r += T) ac_sum[r] = 0.0;
     gather(xg[0], pk[0], q[0]);
+    // (the oldest vector load: it is back when the gather above has its entry words, so this adds no wait of its own)
+    if constexpr (WARM) asm volatile("" :: "v"(warm));
     int cur = q[0].tile;                  // the tile whose row sums are in LDS
     // parked row sums of the previous tile: park[0] is row pair prow of pdst, the next PB * pleft pairs follow 2 T rows apart
     double2 park[NP];
@@ -1083,29 +1144,57 @@ inline void launch_combine(const SlicedView& V, const Epi& epi, double* dot_part
     else launch_combine_ns<Epi, false>(V, epi, dot_partials, done, s);
 }
 
+// IPXK_ACC_WARM=0: the persistent kernel without the load that warms the slice (read once per process; A/B runs and the tests)
+inline bool acc_warm_on() {
+    static const bool setting = [] { const char* e = getenv("IPXK_ACC_WARM"); return !e || atoi(e) != 0; }();
+    return setting;
+}
+
 // The tile kernel of the accumulated tiles (every unmasked product, nmatrix.hip's N N' passes too): the persistent kernel on
 // acc_persist_grid workgroups (at most one per tile), or one workgroup per tile when IPXK_ACC_PERSIST=0.
 template <class Prod>
 inline void launch_acc_tiles(const AccView& W, const double* x, const int* done, hipStream_t s) {
     static bool lds_attr_set = false;       // per instantiation: dynamic LDS beyond 64 KB has to be allowed once
     if (!lds_attr_set) {
-        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_tile_kernel<Prod>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(kAccMaxRows * sizeof(double))));
-        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(kAccMaxRows * sizeof(double))));
-        IPXK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(kAccMaxRows * sizeof(double))));
+        for (const void* f : {reinterpret_cast<const void*>(spmv_acc_tile_kernel<Prod>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, false>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, true>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, false, false, true>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, true, false, true>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, false, true, false>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, true, true, false>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, false, true, true>),
+                              reinterpret_cast<const void*>(spmv_acc_persist_kernel<Prod, true, true, true>)})
+            IPXK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kAccMaxRows * sizeof(double))));
         lds_attr_set = true;
     }
     const size_t lds = (size_t)W.RB * sizeof(double);
     const int ntiles = W.nrb * W.nslices, G = acc_persist_grid(W.nslices);
     const dim3 pgrid(std::min(G, ntiles));
-    if (G > 0 && W.wide)       // (the wide stream: built unless IPXK_ACC_WIDE=0)
+    // WARM unless IPXK_ACC_WARM=0, and only where every slice starts inside x; the HEAD form (the head tables: built only with
+    // IPXK_ACC_HEAD=1) only on the grid they were built for
+    const bool warm = acc_warm_on() && (long long)(W.nslices - 1) * W.slice_elems < (long long)W.xlen;
+    const bool head = G > 0 && W.head && W.head_grid == (int)pgrid.x && (W.head_wide != nullptr) == (W.wide != nullptr);
+    if (head) {
+        const acc_u32x4* hw = reinterpret_cast<const acc_u32x4*>(W.head_wide);
+        const acc_u32x4* wd = reinterpret_cast<const acc_u32x4*>(W.wide);
+        const dim3 blk(kAccThreads);
+        if (wd && warm) hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, true, true, true>), pgrid, blk, lds, s, W, W.tile_step, W.steps, W.wide_start, wd, x, done, W.head, hw);
+        else if (wd) hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, true, true, false>), pgrid, blk, lds, s, W, W.tile_step, W.steps, W.wide_start, wd, x, done, W.head, hw);
+        else if (warm) hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, false, true, true>), pgrid, blk, lds, s, W, W.tile_step, W.steps, (const unsigned*)nullptr, wd, x, done, W.head, hw);
+        else hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, false, true, false>), pgrid, blk, lds, s, W, W.tile_step, W.steps, (const unsigned*)nullptr, wd, x, done, W.head, hw);
+    } else if (G > 0 && W.wide && warm)
+        hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, true, false, true>), pgrid, dim3(kAccThreads), lds, s, W, W.tile_step, W.steps, W.wide_start,
+                           reinterpret_cast<const acc_u32x4*>(W.wide), x, done, (const unsigned*)nullptr, (const acc_u32x4*)nullptr);
+    else if (G > 0 && W.wide)       // (the wide stream: built unless IPXK_ACC_WIDE=0)
         hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, true>), pgrid, dim3(kAccThreads), lds, s, W, W.tile_step, W.steps, W.wide_start,
-                           reinterpret_cast<const acc_u32x4*>(W.wide), x, done);
+                           reinterpret_cast<const acc_u32x4*>(W.wide), x, done, (const unsigned*)nullptr, (const acc_u32x4*)nullptr);
+    else if (G > 0 && warm)
+        hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, false, false, true>), pgrid, dim3(kAccThreads), lds, s, W, W.tile_step, W.steps,
+                           (const unsigned*)nullptr, (const acc_u32x4*)nullptr, x, done, (const unsigned*)nullptr, (const acc_u32x4*)nullptr);
     else if (G > 0)
         hipLaunchKernelGGL((spmv_acc_persist_kernel<Prod, false>), pgrid, dim3(kAccThreads), lds, s, W, W.tile_step, W.steps,
-                           (const unsigned*)nullptr, (const acc_u32x4*)nullptr, x, done);
+                           (const unsigned*)nullptr, (const acc_u32x4*)nullptr, x, done, (const unsigned*)nullptr, (const acc_u32x4*)nullptr);
     else hipLaunchKernelGGL((spmv_acc_tile_kernel<Prod>), dim3(ntiles), dim3(kAccThreads), lds, s, W, x, done);
 }
 

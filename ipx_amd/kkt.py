@@ -375,7 +375,7 @@ class KktContext:
                 "max_tile", "dominant_bits", "sorted_built", None, None, "so_nrb", "so_RB", "so_nrows_pad",
                 "so_max_sub", None, None, "nnz", "P", "G", "RTQ", "use_acc", "acc_built", "acc_nslices", "acc_nrb",
                 "acc_RB", "acc_nrows_pad", "acc_slice_elems", "acc_nbatches", "acc_deferred", "use_acc_fused", "accf_built", "accf_nrb", "accf_RB",
-                "accf_nbatches", "use_plain", "acc_nsteps", "acc_wide_units")
+                "accf_nbatches", "use_plain", "acc_nsteps", "acc_wide_units", "acc_head_grid")
         d = {k: int(v) for k, v in zip(keys, info) if k is not None}
         d["dominant_fraction"] = float(np.array([d.pop("dominant_bits")], dtype=np.int64).view(np.float64)[0])
         return d, [float(v) for v in ms]
@@ -384,7 +384,7 @@ class KktContext:
         """One array of the device layouts as numpy (see ipxk_layout_array)."""
         dt = (np.uint32, np.uint8, np.int32, np.float64, np.uint32, np.uint8, np.uint32, np.float64, np.int32, np.int32, np.float64,
               np.uint32, np.uint32, np.uint32, np.float64, np.uint32, np.uint32, np.uint32, np.float64, np.int32, np.int32,
-              np.uint32, np.uint32, np.uint32, np.uint32)[array]
+              np.uint32, np.uint32, np.uint32, np.uint32, np.uint32, np.uint32)[array]
         nb = C.c_int64(0)
         self._check(self.lib.ipxk_layout_array(self.h, which, array, None, 0, C.byref(nb)))
         out = np.zeros(nb.value // np.dtype(dt).itemsize, dtype=dt)
