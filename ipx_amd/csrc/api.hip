@@ -145,26 +145,6 @@ void time_collect(Context* c, ipxk_times* times) {
     times->solve_Bt = sum[kTimeBt];
 }
 
-const double* stage_in(Context* c, const double* p, size_t len, DevBuf<double>& buf) {
-    if (!p) return nullptr;
-    if (c->pointer_mode == IPXK_POINTER_DEVICE) return p;
-    if (buf.size() < len) buf.resize(len > 0 ? len : 1);
-    buf.upload(p, len, c->stream);
-    return buf.get();
-}
-
-double* stage_out(Context* c, double* p, size_t len, DevBuf<double>& buf) {
-    if (!p) return nullptr;
-    if (c->pointer_mode == IPXK_POINTER_DEVICE) return p;
-    if (buf.size() < len) buf.resize(len > 0 ? len : 1);
-    return buf.get();
-}
-
-void finish_out(Context* c, double* user, const double* dev, size_t len) {
-    if (!user || c->pointer_mode == IPXK_POINTER_DEVICE) return;
-    staged_d2h(user, dev, len * sizeof(double), c->stream);
-}
-
 template <class F>
 static int guarded(F&& f) {
     try {
@@ -182,7 +162,101 @@ static int guarded(F&& f) {
     }
 }
 
-static void bind_device(Context* c) { IPXK_HIP(hipSetDevice(c->device)); }
+static void bind_device(Context* c) {
+    IPXK_REQUIRE(c != nullptr, "ctx is NULL");
+    IPXK_HIP(hipSetDevice(c->device));
+}
+
+namespace {
+
+struct ModelVectors { const double *b, *c, *lb, *ub; };
+
+// The vector arguments of one call.  Device pointer mode: an argument is the caller's device memory and is handed through.
+// Host pointer mode: every argument takes the next slot of Context::stage_slots; in() and inout() upload it on the context's
+// stream, finish() copies each out() and inout() back in the order they were declared.  A null argument stays null.
+class Staged {
+public:
+    explicit Staged(Context* ctx) : c(ctx) { bind_device(c); }
+    const double* in(const double* p, size_t len) { return p && host() ? upload(p, len) : p; }
+    double* out(double* p, size_t len) {
+        if (!p || !host()) return p;
+        double* dev = slot(len);
+        outs[nouts++] = Out{p, dev, len};
+        return dev;
+    }
+    double* inout(double* p, size_t len) {
+        if (!p || !host()) return p;
+        double* dev = out(p, len);
+        staged_h2d(dev, p, len * sizeof(double), c->stream);
+        return dev;
+    }
+    // a vector that lives on the host whatever the pointer mode
+    const double* upload(const double* p, size_t len) {
+        double* dev = slot(len);
+        staged_h2d(dev, p, len * sizeof(double), c->stream);
+        return dev;
+    }
+    const unsigned char* in_bytes(const unsigned char* p, size_t len) {
+        if (!p || !host()) return p;
+        IPXK_REQUIRE(!bytes_taken, "more byte arguments than staging slots");
+        bytes_taken = true;
+        c->stage_bytes.ensure(std::max<size_t>(len, 1));
+        staged_h2d(c->stage_bytes.get(), p, len, c->stream);
+        return c->stage_bytes.get();
+    }
+    // b [m] and c, lb, ub [n+m] of the model in solver form
+    ModelVectors model(const double* b, const double* cc, const double* lb, const double* ub) {
+        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
+        return {in(b, m), in(cc, N), in(lb, N), in(ub, N)};
+    }
+    void finish() {
+        for (int k = 0; k < nouts; k++) staged_d2h(outs[k].user, outs[k].dev, outs[k].len * sizeof(double), c->stream);
+        IPXK_HIP(hipStreamSynchronize(c->stream));
+    }
+
+private:
+    bool host() const { return c->pointer_mode == IPXK_POINTER_HOST; }
+    double* slot(size_t len) {
+        IPXK_REQUIRE(nslots < Context::kStageSlots, "more vector arguments than staging slots");
+        DevBuf<double>& buf = c->stage_slots[nslots++];
+        buf.ensure(std::max<size_t>(len, 1));
+        return buf.get();
+    }
+    Context* c;
+    int nslots = 0, nouts = 0;
+    bool bytes_taken = false;
+    struct Out { double* user; const double* dev; size_t len; } outs[Context::kStageSlots];
+};
+
+// NormalMatrix::Prepare(nullptr) / DiagonalPrecond::Factorize(nullptr): 1 for the structural columns, 0 for the slack columns
+std::vector<double> unit_weights(const Context* c) {
+    std::vector<double> w((size_t)(c->n + c->m), 0.0);
+    std::fill(w.begin(), w.begin() + c->n, 1.0);
+    return w;
+}
+
+// milliseconds the context's stream takes for `reps` runs of launch()
+template <class F>
+double time_on_stream(Context* c, int reps, F&& launch) {
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    IPXK_HIP(hipEventCreate(&ev.e0));
+    IPXK_HIP(hipEventCreate(&ev.e1));
+    IPXK_HIP(hipEventRecord(ev.e0, c->stream));
+    for (int r = 0; r < reps; r++) launch();
+    IPXK_HIP(hipEventRecord(ev.e1, c->stream));
+    IPXK_HIP(hipEventSynchronize(ev.e1));
+    float ms = 0.f;
+    IPXK_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    return ms;
+}
+
+}  // namespace
 
 }  // namespace ipxk
 
@@ -269,7 +343,8 @@ int ipxk_reset_solver_state(ipxk_context* c, double lu_pivottol) {
         // factors, N, the tightened pivot tolerance.  The buffers stay (grow-only workspaces); nothing of their content is used again.
         c->W = nullptr;
         c->normal_prepared = c->diag_factorized = c->kkt_diag_factorized = c->it_set = false;
-        c->sb_live = c->drv_live = false;
+        c->sb.clear();
+        c->drv.clear();
         c->postprocessed = false;
         c->crossover_start = 0.0;
         c->drop_primal = c->drop_dual = 0.0;
@@ -349,18 +424,12 @@ int ipxk_normal_prepare(ipxk_context* c, const double* W) {
         IPXK_REQUIRE(c != nullptr, "ctx is NULL");
         bind_device(c);
         const size_t N = (size_t)(c->n + c->m);
-        if (!W) {
-            std::vector<double> w(N, 0.0);
-            std::fill(w.begin(), w.begin() + c->n, 1.0);
-            c->W_own.resize(N);
-            c->W_own.upload(w, c->stream);
-            IPXK_HIP(hipStreamSynchronize(c->stream));
-            c->W = c->W_own.get();
-        } else if (c->pointer_mode == IPXK_POINTER_DEVICE) {
+        if (W && c->pointer_mode == IPXK_POINTER_DEVICE) {
             c->W = W;
         } else {
             c->W_own.resize(N);
-            c->W_own.upload(W, N, c->stream);
+            if (W) c->W_own.upload(W, N, c->stream);
+            else c->W_own.upload(unit_weights(c), c->stream);
             IPXK_HIP(hipStreamSynchronize(c->stream));
             c->W = c->W_own.get();
         }
@@ -372,17 +441,16 @@ int ipxk_normal_apply(ipxk_context* c, const double* rhs, double* lhs, double* r
     return guarded([&] {
         IPXK_REQUIRE(c && rhs && lhs, "NULL argument");
         IPXK_REQUIRE(c->normal_prepared, "NormalMatrix not prepared");
-        bind_device(c);
-        if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
+        Staged args(c);
+        c->ensure_partials();
         const size_t m = (size_t)c->m;
-        const double* drhs = stage_in(c, rhs, m, c->v_rhs);
-        double* dlhs = stage_out(c, lhs, m, c->v_lhs);
+        const double* drhs = args.in(rhs, m);
+        double* dlhs = args.out(lhs, m);
         int np = 0;
         normal_apply_dev(c, c->W, drhs, dlhs, rhs_dot_lhs ? &np : nullptr, nullptr);
         IPXK_HIP(hipGetLastError());
         if (rhs_dot_lhs) *rhs_dot_lhs = reduce_partials_host(c, kPartCdot, np, false);
-        finish_out(c, lhs, dlhs, m);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -390,25 +458,12 @@ int ipxk_normal_apply(ipxk_context* c, const double* rhs, double* lhs, double* r
 int ipxk_diag_factorize(ipxk_context* c, const double* W, int precond_dense_cols, ipxint* errflag) {
     return guarded([&] {
         IPXK_REQUIRE(c && errflag, "NULL argument");
-        bind_device(c);
-        if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
+        Staged args(c);
+        c->ensure_partials();
         const size_t N = (size_t)(c->n + c->m);
-        const double* dW;
-        DevBuf<double> tmp;
-        if (!W) {
-            std::vector<double> w(N, 0.0);
-            std::fill(w.begin(), w.begin() + c->n, 1.0);
-            tmp.upload(w, c->stream);
-            IPXK_HIP(hipStreamSynchronize(c->stream));
-            dW = tmp.get();
-        } else if (c->pointer_mode == IPXK_POINTER_DEVICE) {
-            dW = W;
-        } else {
-            tmp.upload(W, N, c->stream);
-            dW = tmp.get();
-        }
+        const double* dW = W ? args.in(W, N) : args.upload(unit_weights(c).data(), N);
         diag_factorize_dev(c, dW, precond_dense_cols != 0, errflag);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -416,15 +471,14 @@ int ipxk_diag_apply(ipxk_context* c, const double* rhs, double* lhs, double* rhs
     return guarded([&] {
         IPXK_REQUIRE(c && rhs && lhs, "NULL argument");
         IPXK_REQUIRE(c->diag_factorized, "DiagonalPrecond not factorized");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m;
-        const double* drhs = stage_in(c, rhs, m, c->v_rhs);
-        double* dlhs = stage_out(c, lhs, m, c->v_lhs);
+        const double* drhs = args.in(rhs, m);
+        double* dlhs = args.out(lhs, m);
         const int np = diag_apply_dev(c, drhs, dlhs, kPartScratch, nullptr);
         IPXK_HIP(hipGetLastError());
         if (rhs_dot_lhs) *rhs_dot_lhs = reduce_partials_host(c, kPartScratch, np, false);
-        finish_out(c, lhs, dlhs, m);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -451,22 +505,20 @@ int ipxk_pcr_solve(ipxk_context* c, const double* rhs, double tol, const double*
                    ipxint hist_cap, ipxk_times* times) {
     return guarded([&] {
         IPXK_REQUIRE(c && rhs && lhs && iter && errflag, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m;
-        const bool host = c->pointer_mode == IPXK_POINTER_HOST;
         // Infnorm(lhs) == 0 saves one operator application (conjugate_residuals.cc:118-123);
         // with device pointers the general branch is taken (same result: C*0 == 0).
-        const bool zero = host && host_is_zero(lhs, m);
-        const double* drhs = stage_in(c, rhs, m, c->v_rhs);
-        const double* dscale = stage_in(c, resscale, m, c->v_resscale_in);
-        double* dlhs = stage_out(c, lhs, m, c->v_lhs);
-        if (host) staged_h2d(dlhs, lhs, m * sizeof(double), c->stream);
+        const bool zero = c->pointer_mode == IPXK_POINTER_HOST && host_is_zero(lhs, m);
+        const double* drhs = args.in(rhs, m);
+        const double* dscale = args.in(resscale, m);
+        double* dlhs = args.inout(lhs, m);
         if (times) *times = ipxk_times{};
         CrResult r = pcr_solve_dev(c, drhs, tol, dscale, maxiter, dlhs, zero, interrupt, interrupt_user,
                                    resnorm_hist, hist_cap, times);
         *iter = r.iter;
         *errflag = r.errflag;
-        finish_out(c, lhs, dlhs, m);
+        args.finish();
     });
 }
 
@@ -476,20 +528,18 @@ int ipxk_cr_solve(ipxk_context* c, const double* rhs, double tol, const double* 
                   ipxint hist_cap, ipxk_times* times) {
     return guarded([&] {
         IPXK_REQUIRE(c && rhs && lhs && iter && errflag, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m;
-        const bool host = c->pointer_mode == IPXK_POINTER_HOST;
-        const bool zero = host && host_is_zero(lhs, m);
-        const double* drhs = stage_in(c, rhs, m, c->v_rhs);
-        const double* dscale = stage_in(c, resscale, m, c->v_resscale_in);
-        double* dlhs = stage_out(c, lhs, m, c->v_lhs);
-        if (host) staged_h2d(dlhs, lhs, m * sizeof(double), c->stream);
+        const bool zero = c->pointer_mode == IPXK_POINTER_HOST && host_is_zero(lhs, m);
+        const double* drhs = args.in(rhs, m);
+        const double* dscale = args.in(resscale, m);
+        double* dlhs = args.inout(lhs, m);
         if (times) *times = ipxk_times{};
         CrResult r = cr_solve_dev(c, drhs, tol, dscale, maxiter, dlhs, zero, interrupt, interrupt_user,
                                   resnorm_hist, hist_cap, times);
         *iter = r.iter;
         *errflag = r.errflag;
-        finish_out(c, lhs, dlhs, m);
+        args.finish();
         check_sweep_abort(c);
     });
 }
@@ -500,15 +550,14 @@ int ipxk_kkt_diag_factorize(ipxk_context* c, const double* xl, const double* xu,
     return guarded([&] {
         IPXK_REQUIRE(c && errflag, "NULL argument");
         IPXK_REQUIRE(!xl || (xu && zl && zu), "iterate vectors must be all NULL or all given");
-        bind_device(c);
+        Staged args(c);
         const size_t N = (size_t)(c->n + c->m);
-        DevBuf<double> t0, t1, t2, t3;
-        const double* dxl = stage_in(c, xl, N, t0);
-        const double* dxu = stage_in(c, xu, N, t1);
-        const double* dzl = stage_in(c, zl, N, t2);
-        const double* dzu = stage_in(c, zu, N, t3);
+        const double* dxl = args.in(xl, N);
+        const double* dxu = args.in(xu, N);
+        const double* dzl = args.in(zl, N);
+        const double* dzu = args.in(zu, N);
         kkt_diag_factorize_dev(c, dxl, dxu, dzl, dzu, mu, precond_dense_cols != 0, errflag);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -517,19 +566,17 @@ int ipxk_kkt_diag_solve(ipxk_context* c, const double* a, const double* b, doubl
                         ipxk_interrupt_fn interrupt, void* interrupt_user, ipxk_times* times) {
     return guarded([&] {
         IPXK_REQUIRE(c && a && b && x && y && iter && errflag, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* da = stage_in(c, a, N, c->k_a);
-        const double* db = stage_in(c, b, m, c->k_b);
-        double* dx = stage_out(c, x, N, c->k_x);
-        double* dy = stage_out(c, y, m, c->k_y);
+        const double* da = args.in(a, N);
+        const double* db = args.in(b, m);
+        double* dx = args.out(x, N);
+        double* dy = args.out(y, m);
         if (times) *times = ipxk_times{};
         CrResult r = kkt_diag_solve_dev(c, da, db, tol, maxiter, dx, dy, interrupt, interrupt_user, times);
         *iter = r.iter;
         *errflag = r.errflag;
-        finish_out(c, x, dx, N);
-        finish_out(c, y, dy, m);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -553,27 +600,22 @@ int ipxk_newton_solve(ipxk_context* c, int use_basis, const double* rb, const do
         IPXK_REQUIRE(c && sl && su && xl && xu && zl && zu && state && dx && dxl && dxu && dy && dzl && dzu &&
                      iter && errflag, "NULL argument");
         IPXK_REQUIRE(use_basis ? c->split != nullptr : c->kkt_diag_factorized, "KKT solver not factorized");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         const double* in[10] = {rb, rc, rl, ru, sl, su, xl, xu, zl, zu};
         const double* din[10];
-        for (int k = 0; k < 10; k++) din[k] = in[k] ? stage_in(c, in[k], k == 0 ? m : N, c->nw_in[k]) : nullptr;
-        const unsigned char* dstate = state;
-        if (c->pointer_mode == IPXK_POINTER_HOST) {
-            c->nw_state.upload(state, N, c->stream);
-            dstate = c->nw_state.get();
-        }
+        for (int k = 0; k < 10; k++) din[k] = args.in(in[k], k == 0 ? m : N);
+        const unsigned char* dstate = args.in_bytes(state, N);
         double* out[6] = {dx, dxl, dxu, dy, dzl, dzu};
         double* dout[6];
-        for (int k = 0; k < 6; k++) dout[k] = stage_out(c, out[k], k == 3 ? m : N, c->nw_out[k]);
+        for (int k = 0; k < 6; k++) dout[k] = args.out(out[k], k == 3 ? m : N);
         if (times) *times = ipxk_times{};
         CrResult r = newton_solve_dev(c, use_basis != 0, din[0], din[1], din[2], din[3], din[4], din[5], din[6],
                                       din[7], din[8], din[9], dstate, tol, maxiter, dout[0], dout[1], dout[2],
                                       dout[3], dout[4], dout[5], interrupt, interrupt_user, times);
         *iter = r.iter;
         *errflag = r.errflag;
-        for (int k = 0; k < 6; k++) finish_out(c, out[k], dout[k], k == 3 ? m : N);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -586,6 +628,17 @@ static void copy_out(Context* c, void* dst, const void* src_dev, size_t bytes) {
     if (c->pointer_mode == IPXK_POINTER_HOST) staged_d2h(dst, src_dev, bytes, c->stream);
     else IPXK_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
 }
+// the six vectors of an iterate into the resident one: x, xl, xu [n+m], y [m], zl, zu [n+m]
+static void load_iterate_vectors(Context* c, const double* x, const double* xl, const double* xu, const double* y,
+                                 const double* zl, const double* zu) {
+    DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
+    const double* src[6] = {x, xl, xu, y, zl, zu};
+    for (int k = 0; k < 6; k++) {
+        const size_t len = (size_t)(k == 3 ? c->m : c->n + c->m);
+        dst[k]->resize(std::max<size_t>(len, 1));
+        copy_in(c, dst[k]->get(), src[k], len * sizeof(double));
+    }
+}
 
 // Column partition: the ranks agree on the verdict and on the replicated parts (y, the slack parts of x, xl, xu, zl, zu
 // and state) with one all-reduce, so that ranks holding different iterates fail together instead of in a later collective.
@@ -597,17 +650,10 @@ int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const d
         if (!comm_cols(c)) IPXK_REQUIRE(args, "NULL argument");
         bind_device(c);
         c->it_set = false;
-        c->postprocessed = false;
-        c->sb_live = c->drv_live = false;                 // a starting basis belongs to the iterate it was built from
+        begin_new_iterate(c);
         const size_t m = (size_t)c->m, n = (size_t)c->n, N = (size_t)(c->n + c->m);
-        DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
-        const double* src[6] = {x, xl, xu, y, zl, zu};
         if (args) {
-            for (int k = 0; k < 6; k++) {
-                const size_t len = k == 3 ? m : N;
-                dst[k]->resize(std::max<size_t>(len, 1));
-                copy_in(c, dst[k]->get(), src[k], len * sizeof(double));
-            }
+            load_iterate_vectors(c, x, xl, xu, y, zl, zu);
             c->it_state.resize(std::max<size_t>(N, 1));
             copy_in(c, c->it_state.get(), state, N);
         }
@@ -628,7 +674,8 @@ int ipxk_iterate_set(ipxk_context* c, const double* x, const double* xl, const d
             uint64_t fp = 0;
             if (args) {
                 std::vector<double> h(6 * m);
-                for (int k = 0; k < 6; k++) staged_d2h(h.data() + k * m, dst[k]->get() + (k == 3 ? 0 : n), m * sizeof(double), c->stream);
+                const DevBuf<double>* it[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
+                for (int k = 0; k < 6; k++) staged_d2h(h.data() + k * m, it[k]->get() + (k == 3 ? 0 : n), m * sizeof(double), c->stream);
                 std::vector<unsigned char> hs(m);
                 staged_d2h(hs.data(), c->it_state.get() + n, m, c->stream);
                 Fingerprint F;
@@ -660,13 +707,13 @@ int ipxk_iterate_update(ipxk_context* c, double sp, const double* dx, const doub
                         double sd, const double* dy, const double* dzl, const double* dzu) {
     return guarded([&] {
         IPXK_REQUIRE(c, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
         const double* in[6] = {dx, dxl, dxu, dy, dzl, dzu};
         const double* din[6];
-        for (int k = 0; k < 6; k++) din[k] = in[k] ? stage_in(c, in[k], k == 3 ? m : N, c->nw_out[k]) : nullptr;
+        for (int k = 0; k < 6; k++) din[k] = args.in(in[k], k == 3 ? m : N);
         iterate_update_dev(c, sp, din[0], din[1], din[2], sd, din[3], din[4], din[5]);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -675,22 +722,15 @@ int ipxk_iterate_residuals(ipxk_context* c, const double* b, const double* cc, c
                            double* dresidual) {
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && rb && rc && rl && ru, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        double* drb = stage_out(c, rb, m, c->nw_out[0]);
-        double* drc = stage_out(c, rc, N, c->nw_out[1]);
-        double* drl = stage_out(c, rl, N, c->nw_out[2]);
-        double* dru = stage_out(c, ru, N, c->nw_out[4]);
-        iterate_residuals_dev(c, db, dc, dlb, dub, drb, drc, drl, dru, presidual, dresidual);
-        finish_out(c, rb, drb, m);
-        finish_out(c, rc, drc, N);
-        finish_out(c, rl, drl, N);
-        finish_out(c, ru, dru, N);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        double* drb = args.out(rb, m);
+        double* drc = args.out(rc, N);
+        double* drl = args.out(rl, N);
+        double* dru = args.out(ru, N);
+        iterate_residuals_dev(c, M.b, M.c, M.lb, M.ub, drb, drc, drl, dru, presidual, dresidual);
+        args.finish();
     });
 }
 
@@ -706,10 +746,11 @@ int ipxk_step_to_boundary(ipxk_context* c, const double* x, const double* dx, ip
                           double* alpha, ipxint* blocking_index) {
     return guarded([&] {
         IPXK_REQUIRE(c && x && dx && alpha && len >= 0, "bad argument");
-        bind_device(c);
-        const double* dxv = stage_in(c, x, (size_t)len, c->nw_in[0]);
-        const double* ddx = stage_in(c, dx, (size_t)len, c->nw_in[1]);
+        Staged args(c);
+        const double* dxv = args.in(x, (size_t)len);
+        const double* ddx = args.in(dx, (size_t)len);
         *alpha = step_to_boundary_dev(c, dxv, ddx, len, alpha0, blocking_index);
+        args.finish();
     });
 }
 
@@ -721,14 +762,10 @@ int ipxk_ipm_step(ipxk_context* c, int use_basis, const double* b, const double*
         IPXK_REQUIRE(use_basis ? c->split != nullptr : c->kkt_diag_factorized, "KKT solver not factorized");
         IPXK_REQUIRE(!comm_rows(c), "ipxk_ipm_step does not run on a row-partitioned system: partition the structural columns "
                                     "(ipxk_comm_init_columns)");
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        ipm_step_dev(c, use_basis != 0, db, dc, dlb, dub, kkt_tol, maxiter, info, interrupt, interrupt_user);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        ipm_step_dev(c, use_basis != 0, M.b, M.c, M.lb, M.ub, kkt_tol, maxiter, info, interrupt, interrupt_user);
+        args.finish();
     });
 }
 
@@ -736,14 +773,10 @@ int ipxk_iterate_objectives(ipxk_context* c, const double* b, const double* cc, 
                             double out3[3]) {
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && out3, "NULL argument");
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        iterate_objectives_dev(c, db, dc, dlb, dub, out3);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        iterate_objectives_dev(c, M.b, M.c, M.lb, M.ub, out3);
+        args.finish();
     });
 }
 
@@ -751,14 +784,10 @@ int ipxk_ipm_driver(ipxk_context* c, const double* b, const double* cc, const do
                     const ipxk_ipm_params* params, ipxk_ipm_info* info, ipxk_interrupt_fn interrupt, void* interrupt_user) {
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && params && info, "NULL argument");
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        ipm_driver_dev(c, db, dc, dlb, dub, params, info, interrupt, interrupt_user);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        ipm_driver_dev(c, M.b, M.c, M.lb, M.ub, params, info, interrupt, interrupt_user);
+        args.finish();
     });
 }
 
@@ -768,14 +797,10 @@ int ipxk_ipm_driver_basis(ipxk_context* c, const double* b, const double* cc, co
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && params && info, "NULL argument");
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // its Factorize runs the device LU and Maxvolume
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        ipm_driver_dev(c, db, dc, dlb, dub, params, info, interrupt, interrupt_user, true, basis_out, status_out);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        ipm_driver_dev(c, M.b, M.c, M.lb, M.ub, params, info, interrupt, interrupt_user, true, basis_out, status_out);
+        args.finish();
     });
 }
 
@@ -784,16 +809,11 @@ int ipxk_ipm_starting_point(ipxk_context* c, const double* b, const double* cc, 
                             void* interrupt_user) {
     return guarded([&] {
         IPXK_REQUIRE(c, "NULL argument");
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        c->sb_live = c->drv_live = false;
-        c->postprocessed = false;
-        ipm_starting_point_dev(c, db, dc, dlb, dub, params, info, interrupt, interrupt_user);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        begin_new_iterate(c);
+        ipm_starting_point_dev(c, M.b, M.c, M.lb, M.ub, params, info, interrupt, interrupt_user);
+        args.finish();
     });
 }
 
@@ -806,14 +826,10 @@ int ipxk_ipm_starting_basis(ipxk_context* c, const double* b, const double* cc, 
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // it runs the device LU
         IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
         IPXK_REQUIRE(log_cap >= 0 && (exchange_log || log_cap == 0), "exchange_log is NULL");
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        ipm_starting_basis_dev(c, db, dc, dlb, dub, params, info, basis_out, status_out, exchange_log, log_cap, interrupt, interrupt_user);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        ipm_starting_basis_dev(c, M.b, M.c, M.lb, M.ub, params, info, basis_out, status_out, exchange_log, log_cap, interrupt, interrupt_user);
+        args.finish();
     });
 }
 
@@ -822,29 +838,22 @@ int ipxk_ipm_load_starting_point(ipxk_context* c, const double* x, const double*
                                  const double* zl, const double* zu, const double* lb, const double* ub) {
     return guarded([&] {
         IPXK_REQUIRE(c, "NULL argument");
-        const bool args = x && xl && xu && y && zl && zu && lb && ub;
-        IPXK_REQUIRE(args || comm_cols(c), "NULL argument");
-        bind_device(c);
+        const bool given = x && xl && xu && y && zl && zu && lb && ub;
+        IPXK_REQUIRE(given || comm_cols(c), "NULL argument");
+        Staged args(c);
         c->it_set = false;
-        c->postprocessed = false;
-        c->sb_live = c->drv_live = false;                 // a starting basis belongs to the iterate it was built from
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        std::string err = args ? std::string() : std::string("NULL argument");
-        if (!args) {
-            agree_on_arguments(c, err, 0, "ipxk_ipm_load_starting_point", "y and the slack parts of x, xl, xu, zl, zu, lb and ub");
+        begin_new_iterate(c);
+        const size_t N = (size_t)(c->n + c->m);
+        if (!given) {
+            agree_on_arguments(c, "NULL argument", 0, "ipxk_ipm_load_starting_point", "y and the slack parts of x, xl, xu, zl, zu, lb and ub");
             return;
         }
-        DevBuf<double>* dst[6] = {&c->it_x, &c->it_xl, &c->it_xu, &c->it_y, &c->it_zl, &c->it_zu};
-        const double* src[6] = {x, xl, xu, y, zl, zu};
-        for (int k = 0; k < 6; k++) {
-            const size_t len = k == 3 ? m : N;
-            dst[k]->resize(std::max<size_t>(len, 1));
-            copy_in(c, dst[k]->get(), src[k], len * sizeof(double));
-        }
+        load_iterate_vectors(c, x, xl, xu, y, zl, zu);
         c->it_state.resize(std::max<size_t>(N, 1));
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        const double* dlb = args.in(lb, N);
+        const double* dub = args.in(ub, N);
         ipm_load_starting_point_dev(c, dlb, dub);
+        args.finish();
     });
 }
 
@@ -852,24 +861,25 @@ int ipxk_ipm_load_starting_point(ipxk_context* c, const double* x, const double*
 int ipxk_iterate_postprocess(ipxk_context* c, const double* cc, const double* lb, const double* ub) {
     return guarded([&] {
         IPXK_REQUIRE(c && cc && lb && ub, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t N = (size_t)(c->n + c->m);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        const double* dc = args.in(cc, N);
+        const double* dlb = args.in(lb, N);
+        const double* dub = args.in(ub, N);
         iterate_postprocess_dev(c, dc, dlb, dub);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
 int ipxk_iterate_dropping_residuals(ipxk_context* c, const double* lb, const double* ub, double out2[2]) {
     return guarded([&] {
         IPXK_REQUIRE(c && lb && ub && out2, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t N = (size_t)(c->n + c->m);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
+        const double* dlb = args.in(lb, N);
+        const double* dub = args.in(ub, N);
         iterate_dropping_residuals_dev(c, dlb, dub, out2);
+        args.finish();
     });
 }
 
@@ -900,14 +910,10 @@ int ipxk_ipm_drop_degenerate(ipxk_context* c, const double* b, const double* cc,
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // it runs the device LU
         IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
         IPXK_REQUIRE(log_cap >= 0 && (log || log_cap == 0), "log is NULL");
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        ipm_drop_degenerate_dev(c, db, dc, dlb, dub, info, basis_out, status_out, colscale_out, log, log_cap, interrupt, interrupt_user);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        ipm_drop_degenerate_dev(c, M.b, M.c, M.lb, M.ub, info, basis_out, status_out, colscale_out, log, log_cap, interrupt, interrupt_user);
+        args.finish();
     });
 }
 
@@ -934,28 +940,19 @@ int ipxk_iterate_drop_to_complementarity(ipxk_context* c, const double* lb, cons
                                          double* z_out) {
     return guarded([&] {
         IPXK_REQUIRE(c && lb && ub && x_out && y_out && z_out, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        double* dx = stage_out(c, x_out, N, c->nw_out[0]);
-        double* dy = stage_out(c, y_out, m, c->nw_out[3]);
-        double* dz = stage_out(c, z_out, N, c->nw_out[1]);
+        const double* dlb = args.in(lb, N);
+        const double* dub = args.in(ub, N);
+        double* dx = args.out(x_out, N);
+        double* dy = args.out(y_out, m);
+        double* dz = args.out(z_out, N);
         iterate_drop_to_complementarity_dev(c, dlb, dub, dx, dy, dz);
-        finish_out(c, x_out, dx, N);
-        finish_out(c, y_out, dy, m);
-        finish_out(c, z_out, dz, N);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
 // ---- crossover in solver form (crossover.hip) ------------------------------------------------------------------------
-// an in/out vector: the caller's device memory, or the staging buffer with the host vector in it
-static double* stage_inout(Context* c, double* p, size_t len, DevBuf<double>& buf) {
-    double* d = stage_out(c, p, len, buf);
-    if (d != p) staged_h2d(d, p, len * sizeof(double), c->stream);
-    return d;
-}
 
 int ipxk_crossover_push_dual(ipxk_context* c, const double* lb, const double* ub, const double* x, double* y, double* z,
                              const ipxint* variables, ipxint num_variables, ipxint* basis, const ipxk_crossover_params* params,
@@ -964,17 +961,15 @@ int ipxk_crossover_push_dual(ipxk_context* c, const double* lb, const double* ub
         IPXK_REQUIRE(c && lb && ub && x && y && z && basis && info && (variables || num_variables == 0), "NULL argument");
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
         IPXK_REQUIRE(num_variables >= 0 && log_cap >= 0 && (log || log_cap == 0), "log is NULL or a negative count");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        const double* dx = stage_in(c, x, N, c->nw_out[0]);
-        double* dy = stage_inout(c, y, m, c->nw_out[3]);
-        double* dz = stage_inout(c, z, N, c->nw_out[1]);
+        const double* dlb = args.in(lb, N);
+        const double* dub = args.in(ub, N);
+        const double* dx = args.in(x, N);
+        double* dy = args.inout(y, m);
+        double* dz = args.inout(z, N);
         crossover_push_dual_dev(c, dlb, dub, dx, dy, dz, variables, num_variables, basis, params, info, log, log_cap, interrupt, interrupt_user);
-        finish_out(c, y, dy, m);
-        finish_out(c, z, dz, N);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -986,15 +981,14 @@ int ipxk_crossover_push_primal(ipxk_context* c, const double* lb, const double* 
         IPXK_REQUIRE(c && lb && ub && x && basis && info && (variables || num_variables == 0), "NULL argument");
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
         IPXK_REQUIRE(num_variables >= 0 && log_cap >= 0 && (log || log_cap == 0), "log is NULL or a negative count");
-        bind_device(c);
+        Staged args(c);
         const size_t N = (size_t)(c->n + c->m);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        double* dx = stage_inout(c, x, N, c->nw_out[0]);
+        const double* dlb = args.in(lb, N);
+        const double* dub = args.in(ub, N);
+        double* dx = args.inout(x, N);
         crossover_push_primal_dev(c, dlb, dub, dx, variables, num_variables, fixed_at_bound, basis, params, info, log, log_cap, interrupt,
                                   interrupt_user);
-        finish_out(c, x, dx, N);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -1003,18 +997,15 @@ int ipxk_crossover_basic_solution(ipxk_context* c, const double* b, const double
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && basis && x && y && z, "NULL argument");
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        double* dx = stage_inout(c, x, N, c->nw_out[0]);
-        double* dy = stage_out(c, y, m, c->nw_out[3]);
-        double* dz = stage_inout(c, z, N, c->nw_out[1]);
+        const double* db = args.in(b, m);
+        const double* dc = args.in(cc, N);
+        double* dx = args.inout(x, N);
+        double* dy = args.out(y, m);
+        double* dz = args.inout(z, N);
         crossover_basic_solution_dev(c, db, dc, basis, dx, dy, dz);
-        finish_out(c, x, dx, N);
-        finish_out(c, y, dy, m);
-        finish_out(c, z, dz, N);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -1026,21 +1017,15 @@ int ipxk_crossover_run(ipxk_context* c, const double* b, const double* cc, const
         IPXK_REQUIRE(c && b && cc && lb && ub && basis && info && x_out && y_out && z_out, "NULL argument");
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
         IPXK_REQUIRE(log_cap >= 0 && (log || log_cap == 0), "log is NULL");
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        const double* dw = stage_in(c, weights, N, c->nw_in[4]);
-        double* dx = stage_out(c, x_out, N, c->nw_out[0]);
-        double* dy = stage_out(c, y_out, m, c->nw_out[3]);
-        double* dz = stage_out(c, z_out, N, c->nw_out[1]);
-        crossover_run_dev(c, db, dc, dlb, dub, dw, basis, params, info, dx, dy, dz, basic_statuses, log, log_cap, interrupt, interrupt_user);
-        finish_out(c, x_out, dx, N);
-        finish_out(c, y_out, dy, m);
-        finish_out(c, z_out, dz, N);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        const double* dw = args.in(weights, N);
+        double* dx = args.out(x_out, N);
+        double* dy = args.out(y_out, m);
+        double* dz = args.out(z_out, N);
+        crossover_run_dev(c, M.b, M.c, M.lb, M.ub, dw, basis, params, info, dx, dy, dz, basic_statuses, log, log_cap, interrupt, interrupt_user);
+        args.finish();
     });
 }
 
@@ -1050,14 +1035,10 @@ int ipxk_ipm_solve(ipxk_context* c, const double* b, const double* cc, const dou
     return guarded([&] {
         IPXK_REQUIRE(c && b && cc && lb && ub && params && info, "NULL argument");
         IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);     // its basis phase runs the device LU and Maxvolume
-        bind_device(c);
-        const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* db = stage_in(c, b, m, c->nw_in[0]);
-        const double* dc = stage_in(c, cc, N, c->nw_in[1]);
-        const double* dlb = stage_in(c, lb, N, c->nw_in[2]);
-        const double* dub = stage_in(c, ub, N, c->nw_in[3]);
-        ipm_solve_dev(c, db, dc, dlb, dub, params, info, basis_out, status_out, interrupt, interrupt_user);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        Staged args(c);
+        const ModelVectors M = args.model(b, cc, lb, ub);
+        ipm_solve_dev(c, M.b, M.c, M.lb, M.ub, params, info, basis_out, status_out, interrupt, interrupt_user);
+        args.finish();
     });
 }
 
@@ -1179,21 +1160,16 @@ int ipxk_lp_postsolve_basic(ipxk_lp* lp, const double* x_solver, const double* y
         IPXK_REQUIRE(lp && x_solver && z_solver && basic_statuses, "NULL argument");
         Context* c = lp_context(lp->p);
         IPXK_REQUIRE(y_solver || c->m == 0, "NULL argument");
-        bind_device(c);
+        Staged args(c);
         int64_t num_constr = 0, num_var = 0;
         lp_dims(lp->p, &num_constr, &num_var);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m), nc = (size_t)num_constr, nv = (size_t)num_var;
-        const double* dxs = stage_in(c, x_solver, N, c->nw_in[0]);
-        const double* dys = stage_in(c, y_solver, m, c->nw_in[1]);
-        const double* dzs = stage_in(c, z_solver, N, c->nw_in[2]);
-        const LpBasicPoint out{stage_out(c, x, nv, c->nw_out[0]), stage_out(c, slack, nc, c->nw_out[1]), stage_out(c, y, nc, c->nw_out[2]),
-                               stage_out(c, z, nv, c->nw_out[3]), cbasis, vbasis};
+        const double* dxs = args.in(x_solver, N);
+        const double* dys = args.in(y_solver, m);
+        const double* dzs = args.in(z_solver, N);
+        const LpBasicPoint out{args.out(x, nv), args.out(slack, nc), args.out(y, nc), args.out(z, nv), cbasis, vbasis};
         lp_postsolve_basic(lp->p, dxs, dys, dzs, basic_statuses, out);
-        finish_out(c, x, out.x, nv);
-        finish_out(c, slack, out.slack, nc);
-        finish_out(c, y, out.y, nc);
-        finish_out(c, z, out.z, nv);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -1211,17 +1187,17 @@ int ipxk_lp_evaluate_basic(ipxk_lp* lp, const double* x, const double* slack, co
     return guarded([&] {
         IPXK_REQUIRE(lp && x && z && vbasis && out, "NULL argument");
         Context* c = lp_context(lp->p);
-        bind_device(c);
+        Staged args(c);
         int64_t num_constr = 0, num_var = 0;
         lp_dims(lp->p, &num_constr, &num_var);
         IPXK_REQUIRE((slack && y) || num_constr == 0, "NULL argument");
         const size_t nc = (size_t)num_constr, nv = (size_t)num_var;
-        const double* dx = stage_in(c, x, nv, c->nw_in[0]);
-        const double* ds = stage_in(c, slack, nc, c->nw_in[1]);
-        const double* dy = stage_in(c, y, nc, c->nw_in[2]);
-        const double* dz = stage_in(c, z, nv, c->nw_in[3]);
+        const double* dx = args.in(x, nv);
+        const double* ds = args.in(slack, nc);
+        const double* dy = args.in(y, nc);
+        const double* dz = args.in(z, nv);
         lp_evaluate_basic(lp->p, dx, ds, dy, dz, vbasis, out);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
     });
 }
 
@@ -1341,16 +1317,15 @@ int ipxk_split_apply(ipxk_context* c, const double* rhs, double* lhs, double* rh
         IPXK_REQUIRE(c && rhs && lhs, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "SplittedNormalMatrix not prepared");
         split_check_partition(c);
-        bind_device(c);
-        if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
+        Staged args(c);
+        c->ensure_partials();
         const size_t m = (size_t)c->m;
-        const double* drhs = stage_in(c, rhs, m, c->v_rhs);
-        double* dlhs = stage_out(c, lhs, m, c->v_lhs);
+        const double* drhs = args.in(rhs, m);
+        double* dlhs = args.out(lhs, m);
         const int np = split_apply_dev(c, drhs, dlhs, nullptr);
         IPXK_HIP(hipGetLastError());
         if (rhs_dot_lhs) *rhs_dot_lhs = reduce_partials_host(c, kPartCdot, np, false);
-        finish_out(c, lhs, dlhs, m);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
         check_sweep_abort(c);
     });
 }
@@ -1360,15 +1335,12 @@ static int inplace_solve(ipxk_context* c, double* x, bool forward) {
         IPXK_REQUIRE(c && x, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "SplittedNormalMatrix not prepared");
         split_check_partition(c);
-        bind_device(c);
-        const size_t m = (size_t)c->m;
-        double* dx = stage_out(c, x, m, c->v_lhs);
-        if (c->pointer_mode == IPXK_POINTER_HOST) staged_h2d(dx, x, m * sizeof(double), c->stream);
+        Staged args(c);
+        double* dx = args.inout(x, (size_t)c->m);
         if (forward) forward_solve_dev(c, dx, dx, true, nullptr);
         else backward_solve_dev(c, dx, dx, true, nullptr);
         IPXK_HIP(hipGetLastError());
-        finish_out(c, x, dx, m);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
         check_sweep_abort(c);
     });
 }
@@ -1381,14 +1353,13 @@ int ipxk_solve_dense(ipxk_context* c, const double* rhs, double* lhs, char trans
         IPXK_REQUIRE(c && rhs && lhs, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "SplittedNormalMatrix not prepared");
         split_check_partition(c);
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m;
-        const double* drhs = stage_in(c, rhs, m, c->v_rhs);
-        double* dlhs = stage_out(c, lhs, m, c->v_lhs);
+        const double* drhs = args.in(rhs, m);
+        double* dlhs = args.out(lhs, m);
         solve_dense_dev(c, drhs, dlhs, trans);
         IPXK_HIP(hipGetLastError());
-        finish_out(c, lhs, dlhs, m);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
         check_sweep_abort(c);
     });
 }
@@ -1407,19 +1378,17 @@ int ipxk_kkt_basis_solve(ipxk_context* c, const double* a, const double* b, doub
         IPXK_REQUIRE(c && a && b && x && y && iter && errflag, "NULL argument");
         IPXK_REQUIRE(c->split != nullptr, "KKTSolverBasis not factorized (split operator missing)");
         split_check_partition(c);
-        bind_device(c);
+        Staged args(c);
         const size_t m = (size_t)c->m, N = (size_t)(c->n + c->m);
-        const double* da = stage_in(c, a, N, c->k_a);
-        const double* db = stage_in(c, b, m, c->k_b);
-        double* dx = stage_out(c, x, N, c->k_x);
-        double* dy = stage_out(c, y, m, c->k_y);
+        const double* da = args.in(a, N);
+        const double* db = args.in(b, m);
+        double* dx = args.out(x, N);
+        double* dy = args.out(y, m);
         if (times) *times = ipxk_times{};
         CrResult r = kkt_basis_solve_dev(c, da, db, tol, maxiter, dx, dy, interrupt, interrupt_user, times);
         *iter = r.iter;
         *errflag = r.errflag;
-        finish_out(c, x, dx, N);
-        finish_out(c, y, dy, m);
-        IPXK_HIP(hipStreamSynchronize(c->stream));
+        args.finish();
         check_sweep_abort(c);
     });
 }
@@ -1431,20 +1400,9 @@ int ipxk_time_normal_apply(ipxk_context* c, const double* rhs_dev, double* lhs_d
         IPXK_REQUIRE(c && rhs_dev && lhs_dev && ms_total && reps > 0, "bad argument");
         IPXK_REQUIRE(c->normal_prepared, "NormalMatrix not prepared");
         bind_device(c);
-        if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
-        hipEvent_t e0, e1;
-        IPXK_HIP(hipEventCreate(&e0));
-        IPXK_HIP(hipEventCreate(&e1));
+        c->ensure_partials();
         int np = 0;
-        IPXK_HIP(hipEventRecord(e0, c->stream));
-        for (int r = 0; r < reps; r++) normal_apply_dev(c, c->W, rhs_dev, lhs_dev, &np, nullptr);
-        IPXK_HIP(hipEventRecord(e1, c->stream));
-        IPXK_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        IPXK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        *ms_total = ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+        *ms_total = time_on_stream(c, reps, [&] { normal_apply_dev(c, c->W, rhs_dev, lhs_dev, &np, nullptr); });
         IPXK_HIP(hipGetLastError());
     });
 }
@@ -1454,18 +1412,7 @@ int ipxk_debug_time_pass(ipxk_context* c, int which, const double* x_dev, double
                          double* ms_total) {
     return guarded([&] {
         bind_device(c);
-        hipEvent_t e0, e1;
-        IPXK_HIP(hipEventCreate(&e0));
-        IPXK_HIP(hipEventCreate(&e1));
-        IPXK_HIP(hipEventRecord(e0, c->stream));
-        for (int r = 0; r < reps; r++) debug_single_pass(c, which, x_dev, out_dev);
-        IPXK_HIP(hipEventRecord(e1, c->stream));
-        IPXK_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        IPXK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        *ms_total = ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+        *ms_total = time_on_stream(c, reps, [&] { debug_single_pass(c, which, x_dev, out_dev); });
     });
 }
 

@@ -44,6 +44,25 @@ struct LuState;         // lu.hip
 struct MaxvolState;     // internal.hpp
 struct NMatrix;         // nmatrix.hip
 
+struct Context;
+long lu_generation(const Context* c);   // lu.hip
+
+// A basis and its statuses on the host, together with the factorization they belong to: another factorization in the context
+// ends the state.
+struct LiveBasis {
+    bool live = false;
+    long lu_generation = -1;
+    std::vector<ipxint> basis, status;
+    bool current(const Context* c) const { return live && lu_generation == ipxk::lu_generation(c); }
+    void store(const Context* c, const std::vector<ipxint>& b, const std::vector<ipxint>& s) {
+        basis = b;
+        status = s;
+        lu_generation = ipxk::lu_generation(c);
+        live = true;
+    }
+    void clear() { live = false; }
+};
+
 struct Context {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -52,6 +71,11 @@ struct Context {
     // optional per-operator timing (ipxk_set_profiling): HIP events around every operator /
     // preconditioner / triangular-solve application of a solve, summed into ipxk_times afterwards
     bool profile_ops = false;
+    // host pointer mode: the device copies of one call's vector arguments, one slot per argument in the order the call declares
+    // them (api.hip); grow-only.  kStageSlots: the most vector arguments any entry point has (ipxk_newton_solve, 10 in + 6 out)
+    static constexpr int kStageSlots = 16;
+    DevBuf<double> stage_slots[kStageSlots];
+    DevBuf<unsigned char> stage_bytes;
     ipxint (*interrupt)(void*) = nullptr;   // ipxk_set_interrupt: Control::InterruptCheck for calls without a callback argument
     void* interrupt_user = nullptr;
     bool timing_active = false;
@@ -105,7 +129,6 @@ struct Context {
 
     // ---- CR workspaces (m-vectors) ----
     DevBuf<double> v_rhs, v_lhs, v_residual, v_sresidual, v_step, v_Cstep, v_Cres, v_pCstep;
-    DevBuf<double> v_resscale_in;       // staging for a host resscale
     DevBuf<double> partials;            // kNumPartialSlots * kPartialStride
     DevBuf<CrState> state;
     CrState* h_state = nullptr;         // pinned
@@ -118,14 +141,11 @@ struct Context {
 
     // ---- KKTSolverDiag ----
     DevBuf<double> resscale;            // m
-    DevBuf<double> k_a, k_b, k_x, k_y;  // staging for host vectors (n+m, m, n+m, m)
     DevBuf<double> k_tmp;               // n+m scratch
     bool kkt_diag_factorized = false;
 
     // ---- IPM::SolveNewtonSystem (newton.hip) ----
     DevBuf<double> nw_rhs1, nw_rhs2;    // n+m, m
-    DevBuf<double> nw_in[10], nw_out[6];   // staging for host vectors
-    DevBuf<unsigned char> nw_state;
 
     // ---- the IPM iterate (iterate.hip) ----
     DevBuf<double> it_x, it_xl, it_xu, it_y, it_zl, it_zu, it_partials;
@@ -158,16 +178,12 @@ struct Context {
     NMatrix* nmat = nullptr;               // N of the split operator as a matrix of its own (nmatrix.hip)
     // the factors, the operator and these statuses are the result of ipxk_ipm_starting_basis (starting_basis.hip): the main phase
     // (ipm_driver_dev with use_basis) goes on from them instead of the slack basis
-    bool sb_live = false;
-    long sb_lu_generation = -1;            // of those factors: another factorization in the context ends the state
-    std::vector<ipxint> sb_basis, sb_status;
+    LiveBasis sb;
     // DropPrimal / DropDual (drop.hip): Control::ipm_drop_primal / ipm_drop_dual (0, 0: off), the basis ipm_driver_dev ended with
     // when it did not start from a starting basis (what ipxk_ipm_drop_degenerate then works on), and Info::primal_dropped /
     // dual_dropped / the drop exchanges since the last driver began
     double drop_primal = 0.0, drop_dual = 0.0;
-    bool drv_live = false;
-    long drv_lu_generation = -1;
-    std::vector<ipxint> drv_basis, drv_status;
+    LiveBasis drv;
     ipxint sum_primal_dropped = 0, sum_dual_dropped = 0, sum_drop_updates = 0;
 
     // ---- multi-GPU ----
@@ -192,6 +208,7 @@ struct Context {
     Context() = default;
     ~Context();
     double* part(int slot) const { return partials.get() + (size_t)slot * kPartialStride; }
+    void ensure_partials() { if (partials.size() == 0) partials.resize((size_t)kNumPartialSlots * kPartialStride); }
 };
 
 // ---- model.hip: the model on the device, its gather matrices, the dense-column classification ----
@@ -242,11 +259,6 @@ enum TimeKind { kTimeOp = 0, kTimePrecond = 1, kTimeB = 2, kTimeBt = 3, kNumTime
 void time_mark(Context* c, int kind, bool begin);      // no-op unless timing is active
 void time_start(Context* c, ipxk_times* times);        // called by a solve before it enqueues work
 void time_collect(Context* c, ipxk_times* times);      // after the solve's stream sync
-
-// staging of vector arguments according to the pointer mode
-const double* stage_in(Context* c, const double* p, size_t len, DevBuf<double>& buf);
-double* stage_out(Context* c, double* p, size_t len, DevBuf<double>& buf);
-void finish_out(Context* c, double* user, const double* dev, size_t len);
 
 // ---- spmv.hip ----
 void normal_apply_dev(Context* c, const double* W, const double* rhs, double* lhs, int* ndot,
@@ -333,6 +345,12 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
 uint64_t model_fingerprint(Context* c, const double* b, const double* cc, const double* lb, const double* ub);
 
 // ---- finish.hip ----
+// before a new iterate is loaded: a live basis belongs to the iterate it was built from, and so does the postprocessing
+inline void begin_new_iterate(Context* c) {
+    c->sb.clear();
+    c->drv.clear();
+    c->postprocessed = false;
+}
 // every call that advances the iterate refuses a postprocessed one with this
 constexpr const char* kPostprocessedRefusal =
     "the resident iterate has been postprocessed (ipxk_iterate_postprocess) and no longer advances: load an iterate again "
@@ -429,7 +447,6 @@ void lu_get_factors(Context* c, ipxint* Lp, ipxint* Li, double* Lx, ipxint* Up, 
                     ipxint* rowperm, ipxint* colperm, ipxint* dependent);
 void split_prepare_lu(Context* c, const ipxint* status, const double* colscale);
 void destroy_lu(LuState*);
-long lu_generation(const Context* c);
 void lu_invalidate(Context* c);          // the factors of an earlier factorization are no longer handed out
 // ---- maxvolume.hip ----
 void maxvolume_dev(Context* c, const ipxint* status, const double* colscale, const ipxk_maxvolume_params* prm,

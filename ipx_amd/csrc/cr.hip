@@ -545,7 +545,7 @@ static void ensure_workspaces(Context* c) {
         c->v_residual.resize(m); c->v_sresidual.resize(m); c->v_step.resize(m);
         c->v_Cstep.resize(m); c->v_Cres.resize(m); c->v_pCstep.resize(m);
     }
-    if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
+    c->ensure_partials();
     if (c->state.size() == 0) c->state.resize(1);
     if (!c->h_state) IPXK_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_state), sizeof(CrState)));
     if (!c->ev_a) { IPXK_HIP(hipEventCreate(&c->ev_a)); IPXK_HIP(hipEventCreate(&c->ev_b)); }

@@ -474,12 +474,11 @@ void ipm_drop_degenerate_dev(Context* c, const double* b, const double* cc, cons
     IPXK_REQUIRE(!comm_active(c), kDeviceLuRefusal);
     IPXK_REQUIRE(c->it_set, "no iterate on the device (ipxk_iterate_set)");
     IPXK_REQUIRE(!c->postprocessed, kPostprocessedRefusal);
-    const bool from_sb = c->sb_live && c->sb_lu_generation == lu_generation(c);
-    const bool from_drv = !from_sb && c->drv_live && c->drv_lu_generation == lu_generation(c);
-    IPXK_REQUIRE(from_sb || from_drv, "no live basis: call ipxk_ipm_starting_basis or ipxk_ipm_driver_basis first");
+    IPXK_REQUIRE(c->sb.current(c) || c->drv.current(c), "no live basis: call ipxk_ipm_starting_basis or ipxk_ipm_driver_basis first");
+    LiveBasis& live = c->sb.current(c) ? c->sb : c->drv;
     const int64_t N = c->n + c->m;
     hipStream_t s = c->stream;
-    std::vector<ipxint> basis = from_sb ? c->sb_basis : c->drv_basis, status = from_sb ? c->sb_status : c->drv_status;
+    std::vector<ipxint> basis = live.basis, status = live.status;
     ipxk_drop_info I{};
     // the gate (:36), on the objectives without the offset
     double obj[3];
@@ -496,12 +495,9 @@ void ipm_drop_degenerate_dev(Context* c, const double* b, const double* cc, cons
         IPXK_HIP(hipStreamSynchronize(s));
     }
     if (obj[0] >= obj[1]) {
-        (from_sb ? c->sb_live : c->drv_live) = false;      // (an exception inside the pass leaves no live basis)
+        live.clear();                                       // (an exception inside the pass leaves no live basis)
         ipm_drop_dev(c, basis, status, colscale, &I, log, log_cap, interrupt, user);
-        if (!I.errflag) {
-            if (from_sb) { c->sb_basis = basis; c->sb_status = status; c->sb_lu_generation = lu_generation(c); c->sb_live = true; }
-            else { c->drv_basis = basis; c->drv_status = status; c->drv_lu_generation = lu_generation(c); c->drv_live = true; }
-        }
+        if (!I.errflag) live.store(c, basis, status);
     }
     if (basis_out) std::copy(basis.begin(), basis.end(), basis_out);
     if (status_out) std::copy(status.begin(), status.end(), status_out);

@@ -218,7 +218,8 @@ void iterate_postprocess_dev(Context* c, const double* cc, const double* lb, con
                            c->it_y.get(), V);
     IPXK_HIP(hipGetLastError());
     c->postprocessed = true;
-    c->sb_live = c->drv_live = false;                         // the main phase does not go on from a postprocessed iterate
+    c->sb.clear();                                            // the main phase does not go on from a postprocessed iterate
+    c->drv.clear();
 }
 
 void iterate_dropping_residuals_dev(Context* c, const double* lb, const double* ub, double out2[2]) {
@@ -277,8 +278,7 @@ void ipm_solve_dev(Context* c, const double* b, const double* cc, const double* 
     };
     auto run = [&] {                            // RunIPM, :334-359
         if (!prm->use_resident_point) {
-            c->sb_live = c->drv_live = false;
-            c->postprocessed = false;
+            begin_new_iterate(c);
             ipm_starting_point_dev(c, b, cc, lb, ub, &ip, &gi, interrupt, user);
             info->status_ipm = gi.status_ipm;
             info->errflag = gi.errflag;

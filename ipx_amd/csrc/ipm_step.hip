@@ -294,12 +294,12 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
     if (use_basis) {
         basis.resize((size_t)c->m); status.resize((size_t)(c->n + c->m)); colscale.resize((size_t)(c->n + c->m));
         c->sum_primal_dropped = c->sum_dual_dropped = c->sum_drop_updates = 0;
-        c->drv_live = false;
+        c->drv.clear();
     }
     bool first_factorize = true;
-    if (use_basis && c->sb_live && c->sb_lu_generation != lu_generation(c)) c->sb_live = false;    // the factors are no longer its
-    const bool from_starting_basis = use_basis && c->sb_live;
-    if (from_starting_basis) { basis = c->sb_basis; status = c->sb_status; first_factorize = false; }
+    if (use_basis && !c->sb.current(c)) c->sb.clear();    // the factors are no longer its
+    const bool from_starting_basis = use_basis && c->sb.live;
+    if (from_starting_basis) { basis = c->sb.basis; status = c->sb.status; first_factorize = false; }
     constexpr double kDivergeTol = 1e6;                  // src/ipm.h:55
     *info = ipxk_ipm_info{};
     const int N = (int)(c->n + c->m);
@@ -373,17 +373,12 @@ void ipm_driver_dev(Context* c, const double* b, const double* cc, const double*
         if (errflag == 999) { info->status_ipm = 5; info->errflag = 0; }           // IPX_ERROR_interrupt_time -> time_limit
         else { info->status_ipm = 8; info->errflag = errflag; }                    // failed
     }
-    if (from_starting_basis) {
-        // a later call goes on from the basis this one ended with -- unless it ended inside a Factorize
-        c->sb_live = info->errflag == 0 && info->status_ipm != 8 && !ended_in_factorize;
-        if (c->sb_live) { c->sb_basis = basis; c->sb_status = status; c->sb_lu_generation = lu_generation(c); }
-    }
-    if (use_basis && !from_starting_basis && !first_factorize) {
-        // the basis ipxk_ipm_drop_degenerate works on after a phase that built its own -- unless it ended inside a Factorize
-        c->drv_live = info->errflag == 0 && info->status_ipm != 8 && !ended_in_factorize;
-        if (c->drv_live) { c->drv_basis = basis; c->drv_status = status; c->drv_lu_generation = lu_generation(c); }
-    }
     if (use_basis && !first_factorize) {
+        // a later call goes on from the basis this one ended with, and ipxk_ipm_drop_degenerate works on the basis of a phase that
+        // built its own -- unless it ended inside a Factorize
+        LiveBasis& ended_with = from_starting_basis ? c->sb : c->drv;
+        if (info->errflag == 0 && info->status_ipm != 8 && !ended_in_factorize) ended_with.store(c, basis, status);
+        else ended_with.clear();
         if (basis_out) std::copy(basis.begin(), basis.end(), basis_out);
         if (status_out) std::copy(status.begin(), status.end(), status_out);
     }

@@ -325,7 +325,7 @@ void objectives_local(Context* c, const double* b, const double* cc, const doubl
         out4[0] = pobj; out4[1] = 0.0; out4[2] = dobj; out4[3] = 0.0;
         return;
     }
-    if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
+    c->ensure_partials();
     hipLaunchKernelGGL(iterate_objectives_kernel, dim3(g), dim3(kBlock), 0, s, n, m, c->it_state.get(), b, cc, lb, ub,
                        c->it_x.get(), c->it_y.get(), c->it_zl.get(), c->it_zu.get(), c->it_partials.get());
     EpiObjFixed ef{{}, c->it_state.get(), c->it_x.get()};

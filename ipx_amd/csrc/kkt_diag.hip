@@ -79,7 +79,7 @@ void kkt_diag_factorize_dev(Context* c, const double* xl, const double* xu, cons
     c->kkt_diag_factorized = false;
     c->W_own.resize((size_t)n + m);
     c->resscale.resize(m > 0 ? m : 1);
-    if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
+    c->ensure_partials();
     const int g = vec_grid(n + m);
     if (xl) {
         hipLaunchKernelGGL(kkt_weights_kernel, dim3(g), dim3(kBlock), 0, s, n + m, xl, xu, zl, zu,

@@ -273,7 +273,8 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
     const double dependency_tol = std::max(0.0, prm ? prm->dependency_tol : 1e-6);
     const ipxint max_etas = prm ? prm->max_etas : 0;
     ipxk_starting_basis_info I{};
-    c->sb_live = c->drv_live = false;
+    c->sb.clear();
+    c->drv.clear();
     maxvol_drop_etas(c);                       // an eta file of an earlier Maxvolume: history, the slack basis is factorized below
     if (!c->maxvol) c->maxvol = new MaxvolState;
     MaxvolState& M = *c->maxvol;
@@ -462,10 +463,7 @@ void ipm_starting_basis_dev(Context* c, const double* b, const double* cc, const
     IPXK_HIP(hipStreamSynchronize(s));
     IPXK_HIP(hipGetLastError());
     check_sweep_abort(c);
-    c->sb_basis = basis_h;
-    c->sb_status = status_h;
-    c->sb_lu_generation = lu_generation(c);
-    c->sb_live = true;
+    c->sb.store(c, basis_h, status_h);
     I.seconds = now_s() - t_start;
     if (basis_out) std::copy(basis_h.begin(), basis_h.end(), basis_out);
     if (status_out) std::copy(status_h.begin(), status_h.end(), status_out);

@@ -215,7 +215,7 @@ static void finish_prepare(Context* c, SplitOperator* S, const ipxint* status, c
     IPXK_HIP(hipMemsetAsync(S->xcc_slots.get(), 0, 64 * sizeof(unsigned long long), s));
     S->abort_flag.resize(1);
     IPXK_HIP(hipMemsetAsync(S->abort_flag.get(), 0, sizeof(int), s));
-    if (c->partials.size() == 0) c->partials.resize((size_t)kNumPartialSlots * kPartialStride);
+    c->ensure_partials();
     IPXK_HIP(hipStreamSynchronize(s));
 }
 
